@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- NuboFaceDetector Haar hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the roofline of the timed steps).
+--full adds what takes runs or checks of its own: the last step's boxes against the oracle (boxes_match), the CPU baseline
+and the OpenCV probe, and the secondary table (latency mode, host frames, content sweep, the other BASELINE configs).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float64, fixed shapes).
 
 Workload (BASELINE.json configs[1]): NuboFaceDetector, one 1920x1080 BGR stream per
 GPU, full-resolution mode (width-to-process = 1920), scaleFactor 1.1, minNeighbors 3,
@@ -19,6 +24,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "nubomedia-vca_amd")):
@@ -365,6 +371,62 @@ def secondary_table(ctx, casc, props, frames_np, W, H, F, dev, args, xml_face):
     return tab
 
 
+def submit_frames(pool, W, H, F, rank, content, base_faces, multi_stream, ticks):
+    """The timed frames, [tick][slot] of futures on `pool`: every frame is seeded on its own, so the arrays are those one thread
+    would make.  The gray fields are queued before the frames built on them (a worker waits only on work already started)."""
+    from nubovca import synth
+    sx, sy = W / 1920.0, H / 1080.0
+    if not multi_stream:
+        # 4 x F consecutive synthetic frames of this rank's stream (stream id = rank), faces drifting 8 px/frame: four DISTINCT sets of F
+        # frames cycled through the timed steps -- 4 x 199 MB of input at 32 x 1080p, beyond the 256 MB Infinity Cache, so no step
+        # finds its frames on-die.  Sets 1 .. 3 are the 1/f fields of set 0 mirrored (left-right, top-bottom, both: other bytes at
+        # every address, the same statistics, a quarter of the generation time) with the templates pasted afterwards.
+        base = [pool.submit(synth.make_gray, W, H, synth.frame_seed(rank, i), content) for i in range(F)]
+
+        def frame(r, i):
+            g = base[i].result()
+            if r & 1:
+                g = g[:, ::-1]
+            if r & 2:
+                g = g[::-1]
+            k = r * F + i
+            faces = [(int(((x + 8 * k) % 1500) * sx), int(y * sy), int(s * min(sx, sy))) for (x, y, s) in base_faces]
+            return synth.gray_to_bgr(synth.paste_faces(np.ascontiguousarray(g), faces, synth.frame_seed(rank, k)), synth.frame_seed(rank, k))
+        return [[pool.submit(frame, r, i) for i in range(F)] for r in range(ticks)]
+    # F streams (ids rank*F..), static per-stream background, templates moving 8 px per tick
+    bgs = [pool.submit(synth.make_gray, W, H, synth.frame_seed(rank * F + s, 0), content) for s in range(F)]
+
+    def frame(t, s):
+        faces = [(int((x + 8 * t + 16 * (s % 7)) * sx), int(y * sy), int(sz * min(sx, sy))) for (x, y, sz) in base_faces]
+        return synth.gray_to_bgr(synth.paste_faces(bgs[s].result(), faces, s), synth.frame_seed(rank * F + s, 0))
+    return [[pool.submit(frame, t, s) for s in range(F)] for t in range(ticks)]
+
+
+def dump_outputs(d, faces, tracks=None, track_cap=256):
+    """What the last timed step handed its caller, as DIR/<name>.npy in float64 with fixed shapes (rows past a frame's count are -1):
+    per frame the face count, the boxes (x, y, w, h) and the track ids; with the trackers, per frame their box count and boxes."""
+    os.makedirs(d, exist_ok=True)
+    n = len(faces)
+    counts = np.array([len(b) for b, _ in faces], np.float64)
+    boxes = np.full((n, MAX_BOXES, 4), -1.0)
+    ids = np.full((n, MAX_BOXES), -1.0)
+    for i, (b, k) in enumerate(faces):
+        b = np.asarray(b).reshape(-1, 4)
+        boxes[i, :len(b)] = b
+        ids[i, :len(b)] = np.asarray(k).reshape(-1)
+    out = {"face_counts": counts, "face_boxes": boxes, "face_ids": ids}
+    if tracks is not None:
+        tb = np.full((n, track_cap, 4), -1.0)
+        for i, b in enumerate(tracks):
+            b = np.asarray(b).reshape(-1, 4)
+            tb[i, :len(b)] = b
+        out["tracker_counts"] = np.array([len(b) for b in tracks], np.float64)
+        out["tracker_boxes"] = tb
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(out)
+
+
 def boxes_equal(got, exp):
     if len(got) != len(exp):
         return False
@@ -418,8 +480,12 @@ def main():
     ap.add_argument("--scale-factor-pct", type=int, default=10)
     ap.add_argument("--content", default="natural", choices=["natural", "noise", "gradient"])
     ap.add_argument("--faces", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs (cpu_baseline, boxes_match, the OpenCV probe)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary table (single-frame latency, host-frame rates, content sweep)")
+    ap.add_argument("--full", action="store_true", help="also the oracle legs (boxes_match, cpu_baseline, the OpenCV probe) and the secondary table; "
+                                                         "a plain run times the steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's boxes and ids; the trackers' boxes) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle legs (cpu_baseline, boxes_match, the OpenCV probe)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary table (single-frame latency, host-frame rates, content sweep)")
     ap.add_argument("--host-frames", action="store_true", help="feed host buffers (PCIe-inclusive rate; not `value`)")
     ap.add_argument("--pipeline", action="store_true", help="(the default since round 2) nvca_face_batch_submit / _collect with two batches in flight")
     ap.add_argument("--sync", action="store_true", help="one synchronous nvca_face_batch_process call per step instead of the submit / collect serving loop")
@@ -434,17 +500,39 @@ def main():
                          "the bench's own content so that each stage rejects about half of what reaches it (a trained cascade's profile); "
                          "standin: rounds 1-3's cascade (thresholds from i.i.d. noise: non-monotone stage selectivities on this content)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    try:
+        _cores = len(os.sched_getaffinity(0))
+    except AttributeError:
+        _cores = os.cpu_count() or 1
+    from nubovca import synth
+    if args.workload == "streams720p":
+        args.width, args.height = 1280, 720
+        args.frames_per_step = args.streams_per_gpu or 32
+    elif args.workload == "face_tracker":
+        args.frames_per_step = args.streams_per_gpu or 8
+    multi_stream = args.workload != "face1080p"
+    W, H, F = args.width, args.height, args.frames_per_step
+    TICKS = 4
+    base_faces = [(200, 150, 300), (900, 400, 180), (1400, 100, 120), (1500, 700, 240)][:args.faces]
+    # the seeded inputs (cascade, frames) are made on host threads while torch and the device come up: numpy releases the GIL
+    # in the bulk of this work, and the cascade's calibration (the longest single piece) runs beside the frames
+    gen = ThreadPoolExecutor(max(2, min(16, _cores) // max(world, 1)))
+    xml_job = gen.submit(synth.calibrated_cascade_xml if args.cascade == "calibrated" else synth.synthetic_cascade_xml)
+    frame_jobs = submit_frames(gen, W, H, F, rank, args.content, base_faces, multi_stream, TICKS)
+
     global torch, dist
     import torch as _torch
     import torch.distributed as _dist
     torch, dist = _torch, _dist
-    world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus != world:
         print("bench.py: --gpus %d but WORLD_SIZE=%d: the launcher's world size is what runs" % (args.gpus, world), file=sys.stderr)
-    rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # rehearsal hook for a one-GPU box: NVCA_BENCH_REHEARSAL=1 runs every rank on device 0 with the gloo backend, so the
     # N > 1 code path (barriers, max-over-ranks clock, per-tick gather) can be exercised without N GPUs
@@ -462,21 +550,10 @@ def main():
 
     # helper threads of the library (per-job host work, host-frame copies): a rank takes its share of the box's cores, no more --
     # N ranks x (a serving loop + up to 7 spinning helpers) would oversubscribe the host at N = 8
-    try:
-        _cores = len(os.sched_getaffinity(0))
-    except AttributeError:
-        _cores = os.cpu_count() or 1
     os.environ.setdefault("NVCA_HOST_THREADS", str(max(0, min(7, _cores // max(world, 1) - 1))))
-    from nubovca import capi, synth
-    if args.workload == "streams720p":
-        args.width, args.height = 1280, 720
-        args.frames_per_step = args.streams_per_gpu or 32
-    elif args.workload == "face_tracker":
-        args.frames_per_step = args.streams_per_gpu or 8
-    multi_stream = args.workload != "face1080p"
-    W, H, F = args.width, args.height, args.frames_per_step
+    from nubovca import capi
     w2p = args.width_to_process or W
-    xml = synth.calibrated_cascade_xml() if args.cascade == "calibrated" else synth.synthetic_cascade_xml()
+    xml = xml_job.result()
     ctx = capi.Context(local_rank)
     casc = ctx.load_cascade_xml(xml)
     props = {"width_to_process": w2p, "multi_scale_factor": args.scale_factor_pct}
@@ -484,37 +561,8 @@ def main():
     scale = W // w2p
     w, h = int(np.rint(W / scale)), int(np.rint(H / scale))
 
-    base_faces = [(200, 150, 300), (900, 400, 180), (1400, 100, 120), (1500, 700, 240)][:args.faces]
-    sx, sy = W / 1920.0, H / 1080.0
-    TICKS = 4
-    frames_np = []          # [tick][slot]
-    if not multi_stream:
-        # 4 x F consecutive synthetic frames of this rank's stream (stream id = rank), faces drifting 8 px/frame: four DISTINCT sets of F
-        # frames cycled through the timed steps -- 4 x 199 MB of input at 32 x 1080p, beyond the 256 MB Infinity Cache, so no step
-        # finds its frames on-die.  Sets 1 .. 3 are the 1/f fields of set 0 mirrored (left-right, top-bottom, both: other bytes at
-        # every address, the same statistics, a quarter of the generation time) with the templates pasted afterwards.
-        base = [synth.make_gray(W, H, synth.frame_seed(rank, i), args.content) for i in range(F)]
-        for r in range(TICKS):
-            row = []
-            for i in range(F):
-                g = base[i]
-                if r & 1:
-                    g = g[:, ::-1]
-                if r & 2:
-                    g = g[::-1]
-                k = r * F + i
-                faces = [(int(((x + 8 * k) % 1500) * sx), int(y * sy), int(s * min(sx, sy))) for (x, y, s) in base_faces]
-                row.append(synth.gray_to_bgr(synth.paste_faces(np.ascontiguousarray(g), faces, synth.frame_seed(rank, k)), synth.frame_seed(rank, k)))
-            frames_np.append(row)
-    else:
-        # F streams (ids rank*F..), static per-stream background, templates moving 8 px per tick
-        bgs = [synth.make_gray(W, H, synth.frame_seed(rank * F + s, 0), args.content) for s in range(F)]
-        for t in range(TICKS):
-            row = []
-            for s in range(F):
-                faces = [(int((x + 8 * t + 16 * (s % 7)) * sx), int(y * sy), int(sz * min(sx, sy))) for (x, y, sz) in base_faces]
-                row.append(synth.gray_to_bgr(synth.paste_faces(bgs[s], faces, s), synth.frame_seed(rank * F + s, 0)))
-            frames_np.append(row)
+    frames_np = [[f.result() for f in row] for row in frame_jobs]          # [tick][slot]
+    gen.shutdown()
     if args.host_frames:
         frames_t = [[capi.make_frame(f) for f in row] for row in frames_np]
         keep = frames_np
@@ -535,6 +583,7 @@ def main():
         bgra_frames = [[capi.make_frame(t.data_ptr(), W, H, W * 4, capi.MEM_DEVICE) for t in row] for row in bgra_keep]
         torch.cuda.synchronize()
     tick = [0]
+    tracks = [None]          # the trackers' boxes of the last step (--dump-outputs)
     from nubovca import sharding
     gather = sharding.TableGather(device=coll_dev) if world > 1 else None
 
@@ -556,7 +605,7 @@ def main():
         else:
             res = prepared[tick[0] % TICKS].process()
         if trackers is not None:
-            capi.tracker_batch_process(ctx, trackers, bgra_frames[tick[0] % TICKS], [33.3 * tick[0]] * F, cap=256)
+            tracks[0] = capi.tracker_batch_process(ctx, trackers, bgra_frames[tick[0] % TICKS], [33.3 * tick[0]] * F, cap=256)
         if world > 1:           # result gather (the only collective): fixed-size box table per stream tick, over RCCL;
             tab = sharding.pack_box_arrays(res.boxes, res.counts, rank=rank) if hasattr(res, "counts") else sharding.pack_boxes(res, MAX_BOXES, rank=rank)
             gather.submit(tab)                                      # asynchronous: it overlaps the next tick's kernels
@@ -589,6 +638,8 @@ def main():
     if pipelined:               # the batch queued by the last step has finished inside the timed region; unpack it now
         res = ctx.face_batch_collect(inflight[0], cap=MAX_BOXES)
         inflight[0] = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, as_list(res), tracks[0])
     ktimes = ctx.kernel_timing()
     ctx.enable_kernel_timing(False)
     n_boxes = float(np.mean([len(b) for b, _ in as_list(res)]))
@@ -692,7 +743,7 @@ def main():
                                    if args.cascade == "calibrated" else "standin: rounds 1-3's thresholds from i.i.d. noise")},
             "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # parity at the timed size, through the timed entry point: the boxes and ids of the LAST timed step against the
             # oracle replaying the same sequence of batches (FACE/kmsfacedetect.cpp:805-826)
             try:
@@ -710,7 +761,7 @@ def main():
                                                                  scale_factor=1 + args.scale_factor_pct / 100.0, budget_s=10.0)
             except Exception as e:
                 out["cpu_baseline"]["opencv"] = {"available": False, "note": "probe not run: %s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_secondary and args.workload == "face1080p" and not args.host_frames:
+        if args.full and world == 1 and not args.no_secondary and args.workload == "face1080p" and not args.host_frames:
             try:
                 out["secondary"] = secondary_table(ctx, casc, props, frames_np[0], W, H, F, dev, args, xml)
             except Exception as e:

@@ -1,13 +1,13 @@
 #!/bin/bash
 # usage: scripts/profile_round.sh <tag>   (run on the GPU box via gpurun)
-# 1. bench JSON (the default command line)  2. rocprofv3 kernel stats of the same command  3. PMC passes (FETCH_SIZE / WRITE_SIZE separately)
+# 1. bench JSON (the --full command line)  2. rocprofv3 kernel stats of the same command  3. PMC passes (FETCH_SIZE / WRITE_SIZE separately)
 # 4. phase stamps of k_band (diagnostic build)  5. the other workloads' scripts
 TAG=$1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profile_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B=$GRAFT_REPO_ROOT/bench.py
-timeout -k 10 600 python3 $B --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 600 python3 $B --steps 20 --warmup 3 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 timeout -k 10 300 python3 $B --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --host-frames > $OUT/bench_host_frames.json 2>> $OUT/bench.err
 timeout -k 10 300 python3 $B --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --sync --frames-per-step 1 > $OUT/bench_single_frame.json 2>> $OUT/bench.err
 timeout -k 10 300 python3 $B --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --cascade standin > $OUT/bench_standin_cascade.json 2>> $OUT/bench.err
