@@ -627,7 +627,7 @@ __device__ __forceinline__ TileLds carve_tile(unsigned char *lds, const TileRec 
     L.q0 = (unsigned short *)(lds + kTileSlots * 8);
     L.winx = L.q0 + 2 * kTileSlots; L.winy = L.winx + kTileWin;
     L.qn = (int *)(L.winy + kTileWin);                       // qn[0..2] rotating queue counters, qn[3] = list base, qn[4 ..] stage statistics
-    L.vnf_s = (double *)((unsigned char *)L.qn + 64);
+    L.vnf_s = (double *)((unsigned char *)L.qn + 128);       // behind the 32 counter words (tile_lds_fixed)
     L.cmap = (unsigned short *)(L.vnf_s + kTileSlots);
     L.rmap = L.cmap + ((t.span_x + 3) & ~3);
     L.T = (int *)(L.rmap + ((t.span_y + 3) & ~3));
@@ -641,7 +641,7 @@ __device__ __forceinline__ TileLds carve_tile(unsigned char *lds, const TileRec 
 // the tile's column / row lists for the maps, the window origins, the wave's sample-row offsets and the lane's sample
 // columns.  Round 2 (tile_commit): the maps are scattered into LDS and the sample rows x columns are copied global -> LDS by
 // LDS-DMA (global_load_lds_dword: the source address is per lane -- a gather of the tile's lattice columns -- the
-// destination is 64 consecutive words of the row, no registers in between).  A wave takes rows wave, wave + 16, ...; every
+// destination is 64 consecutive words of the row, no registers in between).  A wave takes rows wave, wave + NW, ...; every
 // transfer of the tile is in flight before the first one is waited for (register staging kept two rows per wave in
 // flight: the copy was a chain of dependent round trips).  The caller waits: s_waitcnt vmcnt(0) + barrier before T is read.
 struct TileCoords { int mapc, mapr, wx, wy; unsigned rowb, xcb[4]; };
@@ -651,7 +651,7 @@ __device__ __forceinline__ TileCoords tile_coords(const CascadeArgs &a, const Ti
     constexpr int NW = kTileThreads / 64;
     const unsigned short *__restrict__ cl = a.tcoords + t.col_off, *__restrict__ rl = a.tcoords + t.row_off;
     TileCoords c;
-    c.mapc = tid < t.ncol ? (int)cl[tid] : -1;               // ncol, nrow <= 256 < kTileThreads: one list entry per thread
+    c.mapc = tid < t.ncol ? (int)cl[tid] : -1;               // ncol <= 256, nrow <= kTileThreads (plan.cpp): one list entry per thread
     c.mapr = tid < t.nrow ? (int)rl[tid] : -1;
     c.wx = tid < t.nx ? a.pos[sc.xpos_off + t.ix0 + tid] : 0;
     c.wy = (tid >= 64 && tid < 64 + t.ny) ? a.pos[sc.ypos_off + t.iy0 + tid - 64] : 0;
@@ -720,7 +720,7 @@ __device__ __forceinline__ void queue_push(bool keep, int w, unsigned short *q, 
 //     takes every NW-th block of G stumps, records per lane (LStumpRec: three 16-byte loads from L1 / L2).  Lanes stay busy
 //     whatever n is: a late stage of 50 .. 213 stumps on a handful of windows is ONE step of the workgroup, not a chain of stumps
 //     walked by a handful of lanes.  With few windows left a round takes several stages at once (as many as fit one step of
-//     the workgroup: 768 window-stump pairs): the stumps of stages s+1, s+2 .. are evaluated for every window of the queue before
+//     the workgroup: kTileThreads window-stump pairs): the stumps of stages s+1, s+2 .. are evaluated for every window of the queue before
 //     it is known whether it passes stage s -- no side effects, and a window goes on iff it passes them all, exactly as if they
 //     had run one after the other; the rounds a surviving window waits for (a barrier pair and a round trip of records each)
 //     shrink from one per stage to one per 2 .. 7 stages.
@@ -730,6 +730,8 @@ __device__ __forceinline__ void queue_push(bool keep, int w, unsigned short *q, 
 // goes on iff it passes all of them, and which of them it fails first is seen by nobody.  Switch "stage_order".
 static constexpr int kStatStages = 6;         // stages 0 .. 5 take part in the adaptive order
 static constexpr int kPairMax = 32;           // windows up to which a round runs lane = (window, stump)
+static_assert(7 * kPairMax <= kTileSlots && 64 + kTileRows <= kTileThreads && kTileRows <= kTileWin,
+              "a round's seven accumulator rows fit the tile's accumulators; threads 64 .. 64 + kTileRows - 1 fill winy[kTileWin]");
 template <bool VNF_LDS>
 __device__ __forceinline__ void tile_stages(const CascadeArgs &a, const TileRec &t, const ScaleRec &sc, int slot, const TileLds &L, int ti = 0, int par = 0)
 {
@@ -979,7 +981,7 @@ __device__ __forceinline__ void tile_prologue(const CascadeArgs &a, const TileLd
     if (tid >= 1 && tid < kStatStages) L.qn[4 + 2 * kStatStages - 1 + tid] = tid < a.nstages ? a.stages[tid].count : 0;      // qn[16 .. 20]: behind the two sets of stat words
 }
 
-__global__ __launch_bounds__(kTileThreads, 2 * kTileThreads / 256) void k_tile(CascadeArgs a)
+__global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_tile(CascadeArgs a)
 {
     extern __shared__ __align__(16) unsigned char lds[];
     const int tid = threadIdx.x;
@@ -1013,7 +1015,7 @@ __global__ __launch_bounds__(kTileThreads, 2 * kTileThreads / 256) void k_tile(C
 // inside the wave -- a wave holds two whole window rows of the tile, so the reject bits it needs are its own ballot, and the
 // parity of the reject run that reaches the tile's left edge is carried from tile to tile in a register -- then run the
 // remaining stages as k_tile does.  No stage-0 pre-pass, no per-window global intermediates.
-__global__ __launch_bounds__(kTileThreads, 2 * kTileThreads / 256) void k_band(CascadeArgs a)
+__global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_band(CascadeArgs a)
 {
     extern __shared__ __align__(16) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1040,7 +1042,7 @@ __global__ __launch_bounds__(kTileThreads, 2 * kTileThreads / 256) void k_band(C
     unsigned carry = 0;                                    // wave-uniform: parity of the stage-0 reject run that ends at the previous tile's right edge, bit 0 / 1: the wave's first / second row
     // The coordinates of a tile (its record, this thread's list entries and window origin) are requested one tile ahead, right
     // behind the previous tile's sample transfers: their round trip passes under those transfers instead of standing at the
-    // head of every tile (768 threads leave the registers for it)
+    // head of every tile (six waves a SIMD leave the registers for it)
     TileRec t = load_const(a.tiles + b.first_tile);
     TileCoords tc = tile_coords(a, t, sc);
     tile_prologue(a, carve_tile(lds, t));                  // the fixed part of the carve-up does not depend on the tile

@@ -134,17 +134,24 @@ static constexpr int kDeepMaxSide = 64;            // patch side (distinct colum
 static constexpr int kDeepMaxSpan = 1280;          // largest corner offset + 1 the patch maps cover
 struct BandRec { int scale, iy0, ny, first_tile, ntiles, pad0, pad1, pad2; };
 static constexpr int kTileWin = 32;                 // windows per tile row (window id = ry * 32 + rx)
-static constexpr int kTileRows = 24;                // window rows per tile
+static constexpr int kTileRows = 16;                // window rows per tile
 static constexpr int kTileSlots = kTileWin * kTileRows;   // windows per tile = queue capacity = threads of the tile kernels
-// 768 threads: two tile workgroups take 24 of a CU's 32 wave slots (and 85 registers each) -- the bandwidth-bound
-// pre-processing kernels of the next batch fit beside them without ever keeping a tile workgroup from starting
+// 512 threads: three tile workgroups take 24 of a CU's 32 wave slots (6 waves a SIMD, 80 registers each) -- the third tile
+// fills the rounds that are chains of dependent LDS / L2 round trips; the bandwidth-bound pre-processing kernels
+// of the next batch fit beside them without ever keeping a tile workgroup from starting
 static constexpr int kTileThreads = kTileSlots;
-static constexpr int kTileLdsBudget = 76 * 1024;   // two tiles resident per CU (160 KiB LDS) and 8 KiB left for small workgroups beside them
+static constexpr int kTilesPerCu = 3;               // tile workgroups resident per CU
+static constexpr int kTileWavesPerSimd = (kTilesPerCu * kTileThreads / 64 + 3) / 4;     // the tile kernels' launch bounds (6: 80 VGPRs)
+// three tiles resident per CU (160 KiB LDS) and 4 KiB left for small workgroups beside them.  Not more: with a 53 KiB budget
+// (largest tile 54 260 B, three of them 1 KiB short of 160 KiB) the band kernel measured as with two tiles per CU
+static constexpr int kTileLdsBudget = 52 * 1024;
+static_assert(kTilesPerCu * kTileLdsBudget <= 160 * 1024 && kTilesPerCu * kTileThreads <= 32 * 64, "tile residency per CU");
 static constexpr int kTileMaxCols = 256;            // staged columns per tile (4 per lane)
 // LDS bytes the tile kernel needs for a tile (host sizing and kernel carve-up agree through these)
 __host__ __device__ inline int tile_pitch(int ncol) { return ncol | 1; }
 // fixed part (carve_tile in kernels_cascade.hip): stage accumulators (8 B a queue slot) | two window queues | window origins |
-// counters and stage statistics (32 words) | per-window variance normaliser
+// counters and stage statistics (32 words: qn[0 .. 3] queue counters and list base, qn[4 .. 15] two sets of stage statistics,
+// qn[16 .. 20] stump counts) | per-window variance normaliser
 __host__ __device__ inline int tile_lds_fixed()
 {
     return kTileSlots * 8 + 2 * kTileSlots * 2 + 4 * kTileWin + 128 + kTileSlots * 8;

@@ -325,7 +325,7 @@ int DetectPlan::build_tables(nvca_ctx *ctx, const Cascade &c, bool allow_tiles, 
     stage_thr.insert(stage_thr.end(), 8, 0.f);
     std::vector<long long> strip_w, tile_w;
     // A scan with few windows (the part detectors' working images and ROIs) cannot fill the GPU with 32 x 32-window tiles: a
-    // handful of workgroups would each walk a long chain of stages.  Smaller tiles give more workgroups and, with the same 1024
+    // handful of workgroups would each walk a long chain of stages.  Smaller tiles give more workgroups and, with the same kTileThreads
     // threads per tile, more stump partitions per window -- a shorter chain.  (Results do not depend on the tiling.)
     int max_tile = kTileWin;
     {
