@@ -3,7 +3,7 @@
 //
 // Rule of the library since round 4: an asynchronous copy is handed a caller's host pointer ONLY while that memory
 // lies inside a range the caller page-locked through nvca_host_register and has not released.  Everything else -- pageable
-// memory, and memory that WAS registered once -- crosses through page-locked memory of the context's own (api.cpp, BounceRing).
+// memory, and memory that WAS registered once -- crosses through page-locked memory of the context's own (host_copy.cpp, BounceRing).
 // The table also remembers which streams carried a copy out of / into a registered range since it was registered:
 // nvca_host_unregister drains exactly those before the pages are released (a copy still in flight on the copy stream or on a
 // lane must never lose its pages).

@@ -1,0 +1,204 @@
+// host_state.h -- host-side state and helpers that the library's host sources share (not part of the ABI): the workspace, the
+// cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect.cpp, roi_batch.cpp), and the
+// helpers one source calls in another.  plan.cpp, host_logic.cpp, cascade_xml.cpp and work_pool.cpp do not include it: the CPU
+// drivers under tests/ build those with host doubles of their own.
+#pragma once
+#include "nvca_internal.h"
+#include "plan.h"
+#include <chrono>
+#include <climits>
+#include <cmath>
+
+namespace nvca {
+
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline int cv_round(double v)
+{
+    if (!(v > -2147483648.5 && v < 2147483647.5)) return INT_MIN;   // _mm_cvtsd_si32 on overflow / inf
+    return (int)lrint(v);
+}
+inline double mono_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- runtime.cpp
+bool alloc_log();                                            // NVCA_ALLOC_LOG=1: allocations and host registrations on stderr
+void drain_timer_now(nvca_ctx *ctx);                         // kernel timing: event pairs -> times
+void drain_timer(nvca_ctx *ctx);                             // ... once many have piled up
+
+// what a cascade job leaves behind for the host: candidate list, box table, thresholds.  Three sets: [0] the synchronous
+// entry points, [1] / [2] the two batches that may be in flight through nvca_face_batch_submit / _collect
+struct ResultBufs {
+    DevBuf hits, grp, gthr, staging, srcptrs;        // staging / srcptrs: host frames on their way in, frame pointer table
+    PinnedBuf h_hits, h_grp, h_gthr, h_srcptrs;   // h_srcptrs: frame pointers on their way to the device array
+    std::vector<int> gthr_last;       // thresholds currently resident in gthr
+    void release() { hits.release(); grp.release(); gthr.release(); staging.release(); srcptrs.release(); h_hits.release(); h_grp.release(); h_gthr.release(); h_srcptrs.release(); gthr_last.clear(); }
+};
+// Working memory of the kernels, per LANE.  A lane is a HIP stream with its own planes and cascade scratch: whatever runs on a
+// lane is ordered by its stream, different lanes run side by side.  Everything uses lane 0 (the context's stream) except
+// the batched part detectors, which spread their streams' small, launch-bound jobs over all lanes (parts.cpp): the GPU then
+// holds several of those tiny kernels at a time instead of one.  What a job leaves for the host lives in ResultBufs regions
+// of its own, shared by all lanes.
+struct Lane {
+    DevBuf gray, hist, lut, bandsum, bandsq, sum, sqsum, tilted, staging, aux, failbits, vnf, deep;
+    int hist_clean = 0;               // leading histogram slots known to be all zero
+    void release_all()
+    {
+        gray.release(); hist.release(); lut.release(); bandsum.release(); bandsq.release(); sum.release();
+        sqsum.release(); tilted.release(); staging.release(); aux.release();
+        failbits.release(); vnf.release(); deep.release();
+    }
+};
+struct Workspace {
+    Lane lanes[kLanes];
+    int *cur_lane = nullptr;          // the context's current lane index
+    Lane &ln() { return lanes[*cur_lane]; }
+    ResultBufs res[3];
+    int cur_res = 0;
+    void release_all()
+    {
+        for (Lane &l : lanes) l.release_all();
+        for (ResultBufs &r : res) r.release();
+    }
+};
+
+// one cached geometry: source frame -> working image -> scan tables
+struct PyrLevel { double f; int szw, szh, winw, winh; size_t gray_off; int gpitch; int plane_off; };
+// Source rows a shrinking bilinear resize reads, when they form equal runs at a fixed period (integer ratios: a 1080p
+// frame shrunk by 12 reads rows 12k + 5 and 12k + 6 only).  Host frames then cross PCIe as one strided 2-D copy of those
+// rows -- into their natural places of the staged frame, so the kernels are unchanged -- instead of whole.
+struct RowCopy {
+    bool on = false;
+    int first = 0, period = 0, run = 0, count = 0;
+};
+
+struct GeomPlan {
+    ResizeTab tab;
+    RowCopy rowcopy;
+    DevBuf d_xofs, d_yofs, d_ialpha, d_ibeta;
+    DetectPlan det;
+    PreGeom g;
+    bool has_det = false;
+    uint64_t last_use = 0;                                    // plan cache is LRU-bounded (store_plan)
+    int inflight = 0;                                         // batches in flight that reference this plan: never evicted
+    // CV_HAAR_SCALE_IMAGE: pyramid levels, their resize tables, plane layout
+    std::vector<PyrLevel> lv;
+    std::vector<std::unique_ptr<GeomPlan>> level_tabs;
+    size_t gray_total = 0, plane_total = 0; int P = 0;
+    std::vector<int> fb_ladder;                               // FIND_BIGGEST: ladder position of each scale of the full-grid plan
+    DevBuf d_pyr, d_level_tabs; int pyr_maxw = 0, pyr_maxh = 0; bool pyr_ok = false;   // device level table (one-launch pyramid kernels)
+    ~GeomPlan() { level_tabs.clear(); d_xofs.release(); d_yofs.release(); d_ialpha.release(); d_ibeta.release(); d_pyr.release(); d_level_tabs.release(); }
+};
+
+// cascade scan over the integral planes of slots [0, n); fills raw[b] (canonical scale,y,x order)
+// group_thr (optional, [n]): cv::groupRectangles thresholds; when given and the plan allows it the grouping
+// runs on the device (k_group) and raw[b] comes back already grouped -- grouped[b] says which.
+// A job owns a result region (`r0` = index of its first frame in the caller's batch of `total` frames): its candidate
+// list and box table stay untouched while later jobs are enqueued, so several jobs can be queued before one sync.
+static constexpr int kMaxHitCap = 1 << 22;   // raw candidates per frame the lists are ever sized for (nvca_ctx_set_hit_capacity's limit)
+static constexpr int kGroupOutCap = 64;      // final boxes per frame returned by k_group (more -> host grouping)
+struct CascadeJob {
+    int r0 = 0, n = 0, total = 0;
+    bool dev_group = false;
+    bool counters_zeroed = false;   // the caller's k_lut launch reset the two list counters (cascade_counters())
+    unsigned cap = 0;
+    size_t first = 0;         // raw candidates fetched with the count (raw mode)
+    unsigned long long *d_hits = nullptr, *h_hits = nullptr;
+    int *d_grp = nullptr, *h_grp = nullptr;
+};
+
+// ---- plans.cpp
+void make_geom(PreGeom &g, int sw, int sh, int sstride, int cn, int w, int h);
+int ensure_ws(nvca_ctx *ctx, const PreGeom &g, int batch);
+int upload_tabs(nvca_ctx *ctx, std::vector<std::unique_ptr<GeomPlan>> &levels, DevBuf &blob);
+void run_integral(nvca_ctx *ctx, const PreGeom &g, const uint8_t *lut, int batch, const uint8_t *gray = nullptr, int *sum = nullptr,
+                  unsigned long long *sq = nullptr);
+int run_tilted(nvca_ctx *ctx, const PreGeom &g, const uint8_t *lut, int batch, const uint8_t *gray = nullptr, int *tilted = nullptr);
+int cascade_counters(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, unsigned long long **hits, unsigned long long **deep);
+int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, CascadeJob &job, const int *group_thr, bool want_group,
+                    hipEvent_t early_done = nullptr /* recorded behind the band / tile kernels, ahead of the late stages */);
+int cascade_collect(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, std::vector<std::vector<nvca_rect>> &raw,
+                    std::vector<char> *grouped, std::vector<std::vector<int>> *scale_of = nullptr);
+void group_all(std::vector<std::vector<nvca_rect>> &raw, int min_neighbors);
+GeomPlan *find_plan(nvca_ctx *ctx, const std::string &key);
+GeomPlan *store_plan(nvca_ctx *ctx, const std::string &key, std::unique_ptr<GeomPlan> gp);
+int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int stride, int cn, int cols, int rows,
+                  double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out);
+int get_resize_plan(nvca_ctx *ctx, int sw, int sh, int dw, int dh, GeomPlan **out);
+
+// ---- host_copy.cpp (caller_h2d / caller_h2d_rows / caller_d2h_rows: nvca_internal.h)
+hipStream_t stream_of_id(const nvca_ctx *ctx, int id);       // the stream a bit of HostRangeTable's stream mask stands for
+void ensure_pool(nvca_ctx *ctx);                             // the context's helper threads, created on first use
+int stage_2d(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width_bytes, size_t height, int mem);
+int unstage_2d(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width_bytes, size_t height, int mem);
+int finish_device_op(nvca_ctx *ctx);
+int check_img(nvca_ctx *ctx, const void *p, int w, int h, int stride, int bpp, int mem);
+size_t staging_need(const nvca_frame *frames, const int *idx, int n);
+int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n, int bpp, int r0 = 0, hipStream_t st = nullptr,
+                 size_t *off_io = nullptr, const RowCopy *rows = nullptr);
+bool frames_aligned4(const nvca_frame *frames, const int *idx, int n);
+
+// ---- detectMultiScale jobs (detect.cpp) and their small-image batches (roi_batch.cpp)
+struct FbStep { double factor, ystep; int winw, winh; };
+
+struct DetectJob {
+    // ---- request
+    int kind = 0;                                    // 0: scale-cascade scan, 1: CV_HAAR_SCALE_IMAGE, 2: CV_HAAR_FIND_BIGGEST_OBJECT
+    const nvca_cascade *casc = nullptr;
+    const void *img[kJobImages] = {nullptr}; int nimg = 1;       // plain scan / SCALE_IMAGE: images of one geometry share the launches
+    int cols = 0, rows = 0, stride = 0, mem = 0;
+    double sf = 1.1; int min_neighbors = 0, flags = 0, minw = 0, minh = 0, maxw = 0, maxh = 0;
+    bool raw_only = false;
+    // ---- result
+    std::vector<nvca_rect> out[kJobImages];
+    // ---- progress
+    int phase = 0;                                   // 0: new, 1: first launch set queued, 2: narrowed set queued, 3: done
+    int slots() const { return nimg; }
+    GeomPlan *gp = nullptr;                          // cached plan of the queued set (kept from eviction while queued)
+    std::unique_ptr<DetectPlan> own;                 // FIND_BIGGEST: this call's narrowed plan
+    DetectPlan *dp = nullptr;                        // plan of the queued set (null: nothing was queued)
+    CascadeJob cj; int gthr = 0;
+    // FIND_BIGGEST: the serial loop's state between the two sets
+    std::vector<FbStep> ladder; std::vector<std::vector<nvca_rect>> hits; std::vector<char> have; std::vector<int> ladder_of;
+    std::vector<nvca_rect> all; nvca_rect scanROI{0, 0, 0, 0}; bool narrowed_done = false; size_t fb_i = 0; int cur_minw = 0, cur_minh = 0;
+    int regrown = 0;                                 // launch sets re-run with a larger candidate list (at most one per set)
+    // small-image path (kernels_roi.hip): the job's steps of the queued launch and the candidates that came back
+    struct RoiStepInfo { double ystep, out_factor; int winw, winh, ladder; };
+    bool small = false;                              // the job runs on the small-image path (decided at its first round)
+    int roi_prev_phase = 0;                          // its phase before the queued set (a set that overflowed the list is queued again)
+    bool fused = false;                              // the queued set went into the round's k_roi launch
+    std::vector<RoiStepInfo> rinfo;
+    std::vector<unsigned> rkeys[kJobImages];         // per image: step << 26 | iy << 13 | ix, ascending (= OpenCV's serial order)
+    // FIND_BIGGEST on the small-image path, dense first launch (Switches::fb_dense): per step of the queued launch where its stage-0 reject bits
+    // lie in the launch's bitmap (word offset, words per grid row, grid size); per LADDER step what came back -- every window that passes the whole
+    // cascade, visited by the serial walk or not (iy << 13 | ix, ascending), and the reject bits of the step's full grid
+    struct RejInfo { int off, wpr, nx, ny; };
+    bool dense = false;                              // the queued launch was a dense one
+    std::vector<RejInfo> rej_info;                   // [step of the launch]
+    std::vector<std::vector<unsigned>> dense_hits;   // [ladder step]
+    std::vector<const unsigned long long *> rej_bits; std::vector<int> rej_wpr, rej_rows;      // [ladder step]: into the launch's page-locked bitmap (valid until the next launch of its buffer set: the job is advanced before)
+};
+
+struct RoiBatch {
+    std::vector<RoiJobDev> jobs; std::vector<RoiStep> steps; std::vector<unsigned char> tabs; std::vector<DetectJob *> owners; std::vector<int> owner_img;
+    std::vector<ScaleTable *> held;                 // stump tables of the launch: kept from eviction until it has been collected
+    int plane_words = 0, lev_bytes = 0, lane = 0; unsigned cap = 0; size_t first = 0;
+    size_t rej_words = 0;                           // stage-0 reject bitmaps of the launch's dense steps (u64 words)
+    void release() { for (ScaleTable *t : held) if (t->refs > 0) t->refs--; held.clear(); }
+    ~RoiBatch() { release(); }
+    RoiBatch() = default;
+    RoiBatch(const RoiBatch &) = delete; RoiBatch &operator=(const RoiBatch &) = delete;
+    // (a round object is reused from round to round: what the previous round held is released first)
+    void reset() { release(); jobs.clear(); steps.clear(); tabs.clear(); owners.clear(); owner_img.clear(); plane_words = 0; lev_bytes = 0; lane = 0; cap = 0; first = 0; rej_words = 0; }
+};
+
+// ---- roi_batch.cpp
+bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round);
+bool roi_grid(int cols, int rows, double ystep, int winw, int winh, int startX, int endX, int startY, int endY, RoiStep &st);
+int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j);
+int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap);
+int roi_collect(nvca_ctx *ctx, RoiBatch &rb);
+
+// ---- detect.cpp: NVCA_PART_STATS (diagnostic, one context at a time) -- where run_detect_jobs spends the host's time (parts.cpp prints them)
+extern double g_jobs_fine_s[6];        // roi_add_job, roi_launch, roi_collect, helper-thread advance, serial advance, small-path jobs (count)
+extern double g_jobs_enqueue_s, g_jobs_wait_s, g_jobs_advance_s;
+
+} // namespace nvca

@@ -1,0 +1,246 @@
+// imgproc.cpp -- the image primitives of the C ABI: cvtColor, resize, equalizeHist, the view-* outlines, the overlay, flip and
+// the integral images.
+#include "host_state.h"
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <algorithm>
+
+using namespace nvca;
+
+// =========================================================================
+// imgproc primitives
+// =========================================================================
+
+extern "C" {
+
+int nvca_bgr2gray(nvca_ctx *ctx, const void *src, int w, int h, int stride, int channels, int mem, void *dst, int dst_stride)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    if (channels != 3 && channels != 4) return NVCA_ERR_ARG;
+    int rc = check_img(ctx, src, w, h, stride, channels, mem);
+    if (rc || !dst || dst_stride < w) return NVCA_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    PreGeom g; make_geom(g, w, h, stride, channels, w, h);
+    if ((rc = ensure_ws(ctx, g, 1))) return rc;
+    nvca_frame f{src, w, h, stride, mem, 0};
+    // The frame pointer reaches the kernel through a pointer table that is uploaded asynchronously from page-locked host
+    // memory.  Callers that chain primitives without draining the stream (the part detectors queue many frames back to back)
+    // must not reuse a table entry whose upload may still be pending: every call takes the next entry of a ring.
+    static constexpr int kPtrRing = 1024;
+    Workspace &ws = *ctx->ws;
+    ResultBufs &rb = ws.res[ws.cur_res];
+    if (rb.srcptrs.ensure(kPtrRing * sizeof(void *)) || rb.h_srcptrs.ensure(kPtrRing * sizeof(void *))) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+    if (ctx->defer_device_sync > 0 && ++ctx->ptr_ring_used >= kPtrRing) {       // a full turn without a drain: drain once
+        NVCA_HIP_CHECK(ctx, hipDeviceSynchronize());
+        ctx->ptr_ring_used = 0;
+    }
+    const int slot = ctx->defer_device_sync > 0 ? ctx->ptr_ring_used : 0;
+    if ((rc = stage_frames(ctx, &f, nullptr, 1, channels, slot))) return rc;
+    { TimedLaunch t(ctx, NVCA_K_GRAY);
+      launch_gray(ctx->cs(), rb.srcptrs.as<const uint8_t *>() + slot, g, 0, nullptr, nullptr, nullptr, nullptr, w,
+                  ctx->ws->ln().gray.as<uint8_t>(), nullptr, 1, frames_aligned4(&f, nullptr, 1)); }
+    return unstage_2d(ctx, dst, dst_stride, ctx->ws->ln().gray.p, g.gpitch, w, h, mem);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_resize_linear(nvca_ctx *ctx, const void *src, int sw, int sh, int sstride, int channels, int mem, void *dst,
+                       int dw, int dh, int dstride)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    if (channels == 3) {
+        int rc3 = check_img(ctx, src, sw, sh, sstride, 3, mem);
+        if (rc3 || !dst || dw <= 0 || dh <= 0 || dstride < dw * 3) return NVCA_ERR_ARG;
+        (void)hipSetDevice(ctx->device);
+        Workspace &w3 = *ctx->ws;
+        const size_t sp = round_up((size_t)sw * 3, 64), dp3 = round_up((size_t)dw * 3, 64);
+        if (w3.ln().staging.ensure(sp * sh + 64) || w3.ln().aux.ensure(dp3 * dh + 64)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+        if ((rc3 = stage_2d(ctx, w3.ln().staging.p, sp, src, sstride, (size_t)sw * 3, sh, mem))) return rc3;
+        GeomPlan *gp3 = nullptr;
+        if ((rc3 = get_resize_plan(ctx, sw, sh, dw, dh, &gp3))) return rc3;
+        { TimedLaunch t(ctx, NVCA_K_RESIZE1);
+          launch_resize3(ctx->cs(), w3.ln().staging.as<uint8_t>(), sw, sh, (int)sp, gp3->tab.mode, gp3->d_xofs.as<int>(), gp3->d_ialpha.as<short>(),
+                         gp3->d_yofs.as<int>(), gp3->d_ibeta.as<short>(), gp3->tab.xmax, w3.ln().aux.as<uint8_t>(), dw, dh, (int)dp3); }
+        return unstage_2d(ctx, dst, dstride, w3.ln().aux.p, dp3, (size_t)dw * 3, dh, mem);
+    }
+    if (channels != 1) return NVCA_ERR_ARG;
+    int rc = check_img(ctx, src, sw, sh, sstride, 1, mem);
+    if (rc || !dst || dw <= 0 || dh <= 0 || dstride < dw) return NVCA_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    Workspace &ws = *ctx->ws;
+    PreGeom gs; make_geom(gs, sw, sh, sstride, 1, sw, sh);
+    PreGeom gd; make_geom(gd, sw, sh, sstride, 1, dw, dh);
+    GeomPlan *gp = nullptr;
+    if ((rc = get_resize_plan(ctx, sw, sh, dw, dh, &gp))) return rc;
+    if (mem == NVCA_MEM_DEVICE) {          // device images are read and written in place (ordered on the context's stream)
+        { TimedLaunch t(ctx, NVCA_K_RESIZE1);
+          launch_resize1(ctx->cs(), (const uint8_t *)src, sw, sh, sstride, gp->tab.mode, gp->d_xofs.as<int>(),
+                         gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,
+                         (uint8_t *)dst, dw, dh, dstride, nullptr); }
+        return finish_device_op(ctx);
+    }
+    if ((rc = ensure_ws(ctx, gs, 1)) || (rc = ensure_ws(ctx, gd, 1))) return rc;
+    if (ws.ln().aux.ensure(gd.gray_slot + 64)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+    if ((rc = stage_2d(ctx, ws.ln().gray.p, gs.gpitch, src, sstride, sw, sh, mem))) return rc;
+    { TimedLaunch t(ctx, NVCA_K_RESIZE1);
+      launch_resize1(ctx->cs(), ws.ln().gray.as<uint8_t>(), sw, sh, gs.gpitch, gp->tab.mode, gp->d_xofs.as<int>(),
+                     gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,
+                     ws.ln().aux.as<uint8_t>(), dw, dh, gd.gpitch, nullptr); }
+    return unstage_2d(ctx, dst, dstride, ws.ln().aux.p, gd.gpitch, dw, dh, mem);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_equalize_hist(nvca_ctx *ctx, const void *src, int w, int h, int stride, int mem, void *dst, int dst_stride)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    int rc = check_img(ctx, src, w, h, stride, 1, mem);
+    if (rc || !dst || dst_stride < w) return NVCA_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    Workspace &ws = *ctx->ws;
+    PreGeom g; make_geom(g, w, h, stride, 1, w, h);
+    if ((rc = ensure_ws(ctx, g, 1))) return rc;
+    if (mem == NVCA_MEM_DEVICE) {          // histogram of the caller's image, LUT applied straight into the destination (in place allowed)
+        NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.ln().hist.p, 0, 256 * sizeof(unsigned), ctx->cs()));
+        { TimedLaunch t(ctx, NVCA_K_GRAY); launch_hist(ctx->cs(), (const uint8_t *)src, w, h, stride, ws.ln().hist.as<unsigned>()); }
+        { TimedLaunch t(ctx, NVCA_K_LUT); launch_lut(ctx->cs(), ws.ln().hist.as<unsigned>(), w * h, ws.ln().lut.as<uint8_t>(), 1, 1); }
+        launch_apply_lut(ctx->cs(), (const uint8_t *)src, w, h, stride, ws.ln().lut.as<uint8_t>(), (uint8_t *)dst, dst_stride);
+        return finish_device_op(ctx);
+    }
+    if (ws.ln().aux.ensure(g.gray_slot + 64)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+    if ((rc = stage_2d(ctx, ws.ln().gray.p, g.gpitch, src, stride, w, h, mem))) return rc;
+    NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.ln().hist.p, 0, 256 * sizeof(unsigned), ctx->cs()));
+    { TimedLaunch t(ctx, NVCA_K_GRAY); launch_hist(ctx->cs(), ws.ln().gray.as<uint8_t>(), w, h, g.gpitch, ws.ln().hist.as<unsigned>()); }
+    { TimedLaunch t(ctx, NVCA_K_LUT); launch_lut(ctx->cs(), ws.ln().hist.as<unsigned>(), w * h, ws.ln().lut.as<uint8_t>(), 1, 1); }   // slot 0 left zeroed again
+    launch_apply_lut(ctx->cs(), ws.ln().gray.as<uint8_t>(), w, h, g.gpitch, ws.ln().lut.as<uint8_t>(), ws.ln().aux.as<uint8_t>(), g.gpitch);
+    return unstage_2d(ctx, dst, dst_stride, ws.ln().aux.p, g.gpitch, w, h, mem);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_draw_shapes(nvca_ctx *ctx, const nvca_frame *frame, int channels, const nvca_shape *shapes, int n)
+try {
+    // host frames need no device (and no context): plain loops over the mapped buffer
+    const bool host = frame && frame->mem == NVCA_MEM_HOST;
+    if (!frame || (!ctx && !host) || (channels != 3 && channels != 4) || n < 0 || (n > 0 && !shapes) || n > 1024) return NVCA_ERR_ARG;
+    if (!frame->data || frame->width <= 0 || frame->height <= 0 || frame->stride < frame->width * channels || (frame->mem != NVCA_MEM_HOST && frame->mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if ((shapes[i].kind != NVCA_SHAPE_RECT3 && shapes[i].kind != NVCA_SHAPE_RING4) || std::abs((long long)shapes[i].x) > (1 << 24) || std::abs((long long)shapes[i].y) > (1 << 24) ||
+            std::abs((long long)shapes[i].w) > (1 << 24) || std::abs((long long)shapes[i].h) > (1 << 24)) return NVCA_ERR_ARG;
+    if (!n) return NVCA_OK;
+    if (host) { draw_shapes_host((uint8_t *)frame->data, frame->width, frame->height, frame->stride, channels, shapes, n); return NVCA_OK; }
+    NVCA_LOCK_OR_FAIL(ctx);
+    int rc;
+    (void)hipSetDevice(ctx->device);
+    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = INT_MIN, by1 = INT_MIN;          // common bounding box, clipped to the frame
+    for (int i = 0; i < n; i++) {
+        const nvca_shape &sh = shapes[i];
+        int x0, y0, x1, y1;
+        if (sh.kind == NVCA_SHAPE_RING4) { const int r = (sh.w > 0 ? sh.w : 0) + 2; x0 = sh.x - r; x1 = sh.x + r; y0 = sh.y - r; y1 = sh.y + r; }
+        else { x0 = std::min(sh.x, sh.x + sh.w) - 1; x1 = std::max(sh.x, sh.x + sh.w) + 1; y0 = std::min(sh.y, sh.y + sh.h) - 1; y1 = std::max(sh.y, sh.y + sh.h) + 1; }
+        bx0 = std::min(bx0, x0); by0 = std::min(by0, y0); bx1 = std::max(bx1, x1); by1 = std::max(by1, y1);
+    }
+    bx0 = std::max(bx0, 0); by0 = std::max(by0, 0); bx1 = std::min(bx1, frame->width - 1); by1 = std::min(by1, frame->height - 1);
+    if (bx0 > bx1 || by0 > by1) return NVCA_OK;
+    void *d_shapes = nullptr;
+    if ((rc = part_table(ctx, shapes, (size_t)n * sizeof(nvca_shape), &d_shapes))) return rc;
+    launch_draw_shapes(ctx->cs(), (uint8_t *)frame->data, frame->width, frame->height, frame->stride, channels, (const nvca_shape *)d_shapes, n, bx0, by0, bx1, by1);
+    return finish_device_op(ctx);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_overlay_blend(nvca_ctx *ctx, const nvca_frame *frame, const nvca_rect *boxes, int n, const nvca_overlay *ov)
+try {
+    const bool host = frame && frame->mem == NVCA_MEM_HOST;
+    if (!frame || !ov || (!ctx && !host) || n < 0 || (n > 0 && !boxes) || n > 1024) return NVCA_ERR_ARG;
+    if (!frame->data || frame->width <= 0 || frame->height <= 0 || frame->stride < frame->width * 3 || (frame->mem != NVCA_MEM_HOST && frame->mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+    if (!ov->data || ov->width <= 0 || ov->height <= 0 || (ov->channels != 1 && ov->channels != 3 && ov->channels != 4) || ov->stride < ov->width * ov->channels ||
+        ov->width > 8192 || ov->height > 8192) return NVCA_ERR_ARG;
+    if (!(std::fabs(ov->offset_x_percent) <= 64 && std::fabs(ov->offset_y_percent) <= 64 && ov->width_percent >= 0 && ov->width_percent <= 64 && ov->height_percent >= 0 && ov->height_percent <= 64)) return NVCA_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if (std::abs((long long)boxes[i].x) > (1 << 20) || std::abs((long long)boxes[i].y) > (1 << 20) || boxes[i].w < 0 || boxes[i].h < 0 || boxes[i].w > (1 << 14) || boxes[i].h > (1 << 14)) return NVCA_ERR_ARG;
+    if (!n || ov->height_percent == 0 || ov->width_percent == 0) return NVCA_OK;           // FACE/kmsfacedetect.cpp:436-439
+    if (host) { overlay_blend_host((uint8_t *)frame->data, frame->width, frame->height, frame->stride, boxes, n, *ov); return NVCA_OK; }
+    NVCA_LOCK_OR_FAIL(ctx);
+    (void)hipSetDevice(ctx->device);
+    int rc;
+    const size_t bytes = (size_t)ov->stride * (ov->height - 1) + (size_t)ov->width * ov->channels;
+    if (ctx->overlay_img.ensure(bytes + 64)) { ctx->set_error("allocation failed (overlay image)"); return NVCA_ERR_NOMEM; }
+    if ((rc = caller_h2d(ctx, ctx->overlay_img.p, ov->data, bytes, ctx->cs()))) return rc;
+    for (int b = 0; b < n; b++) {            // in order: a later box overwrites an earlier one where they overlap
+        const OverlayPlace p = overlay_place(boxes[b], *ov);
+        if (p.w <= 0 || p.h <= 0) continue;
+        GeomPlan *gp = nullptr;
+        if ((rc = get_resize_plan(ctx, ov->width, ov->height, p.w, p.h, &gp))) return rc;
+        launch_overlay(ctx->cs(), (uint8_t *)frame->data, frame->width, frame->height, frame->stride, p, ctx->overlay_img.as<uint8_t>(), ov->height, ov->stride, ov->channels,
+                       gp->tab.mode, gp->d_xofs.as<int>(), gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax);
+    }
+    // the image is the caller's: the upload must have left it before the call returns
+    NVCA_LAUNCH_CHECK(ctx);
+    NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
+    return NVCA_OK;
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_flip_horizontal(nvca_ctx *ctx, const void *src, int w, int h, int stride, int mem, void *dst, int dst_stride)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    int rc = check_img(ctx, src, w, h, stride, 1, mem);
+    if (rc || !dst || dst_stride < w) return NVCA_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    Workspace &ws = *ctx->ws;
+    PreGeom g; make_geom(g, w, h, stride, 1, w, h);
+    if (mem == NVCA_MEM_DEVICE && src != dst) {
+        launch_flip_h(ctx->cs(), (const uint8_t *)src, w, h, stride, (uint8_t *)dst, dst_stride);
+        return finish_device_op(ctx);
+    }
+    if ((rc = ensure_ws(ctx, g, 1))) return rc;
+    if (ws.ln().aux.ensure(g.gray_slot + 64)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+    if ((rc = stage_2d(ctx, ws.ln().gray.p, g.gpitch, src, stride, w, h, mem))) return rc;
+    launch_flip_h(ctx->cs(), ws.ln().gray.as<uint8_t>(), w, h, g.gpitch, ws.ln().aux.as<uint8_t>(), g.gpitch);
+    return unstage_2d(ctx, dst, dst_stride, ws.ln().aux.p, g.gpitch, w, h, mem);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_integral(nvca_ctx *ctx, const void *src, int w, int h, int stride, int mem, int32_t *sum, double *sqsum)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    int rc = check_img(ctx, src, w, h, stride, 1, mem);
+    if (rc || !sum) return NVCA_ERR_ARG;
+    if (mem != NVCA_MEM_HOST) { ctx->set_error("nvca_integral: host output only"); return NVCA_ERR_ARG; }
+    (void)hipSetDevice(ctx->device);
+    Workspace &ws = *ctx->ws;
+    PreGeom g; make_geom(g, w, h, stride, 1, w, h);
+    if ((rc = ensure_ws(ctx, g, 1))) return rc;
+    if ((rc = stage_2d(ctx, ws.ln().gray.p, g.gpitch, src, stride, w, h, mem))) return rc;
+    run_integral(ctx, g, nullptr, 1);
+    rc = unstage_2d(ctx, sum, (size_t)(w + 1) * 4, ws.ln().sum.p, (size_t)g.spitch * 4, (size_t)(w + 1) * 4, h + 1, NVCA_MEM_HOST);
+    if (rc) return rc;
+    if (sqsum) {                                       // device layout: u32 low-word plane, then u8 high-byte plane
+        const size_t n = (size_t)(w + 1) * (h + 1);
+        std::vector<unsigned> lo(n); std::vector<uint8_t> hi(n);
+        rc = unstage_2d(ctx, lo.data(), (size_t)(w + 1) * 4, ws.ln().sqsum.p, (size_t)g.spitch * 4, (size_t)(w + 1) * 4, h + 1, NVCA_MEM_HOST);
+        if (rc) return rc;
+        rc = unstage_2d(ctx, hi.data(), (size_t)(w + 1), ws.ln().sqsum.as<unsigned>() + g.sum_slot, (size_t)g.spitch, (size_t)(w + 1), h + 1, NVCA_MEM_HOST);
+        if (rc) return rc;
+        for (size_t i = 0; i < n; i++) sqsum[i] = (double)(((unsigned long long)hi[i] << 32) | lo[i]);
+    }
+    return NVCA_OK;
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_integral_tilted(nvca_ctx *ctx, const void *src, int w, int h, int stride, int mem, int32_t *tilted)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    int rc = check_img(ctx, src, w, h, stride, 1, mem);
+    if (rc || !tilted) return NVCA_ERR_ARG;
+    if (mem != NVCA_MEM_HOST) { ctx->set_error("nvca_integral_tilted: host output only"); return NVCA_ERR_ARG; }
+    (void)hipSetDevice(ctx->device);
+    Workspace &ws = *ctx->ws;
+    PreGeom g; make_geom(g, w, h, stride, 1, w, h);
+    if ((rc = ensure_ws(ctx, g, 1))) return rc;
+    if ((rc = stage_2d(ctx, ws.ln().gray.p, g.gpitch, src, stride, w, h, mem))) return rc;
+    if ((rc = run_tilted(ctx, g, nullptr, 1))) return rc;
+    return unstage_2d(ctx, tilted, (size_t)(w + 1) * 4, ws.ln().tilted.p, (size_t)g.spitch * 4, (size_t)(w + 1) * 4, h + 1, NVCA_MEM_HOST);
+}
+NVCA_API_CATCH(ctx)
+
+} // extern "C"

@@ -13,7 +13,7 @@
 //   * OpenCV's adaptive x step (ix += result != 0 ? 1 : 2) is resolved per row from the stage-0 reject bits of the 64-window
 //     chunks a wave walks left to right (the parity of a reject run is carried from chunk to chunk);
 //   * candidates go to one list for the whole launch as (job << 32) | step << 26 | iy << 13 | ix; the host orders them
-//     (= OpenCV's serial order), groups them and, for FIND_BIGGEST, replays the serial search on them (api.cpp).
+//     (= OpenCV's serial order), groups them and, for FIND_BIGGEST, replays the serial search on them (detect.cpp).
 // Same arithmetic as the large-image kernels: i32 rectangle sums, f32 products, f64 variance / thresholds / stage sums in
 // OpenCV's order (one lane walks a window's stumps in order; a stage whose partial sums are exact in any order may be split over
 // lanes and summed in LDS), contraction off.  Stump cascades with upright features only.

@@ -197,13 +197,11 @@ struct Switches {
     bool trk_fold = true;            // NVCA_TRK_FOLD=0: NuboTracker's components through the per-pixel kernels (k_ccl_flatten / _reduce / _collect) instead of the per-tile reduction + fold of tile roots
     int  trk_order = -1;             // NVCA_TRK_ORDER: visiting order of k_ccl_reduce (-1: decided per frame on the device)
     int  host_threads = -1;          // NVCA_HOST_THREADS=n: helper threads for per-job host work (-1: min(8, cores / 2) - 1; 0: none)
-    bool two_lanes = true;           // NVCA_TWO_LANES=0: both submitted face batches on the context's stream (one after the other)
     bool fb_dense = true;            // NVCA_FB_DENSE=0: a FIND_BIGGEST search on the small-image path re-scans its narrowed grids in a second launch instead of replaying them on the host from the first launch's dense candidates + stage-0 reject bits
     bool roi = true;                 // NVCA_ROI=0: small images take the large-image path too (plan + four launches per job)
     bool stage_order = false;        // NVCA_STAGE_ORDER=1 (0, the default: the cascade's own order on every tile -- the cheapest one for a cascade whose stages each reject about half, as trained ones do; a round then may take two stages at once): the tile kernels walk the early stages 1 .. 5 in the cascade's order on every tile (1: in the order the previous tile of the band found cheapest -- cost per window killed; the set of survivors is the same.  A cascade whose stages each reject about half, as trained ones do, keeps its own order either way)
     int  pair_max = 32;              // NVCA_PAIR_MAX=n (<= 32): windows up to which a round of the tile kernels runs lane = (window, stump) instead of a window per lane
     int  spec_pairs = 1536;          // NVCA_SPEC_PAIRS=n: with at most 32 windows left a round takes as many stages as stay within n (window, stump) pairs (768 = one step of the workgroup)
-    int  pre_cus = 0;                // NVCA_PRE_CUS=n: a submitted face batch's pre-processing runs on a stream confined to n CUs (hipExtStreamCreateWithCUMask), beside the other batch's band kernel (0: behind it, on the lane's own stream)
     bool quiet = false;              // NVCA_QUIET: no one-time notes on stderr (a plan that falls back to the row-strip kernel)
     const char *stamps_out = nullptr;   // NVCA_STAMPS_OUT (diagnostic build only)
 };
@@ -235,7 +233,7 @@ struct PinnedBuf {
 };
 
 // Page-locked memory of the context's own that caller host memory crosses through when it is not page-locked by the caller
-// (nvca_host_register): a ring of fixed slots, each with the event of the last copy that read or wrote it (api.cpp, caller_h2d ...).
+// (nvca_host_register): a ring of fixed slots, each with the event of the last copy that read or wrote it (host_copy.cpp, caller_h2d ...).
 struct BounceRing {
     static constexpr size_t kSlot = 8u << 20;      // a 1080p BGR frame (6.2 MB) is one slot: one CPU copy (shared by the helper threads) + one DMA
     static constexpr int kSlots = 12;
@@ -271,10 +269,10 @@ int work_pool_threads(const WorkPool *p);          // helper threads (0 for null
 
 struct DetectPlan;   // plan.cpp
 struct ScaleTable;   // plan.cpp: one cascade at one scale factor (geometry-independent stump records), cached in the context
-struct FaceTicket;   // api.cpp
+struct FaceTicket;   // face_stream.cpp
 void free_face_ticket(FaceTicket *t);
-struct GeomPlan;     // api.cpp
-struct Workspace;    // api.cpp
+struct GeomPlan;     // host_state.h
+struct Workspace;    // host_state.h
 
 struct KernelTimer {
     bool on = false;
@@ -303,12 +301,9 @@ static constexpr int kTrackerLane = 9;    // NuboTracker's kernels: its state an
 struct nvca_ctx {
     int device = 0;
     hipStream_t stream = nullptr;             // lane 0
-    hipStream_t lane_streams[nvca::kLanes] = {nullptr};   // [0] == stream; the others carry the batched part detectors' jobs (api.cpp, Lane)
+    hipStream_t lane_streams[nvca::kLanes] = {nullptr};   // [0] == stream; the others carry the batched part detectors' jobs (host_state.h, Lane)
     int cur_lane = 0;
     hipStream_t cs() const { return lane_streams[cur_lane]; }       // the stream of the lane that is being queued on
-    hipStream_t pre_streams[2] = {nullptr, nullptr};   // CU-masked streams for the pre-processing of the two face batches in flight ("pre_cus"), created on first use
-    int pre_streams_cus = 0;                  // the CU count they were created for
-    hipEvent_t pre_done[2] = {nullptr, nullptr};
     nvca::HostRangeTable host_ranges;         // what the caller page-locked through nvca_host_register (host_ranges.h: the only caller memory a copy is handed as it stands)
     nvca::BounceRing bounce;                  // everything else crosses through here
     hipStream_t copy_stream = nullptr;        // H2D of the next chunk of host frames while the current one computes
@@ -518,7 +513,7 @@ struct CascadeArgs {
 // lds_grant: the calling context's record of the dynamic LDS already granted to k_tile ([0]) / k_band ([1]); returns a
 // hipError_t (as int) when the grant is refused, 0 otherwise
 int launch_cascade_sc(hipStream_t st, const CascadeArgs &a, int batch, int which, int *lds_grant);
-// detectMultiScale calls in halves (api.cpp): many calls share one wait per round
+// detectMultiScale calls in halves (detect.cpp): many calls share one wait per round
 // ---- view-* outlines (nvca_draw_shapes): one coverage rule for the host rasteriser and the kernel
 #if defined(__HIPCC__)
 #define NVCA_HD __host__ __device__
@@ -592,32 +587,18 @@ void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, co
 void launch_draw_shapes(hipStream_t st, uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *d_shapes, int n,
                         int bx0, int by0, int bx1, int by1);
 
-// ---- caller host memory <-> device (api.cpp): direct only inside a range the caller registered, otherwise through the bounce ring
+// ---- caller host memory <-> device (host_copy.cpp): direct only inside a range the caller registered, otherwise through the bounce ring
 int caller_h2d(nvca_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t st);
 int caller_h2d_rows(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows, hipStream_t st);
 int caller_d2h_rows(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows, hipStream_t st);   // returns with dst filled (the stream is drained)
 
-// ---- working images of a batched part call (api.cpp), all on the current lane
-// N images of one launch set: image k = [equalizeHist](resize(source k)) at dst + k * slot, pitch dw.  BGR sources: gray of the frame
-// computed on the fly (cvtColor then resize); gray sources go through LUT lut_idx[k] of `luts` first when lut_idx is given
-struct PartImageBatch {
-    bool bgr = true, post_eq = true;
-    int sw = 0, sh = 0, sstride = 0, dw = 0, dh = 0;
-    std::vector<const void *> src; std::vector<int> lut_idx;
-    uint8_t *dst = nullptr; size_t slot = 0;
-};
+// ---- the part detectors' upload ring for small tables (parts.cpp); nvca_draw_shapes queues its shapes through it too
 int part_table(nvca_ctx *ctx, const void *host, size_t bytes, void **dev);   // a small table for the next launch on the current lane (upload ring)
-int part_arena(nvca_ctx *ctx, size_t bytes, uint8_t **base);                 // grows the arena (before anything of the call is queued)
-int part_luts(nvca_ctx *ctx, int n_keep, int n_scratch, uint8_t **keep);     // LUT storage: n_keep that live through the call + scratch
-int part_gray_eq(nvca_ctx *ctx, const void *const *bgr, int n, int w, int h, int stride, uint8_t *gray, size_t slot, uint8_t *luts);   // gray images + their equalisation LUTs
-int part_image_batch(nvca_ctx *ctx, const PartImageBatch &b, const uint8_t *luts);
-int part_flip_batch(nvca_ctx *ctx, const uint8_t *src, uint8_t *dst, int w, int h, int n, size_t slot);
-int part_images_done(nvca_ctx *ctx, const int *lanes, int n);                // the lanes in `lanes` wait for what the current lane has queued so far
 struct DetectJob;
 int make_detect_job(nvca_ctx *ctx, DetectJob &j, const nvca_cascade *casc, const void *gray, int w, int h, int stride, int mem,
                     double sf, int min_neighbors, int flags, int minw, int minh, int maxw, int maxh, bool raw_only);
 int run_detect_jobs(nvca_ctx *ctx, DetectJob *const *jobs, int n, const int *lanes);      // lanes: per job, or null (current lane)
-// ... in two halves: the first round queued and left in flight, then the rest (api.cpp)
+// ... in two halves: the first round queued and left in flight, then the rest (detect.cpp)
 struct JobRound;
 JobRound *job_round_new();
 void job_round_free(JobRound *r);
@@ -628,9 +609,6 @@ void detect_job_free(DetectJob *j);
 const std::vector<nvca_rect> &detect_job_out(const DetectJob *j, int k);
 constexpr int kJobImages = 32;                                    // images of one geometry that a plain / SCALE_IMAGE job can carry
 int detect_job_add_image(DetectJob *j, const void *image);       // one more image for the job's launch set; returns its index k (detect_job_out), -1: full / not possible
-// detectMultiScale(CV_HAAR_SCALE_IMAGE) on two images of one geometry with shared launches (api.cpp; used by parts.cpp)
-int detect_scale_image_pair(nvca_ctx *ctx, const nvca_cascade *casc, const void *img_a, const void *img_b, int w, int h, int stride,
-                            int mem, double sf, int min_neighbors, int minw, int minh, std::vector<nvca_rect> *outs /* [2] */);
 // general cascades: which = 0: variance + stage 0 for every window (reject bits + normaliser), 1: the remaining stages on the
 // visited stage-0 survivors, window per lane
 void launch_generic(hipStream_t st, const CascadeArgs &a, int batch, int which);
@@ -650,7 +628,7 @@ struct RoiStep {                  // one ladder step (scale-cascade scan) or one
     double inv_area, ystep;
     // adaptive == 2 ("dense", FIND_BIGGEST searches): every window that passes stage 0 goes on, visited by the serial walk or not, and the
     // stage-0 reject bits of the step's grid are written out -- row r's chunk c at rej[rej_off + r * rej_wpr + c] (64 windows a word) -- so
-    // that the host can replay the walk from ANY start column: a narrowed re-scan needs no second launch (api.cpp, fb_replay)
+    // that the host can replay the walk from ANY start column: a narrowed re-scan needs no second launch (detect.cpp, fb_replay)
     int rej_off, rej_wpr;
 };
 struct RoiJobDev {

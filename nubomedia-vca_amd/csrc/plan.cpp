@@ -355,7 +355,7 @@ int DetectPlan::build_tables(nvca_ctx *ctx, const Cascade &c, bool allow_tiles, 
                 for (int q = 0; q < (g.flags & 255); q++)
                     for (int e = 0; e < 4; e++) { mnx = std::min<int>(mnx, g.dx[q][e]); mxx = std::max<int>(mxx, g.dx[q][e]); mny = std::min<int>(mny, g.dy[q][e]); mxy = std::max<int>(mxy, g.dy[q][e]); }
             if (!sp.xs.empty() && !sp.ys.empty() &&
-                (sp.xs.front() + mnx < 0 || sp.xs.back() + mxx >= pitch || sp.ys.front() + mny < 0 || sp.ys.back() + mxy >= sp.plane_rows + 2)) {      // the planes are allocated with a few spare rows (api.cpp)
+                (sp.xs.front() + mnx < 0 || sp.xs.back() + mxx >= pitch || sp.ys.front() + mny < 0 || sp.ys.back() + mxy >= sp.plane_rows + 2)) {      // the planes are allocated with a few spare rows (plans.cpp, ensure_ws)
                 err = "a feature of the cascade leaves the image at this scale"; return NVCA_ERR_UNSUPPORTED;
             }
         }
@@ -500,7 +500,7 @@ int DetectPlan::build_tables(nvca_ctx *ctx, const Cascade &c, bool allow_tiles, 
         std::stable_sort(band_order.begin(), band_order.end(), [&](int x, int y) { return bands[x].ntiles > bands[y].ntiles; });
         band_blocks_per_frame = (int)bands.size();
     }
-    // per-scale segments of the global survivor lists (sized per frame; api.cpp scales them by the batch)
+    // per-scale segments of the global survivor lists (sized per frame; plans.cpp scales them by the batch)
     device_group_ok = true;
     for (size_t q = 0; q < specs.size(); q++)
         if (specs[q].out_factor != 0 || specs[q].out_w != scales[q].winw || specs[q].out_h != scales[q].winh) device_group_ok = false;

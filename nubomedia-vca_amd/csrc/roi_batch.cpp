@@ -1,0 +1,282 @@
+// roi_batch.cpp -- the small-image path of detectMultiScale: every small job of a round in one k_roi launch (kernels_roi.hip),
+// and its candidates handed back to the jobs.
+#include "host_state.h"
+#include <cstring>
+#include <algorithm>
+
+using namespace nvca;
+
+namespace nvca {
+
+// ---- small images: one launch for every such job of a round (kernels_roi.hip) -----------------------------------------------
+// A job qualifies when its image's integral pair fits the workgroup's LDS, the cascade is a stump cascade with upright
+// features, and the ladder fits the candidate key.  No plan is built: the launch gets, per job, a handful of step records
+// (the cached stump table of the step's factor, the variance rectangle, the grid limits) -- so a face region of a size never
+// seen before costs no table work, and all regions of all streams of a round share ONE launch.
+static constexpr int kRoiMaxWords = 14848;          // (cols + 1) * (rows + 2) words per plane: the part detectors' 160 x 90 face-pass image still fits (two planes + queues + a level image = 157 KB of the 160 KB of LDS)
+bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round)
+{
+    const Cascade &c = j.casc->c;
+    if (!ctx->sw.roi) return false;
+    if (!c.stump_based || c.has_tilted || (j.nimg != 1 && j.mem != NVCA_MEM_DEVICE)) return false;
+    if ((long long)(j.cols + 1) * (j.rows + 2) > kRoiMaxWords || j.cols < 1 || j.rows < 1) return false;
+    if (j.mem != NVCA_MEM_DEVICE && njobs_in_round != 1) return false;       // a host image is staged in the lane's one gray buffer
+    return true;
+}
+static const StageRec *roi_stage_recs(nvca_ctx *ctx, const Cascade &c)
+{
+    auto it = ctx->roi_stage_recs.find(c.uid);
+    if (it != ctx->roi_stage_recs.end()) return it->second->as<StageRec>();
+    std::vector<StageRec> st; build_stage_recs(c, st);
+    std::unique_ptr<DevBuf> d(new DevBuf());
+    if (d->ensure(st.size() * sizeof(StageRec) + 8) || hipMemcpy(d->p, st.data(), st.size() * sizeof(StageRec), hipMemcpyHostToDevice) != hipSuccess) {
+        d->release(); ctx->set_error("allocation failed (stage records)"); return nullptr;
+    }
+    const StageRec *p = d->as<StageRec>();
+    ctx->roi_stage_recs[c.uid] = d.release();
+    return p;
+}
+static ScaleTable *roi_table(nvca_ctx *ctx, RoiBatch &rb, const Cascade &c, double factor)
+{
+    ScaleTable *t = get_scale_table(ctx, c, factor);
+    if (t) { t->refs++; rb.held.push_back(t); }
+    return t;
+}
+static void roi_step_common(RoiStep &st, const ScaleTable &t)
+{
+    memset(&st, 0, sizeof(st));
+    st.trecs = t.dev.as<TStumpRec>(); st.ex = t.ex; st.ey = t.ey; st.ew = t.ew; st.eh = t.eh; st.inv_area = t.inv_area; st.step = 1;
+}
+// scale-cascade grid of one ladder step, limits as indices: false = nothing to scan (fb_make_spec's rules: grid points whose
+// window would leave the image -- cvRunHaarClassifierCascadeSum returns -1 there -- are dropped from the end, a negative origin voids the step)
+bool roi_grid(int cols, int rows, double ystep, int winw, int winh, int startX, int endX, int startY, int endY, RoiStep &st)
+{
+    if (!(endX > startX && endY > startY)) return false;
+    while (endX > startX && cv_round((endX - 1) * ystep) + winw >= cols + 1) endX--;
+    while (endY > startY && cv_round((endY - 1) * ystep) + winh >= rows + 1) endY--;
+    if (!(endX > startX && endY > startY)) return false;
+    if (cv_round(startX * ystep) < 0 || cv_round(startY * ystep) < 0 || endX > 8191 || endY > 8191) return false;
+    st.startX = startX; st.endX = endX; st.startY = startY; st.endY = endY; st.ystep = ystep; st.adaptive = 1;
+    return true;
+}
+// returns NVCA_OK with j.fused set when the job's next set went into the batch, NVCA_OK with j.fused clear when it has to take
+// the large-image path after all (too many steps), or an error
+int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
+{
+    const Cascade &c = j.casc->c;
+    const int cols = j.cols, rows = j.rows;
+    j.fused = false;
+    const StageRec *d_stages = roi_stage_recs(ctx, c);
+    if (!d_stages) return NVCA_ERR_NOMEM;
+    std::vector<RoiStep> steps; std::vector<DetectJob::RoiStepInfo> info; std::vector<unsigned char> tabs;
+    const size_t tab0 = rb.tabs.size();
+    int lev_bytes = 0;
+    const bool dense = j.kind == 2 && j.phase == 0 && ctx->sw.fb_dense && j.nimg == 1;
+    std::vector<DetectJob::RejInfo> rej; size_t rej_local = 0;
+    if (j.phase == 0) for (int k = 0; k < kJobImages; k++) j.out[k].clear();
+    if (j.kind == 1) {
+        // the pyramid levels of si_plan, each with its cv::resize tables
+        ScaleTable *t1 = nullptr;
+        for (double factor = 1;; factor *= j.sf) {
+            const int winw = cv_round(c.ow * factor), winh = cv_round(c.oh * factor);
+            const int szw = cv_round(cols / factor), szh = cv_round(rows / factor);
+            if (szw - c.ow + 1 <= 0 || szh - c.oh + 1 <= 0) break;
+            if (winw > j.maxw || winh > j.maxh) break;
+            if (winw < j.minw || winh < j.minh) continue;
+            if (szw + 1 <= 1 + c.ow) continue;
+            if (!t1 && !(t1 = roi_table(ctx, rb, c, 1.))) return NVCA_ERR_NOMEM;
+            RoiStep st; roi_step_common(st, *t1);
+            st.szw = szw; st.szh = szh; st.step = factor > 2 ? 1 : 2; st.startX = 0; st.endX = szw - c.ow; st.startY = 0; st.endY = szh - c.oh;
+            if (st.endX <= 0 || st.endY <= 0) continue;
+            ResizeTab tab; build_resize_tab(cols, rows, szw, szh, tab);
+            st.mode = tab.mode; st.xmax = tab.xmax;
+            auto put = [&](const void *p, size_t n) { const size_t at = (tab0 + tabs.size() + 15) & ~(size_t)15; tabs.resize(at - tab0 + n); if (n) memcpy(tabs.data() + at - tab0, p, n); return (int)at; };
+            st.xofs_off = put(tab.xofs.data(), tab.xofs.size() * 4); st.yofs_off = put(tab.yofs.data(), tab.yofs.size() * 4);
+            st.ialpha_off = put(tab.ialpha.data(), tab.ialpha.size() * 2); st.ibeta_off = put(tab.ibeta.data(), tab.ibeta.size() * 2);
+            steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{0., factor, winw, winh, -1});
+            lev_bytes = std::max(lev_bytes, szw * szh);
+        }
+        j.phase = 1;
+    } else if (j.kind == 0) {
+        std::vector<double> factors;
+        scale_grid(c.ow, c.oh, cols, rows, j.sf, j.minw, j.minh, j.maxw, j.maxh, false, factors);
+        for (double factor : factors) {
+            const double ystep = std::max(2., factor);
+            ScaleTable *t = roi_table(ctx, rb, c, factor);
+            if (!t) return NVCA_ERR_NOMEM;
+            RoiStep st; roi_step_common(st, *t);
+            if (!roi_grid(cols, rows, ystep, t->winw, t->winh, 0, cv_round((cols - t->winw) / ystep), 0, cv_round((rows - t->winh) / ystep), st)) continue;
+            steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{ystep, 0., t->winw, t->winh, -1});
+        }
+        j.gthr = (!j.raw_only && j.min_neighbors != 0) ? std::max(j.min_neighbors, 1) : 0;
+        j.phase = 1;
+    } else {
+        if (j.phase == 0) {
+            // the ladder of factors, largest first, exactly as the serial loop walks it (fb_enqueue_first)
+            j.ladder.clear();
+            int n_factors = 0; double factor;
+            for (n_factors = 0, factor = 1; factor * c.ow < cols - 10 && factor * c.oh < rows - 10; n_factors++, factor *= j.sf)
+                ;
+            const double inv = 1. / j.sf; factor *= inv;
+            for (; n_factors-- > 0; factor *= inv) j.ladder.push_back(FbStep{factor, std::max(2., factor), cv_round(c.ow * factor), cv_round(c.oh * factor)});
+            j.hits.assign(j.ladder.size(), {}); j.have.assign(j.ladder.size(), 1);
+            j.all.clear(); j.scanROI = nvca_rect{0, 0, 0, 0}; j.narrowed_done = false; j.fb_i = 0; j.cur_minw = j.minw; j.cur_minh = j.minh;
+            j.ladder_of.clear();
+            for (size_t i = 0; i < j.ladder.size(); i++) {
+                const FbStep &fs = j.ladder[i];
+                if (fs.winw < j.minw || fs.winh < j.minh) break;
+                if (fs.winw > j.maxw || fs.winh > j.maxh) continue;
+                ScaleTable *t = roi_table(ctx, rb, c, fs.factor);
+                if (!t) return NVCA_ERR_NOMEM;
+                RoiStep st; roi_step_common(st, *t);
+                if (!roi_grid(cols, rows, fs.ystep, fs.winw, fs.winh, 0, cv_round((cols - fs.winw) / fs.ystep), 0, cv_round((rows - fs.winh) / fs.ystep), st)) continue;
+                if (dense) {                     // every stage-0 passer of the full grid + the grid's reject bits: a narrowed re-scan is replayed on the host
+                    st.adaptive = 2; st.rej_wpr = (st.endX + 63) / 64; st.rej_off = (int)(rb.rej_words + rej_local);
+                    rej.push_back(DetectJob::RejInfo{st.rej_off, st.rej_wpr, st.endX, st.endY});
+                    rej_local += (size_t)st.rej_wpr * st.endY;
+                }
+                steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{fs.ystep, 0., fs.winw, fs.winh, (int)i}); j.ladder_of.push_back((int)i);
+            }
+            j.phase = 1;
+        } else {
+            // the narrowed set fb_replay asked for: steps fb_i .. on their narrowed grids (j.ladder_of / j.have were set by the replay)
+            for (int li : j.ladder_of) {
+                const FbStep &fs = j.ladder[li];
+                ScaleTable *t = roi_table(ctx, rb, c, fs.factor);
+                if (!t) return NVCA_ERR_NOMEM;
+                RoiStep st; roi_step_common(st, *t);
+                if (!roi_grid(cols, rows, fs.ystep, fs.winw, fs.winh, cv_round(j.scanROI.x / fs.ystep), cv_round((j.scanROI.x + j.scanROI.w - fs.winw) / fs.ystep),
+                              cv_round(j.scanROI.y / fs.ystep), cv_round((j.scanROI.y + j.scanROI.h - fs.winh) / fs.ystep), st)) continue;
+                steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{fs.ystep, 0., fs.winw, fs.winh, li});
+            }
+        }
+    }
+    bool fits = steps.size() <= 63;                                  // the key holds 6 bits of step
+    {
+        // A step's rows are independent of one another (the adaptive x step works row by row, a pyramid level's grid is fixed):
+        // a step with more windows than the queues hold goes out as several records, a band of whole rows each -- one workgroup
+        // per band instead of one per step walking its bands one after the other (the largest pyramid level of a 160 x 90 face
+        // pass is 10 k windows: alone it set the length of the whole launch).  Every band builds the integral pair for itself.
+        std::vector<RoiStep> bands;
+        for (size_t li = 0; li < steps.size(); li++) {
+            RoiStep st = steps[li];
+            const int nx = (st.endX - st.startX + st.step - 1) / st.step, ny = (st.endY - st.startY + st.step - 1) / st.step;
+            if (nx > kRoiMaxWin) fits = false;                       // (a grid row longer than the queues: not with images this small)
+            st.key_step = (int)li;
+            st.key_x0 = st.startX; st.key_dx = st.step; st.key_dy = st.step;
+            const int rows_per = nx > 0 && nx < kRoiMaxWin ? kRoiMaxWin / nx : 1;
+            for (int gy0 = 0; gy0 < std::max(ny, 1); gy0 += rows_per) {
+                RoiStep b = st;
+                b.startY = st.startY + gy0 * st.step;
+                b.endY = std::min(st.endY, st.startY + (gy0 + rows_per) * st.step);
+                b.key_y0 = b.startY;
+                bands.push_back(b);
+            }
+        }
+        steps.swap(bands);
+    }
+    if (!fits && j.roi_prev_phase == 2) { ctx->set_error("internal: a narrowed search outgrew the small-image path"); return NVCA_ERR_INTERNAL; }   // (its full grids fitted)
+    if (!fits) { j.phase = j.roi_prev_phase; return NVCA_OK; }       // this one takes the large-image path
+    j.fused = true; j.rinfo.swap(info); j.dp = nullptr;
+    j.dense = dense && !rej.empty(); j.rej_info.swap(rej);
+    if (j.dense) rb.rej_words += rej_local;
+    for (int k = 0; k < kJobImages; k++) j.rkeys[k].clear();
+    if (steps.empty()) return NVCA_OK;                               // nothing to scan: the job completes with what it has
+    rb.tabs.insert(rb.tabs.end(), tabs.begin(), tabs.end());
+    for (int k = 0; k < j.nimg; k++) {            // every image of the job: its own records (the steps name their image), the same tables
+        RoiJobDev d; memset(&d, 0, sizeof(d));
+        d.w = cols; d.h = rows; d.stride = j.stride; d.img = (const uint8_t *)j.img[k];
+        if (j.mem != NVCA_MEM_DEVICE) {
+            PreGeom g; make_geom(g, cols, rows, j.stride, 1, cols, rows);
+            int rc;
+            if ((rc = ensure_ws(ctx, g, 1))) return rc;
+            if ((rc = stage_2d(ctx, ctx->ws->ln().gray.p, g.gpitch, j.img[0], j.stride, cols, rows, j.mem))) return rc;
+            d.img = ctx->ws->ln().gray.as<uint8_t>(); d.stride = g.gpitch;
+        }
+        d.first_step = (int)rb.steps.size(); d.nsteps = (int)steps.size(); d.scale_image = j.kind == 1;
+        d.stages = d_stages; d.nstages = (int)c.stages.size(); d.pair_policy = ctx->policy == NVCA_SUM_F32PAIR; d.slot = (int)rb.jobs.size();
+        for (RoiStep &st : steps) st.job = d.slot;
+        rb.steps.insert(rb.steps.end(), steps.begin(), steps.end());
+        rb.jobs.push_back(d); rb.owners.push_back(&j); rb.owner_img.push_back(k);
+    }
+    rb.plane_words = std::max(rb.plane_words, (cols + 1) * (rows + 2));
+    rb.lev_bytes = std::max(rb.lev_bytes, lev_bytes);
+    return NVCA_OK;
+}
+// upload the round's tables and launch k_roi on the current lane
+int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap)
+{
+    const int nj = (int)rb.jobs.size();
+    const size_t jb = (size_t)nj * sizeof(RoiJobDev), sb = rb.steps.size() * sizeof(RoiStep);
+    const size_t o_steps = (jb + 255) & ~(size_t)255, o_tabs = (o_steps + sb + 255) & ~(size_t)255, total = o_tabs + rb.tabs.size() + 64;
+    // the list starts at a quarter of a million candidates for the whole launch however many jobs share it; a launch that
+    // overflows it is queued again with the exact size (run_detect_jobs raises hit_cap for the rest of the call)
+    const long long want = (long long)ctx->hit_cap * nj;
+    rb.cap = (unsigned)std::min<long long>(want, full_cap ? (1ll << 26) : (1ll << 18));
+    const size_t first = std::min<size_t>(rb.cap, std::max<size_t>(8192, ctx->roi_first_hint));
+    rb.first = first;
+    if (ctx->rbuf().tables.ensure(total) || ctx->rbuf().h_tables.ensure(total) || ctx->rbuf().hits.ensure(((size_t)rb.cap + 1) * 8) || ctx->rbuf().h_hits.ensure(((size_t)rb.cap + 1) * 8) ||
+        ctx->rbuf().rej.ensure((rb.rej_words + 1) * 8) || ctx->rbuf().h_rej.ensure((rb.rej_words + 1) * 8)) {
+        ctx->set_error("allocation failed (small-image detector)"); return NVCA_ERR_NOMEM;
+    }
+    unsigned char *h = ctx->rbuf().h_tables.as<unsigned char>();
+    memcpy(h, rb.jobs.data(), jb); memcpy(h + o_steps, rb.steps.data(), sb);
+    if (!rb.tabs.empty()) memcpy(h + o_tabs, rb.tabs.data(), rb.tabs.size());
+    NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().tables.p, h, total - 64, hipMemcpyHostToDevice, ctx->cs()));
+    NVCA_HIP_CHECK(ctx, hipMemsetAsync(ctx->rbuf().hits.p, 0, sizeof(unsigned long long), ctx->cs()));
+    const int lds = rb.plane_words * 8 + kRoiMaxWin * (8 + 2 + 2) + 16 + ((rb.lev_bytes + 15) & ~15) + 64;      // k_roi's carve-up
+    if (const int e = roi_grant_lds(lds)) { ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e)); return NVCA_ERR_HIP; }
+    const unsigned char *d = ctx->rbuf().tables.as<unsigned char>();
+    { TimedLaunch t(ctx, NVCA_K_ROI);
+      launch_roi(ctx->cs(), (const RoiJobDev *)d, (int)rb.steps.size(), (const RoiStep *)(d + o_steps), d + o_tabs, ctx->rbuf().hits.as<unsigned long long>(), rb.cap, rb.plane_words, lds,
+                 ctx->rbuf().rej.as<unsigned long long>()); }
+    if (rb.rej_words) NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().h_rej.p, ctx->rbuf().rej.p, rb.rej_words * 8, hipMemcpyDeviceToHost, ctx->cs()));
+    NVCA_LAUNCH_CHECK(ctx);
+    NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().h_hits.p, ctx->rbuf().hits.p, (first + 1) * 8, hipMemcpyDeviceToHost, ctx->cs()));
+    return NVCA_OK;
+}
+// after the lane has drained: hand every job its candidates; NVCA_ERR_OVERFLOW (with hit_cap_wanted set) when the list was too short
+int roi_collect(nvca_ctx *ctx, RoiBatch &rb)
+{
+    unsigned long long *hh = ctx->rbuf().h_hits.as<unsigned long long>();
+    const unsigned long long total = hh[0];
+    const int nj = (int)rb.jobs.size();
+    if (total > rb.cap) {
+        const unsigned long long per = (total + (unsigned long long)nj - 1) / (unsigned long long)nj + 64;
+        if (per <= (unsigned long long)kMaxHitCap && (long long)per > ctx->hit_cap_wanted) ctx->hit_cap_wanted = (int)per;
+        ctx->set_error("raw candidate capacity exceeded (nvca_ctx_set_hit_capacity)");
+        return NVCA_ERR_OVERFLOW;
+    }
+    // the list's head came back with the launch; how much of it to fetch that way next time follows the recent rounds (a second
+    // copy is a second wait)
+    ctx->roi_first_hint = std::max<size_t>((size_t)(total + total / 4), ctx->roi_first_hint - ctx->roi_first_hint / 16);
+    const size_t first = rb.first;
+    if (total > first) {
+        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(hh + 1 + first, ctx->rbuf().hits.as<unsigned long long>() + 1 + first, (total - first) * 8, hipMemcpyDeviceToHost, ctx->cs()));
+        NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
+    }
+    // the dense jobs' reject bits: per ladder step of the job (detect.cpp, fb_replay)
+    for (DetectJob *o : rb.owners) {
+        if (!o->dense) continue;
+        const unsigned long long *hr = ctx->rbuf().h_rej.as<unsigned long long>();
+        o->rej_bits.assign(o->ladder.size(), nullptr); o->rej_wpr.assign(o->ladder.size(), 0); o->rej_rows.assign(o->ladder.size(), 0); o->dense_hits.assign(o->ladder.size(), {});
+        for (size_t k = 0; k < o->rej_info.size() && k < o->rinfo.size(); k++) {
+            const DetectJob::RejInfo &ri = o->rej_info[k];
+            const int li = o->rinfo[k].ladder;
+            if (li < 0 || (size_t)li >= o->ladder.size() || (size_t)ri.off + (size_t)ri.wpr * ri.ny > rb.rej_words) { ctx->set_error("internal: reject bitmap of an unknown ladder step"); return NVCA_ERR_INTERNAL; }
+            o->rej_bits[li] = hr + ri.off; o->rej_wpr[li] = ri.wpr; o->rej_rows[li] = ri.ny;
+        }
+    }
+    // (the list is in the order the workgroups appended: every job sorts its own keys into the serial order when it advances)
+    for (unsigned long long i = 0; i < total; i++) {
+        const unsigned long long slot = hh[1 + i] >> 32;
+        const unsigned key = (unsigned)hh[1 + i];
+        if (slot >= (unsigned long long)nj || (key >> 26) >= rb.owners[slot]->rinfo.size()) {
+            ctx->set_error("internal: candidate of an unknown job / step (device result rejected)"); return NVCA_ERR_INTERNAL;
+        }
+        rb.owners[slot]->rkeys[rb.owner_img[slot]].push_back(key);
+    }
+    return NVCA_OK;
+}
+
+} // namespace nvca

@@ -23,6 +23,13 @@ constexpr int kCompCap = 1 << 18;
 
 extern "C" {
 
+void nvca_tracker_params_default(nvca_tracker_params *p)
+try {
+    if (!p) return;
+    p->threshold = 20; p->min_area = 50; p->max_area = 30000; p->distance = 35; p->mhi_duration = 0.2; p->seg_thresh = 32;
+}
+NVCA_API_CATCH_VOID
+
 int nvca_tracker_create(nvca_ctx *ctx, const nvca_tracker_params *params, nvca_tracker **out)
 try {
     if (!ctx || !out) return NVCA_ERR_ARG;

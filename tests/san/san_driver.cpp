@@ -16,7 +16,7 @@
 #include <sstream>
 #include <set>
 
-// ---- host doubles of what api.cpp / the HIP runtime provide to these sources ------------------------------------------
+// ---- host doubles of what runtime.cpp / plans.cpp / api.cpp / the HIP runtime provide to these sources -------------------
 extern "C" hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) { memcpy(dst, src, n); return hipSuccess; }
 extern "C" hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
 extern "C" hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }

@@ -1,5 +1,5 @@
 """The parity tests of the primitives and the detectMultiScale variants once more, in a child process whose device buffers are
-mapped between unmapped guard ranges and end where their mappings end (NVCA_ALLOC_GUARD=2: csrc/api.cpp, "electric fence"; released
+mapped between unmapped guard ranges and end where their mappings end (NVCA_ALLOC_GUARD=2: csrc/runtime.cpp, "electric fence"; released
 buffers are unmapped too): a kernel that reads or writes past one of the library's buffers, or touches a released one, faults at
 that access and takes the child down -- every time, not now and then as on an ordinary heap.  (In a child: a fault ends the process.)"""
 import os
