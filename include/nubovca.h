@@ -86,11 +86,12 @@ const char *nvca_version(void);
 int  nvca_ctx_set_hit_capacity(nvca_ctx *ctx, int cap);
 int  nvca_ctx_set_sum_policy(nvca_ctx *ctx, int policy);
 /* Measurement / bisecting switches, per context.  The process-wide defaults come from the environment
- * (NVCA_BAND, NVCA_TILES, ... read once, when the first context is created); this sets one for this context.  Names: "band"
- * (-1 / 0 / 1), "band_map", "tiles", "deep_stage", "deep_lds", "pyr_off", "stage_order", "spec_pairs", "pair_max", "host_group",
- * "group_zerocopy", "sparse_ingest", "ingest_chunk", "skip_cascade", "host_profile", "part_stats", "trk_order", "trk_fold",
- * "plan_debug", "quiet", "roi", "fb_dense", "host_threads"; any other name is refused with NVCA_ERR_ARG.  None of them changes a
- * result.  Switches that shape plans drop the context's cached plans (not while a submitted batch is in flight).
+ * (NVCA_BAND, NVCA_TILES, ... read once, when the first context is created); this sets one for this context.  Names, in the
+ * order of the table in csrc/options.cpp: "group_zerocopy", "skip_cascade", "host_group", "band_map", "band" (-1 / 0 / 1),
+ * "host_profile", "sparse_ingest", "pyr_off", "part_stats", "ingest_chunk", "deep_stage", "tiles", "plan_debug", "deep_lds",
+ * "trk_fold", "trk_order", "host_threads", "fb_dense", "roi", "stage_order", "pair_max", "spec_pairs", "quiet"; any other name is refused with NVCA_ERR_ARG.
+ * None of them changes a result.  Switches that shape plans drop the context's cached plans (not while a submitted batch is
+ * in flight).
  * nvca_ctx_get_option reads the value a switch holds for this context (so that a caller can put it back). */
 int  nvca_ctx_set_option(nvca_ctx *ctx, const char *name, int value);
 int  nvca_ctx_get_option(nvca_ctx *ctx, const char *name, int *value);

@@ -100,33 +100,9 @@ int nvca_ctx_set_option(nvca_ctx *ctx, const char *name, int value)
 try {
     NVCA_LOCK_OR_FAIL(ctx);
     if (!name) return NVCA_ERR_ARG;
-    const std::string n(name);
-    Switches &w = ctx->sw;
     bool replan = false;
-    if (n == "band") w.band = value;
-    else if (n == "band_map") w.band_map = value;
-    else if (n == "group_zerocopy") w.group_zero_copy = value != 0;
-    else if (n == "host_group") w.host_group = value != 0;
-    else if (n == "skip_cascade") w.skip_cascade = value != 0;
-    else if (n == "host_profile") w.host_profile = value != 0;
-    else if (n == "sparse_ingest") w.sparse_ingest = value != 0;
-    else if (n == "ingest_chunk") w.ingest_chunk = value;
-    else if (n == "part_stats") w.part_stats = value;
-    else if (n == "trk_order") w.trk_order = value;
-    else if (n == "trk_fold") w.trk_fold = value != 0;
-    else if (n == "quiet") w.quiet = value != 0;
-    else if (n == "roi") w.roi = value != 0;
-    else if (n == "fb_dense") w.fb_dense = value != 0;
-    else if (n == "host_threads") { w.host_threads = value; work_pool_destroy(ctx->pool); ctx->pool = nullptr; ctx->pool_tried = false; }
-    else if (n == "plan_debug") w.plan_debug = value != 0;
-    else if (n == "stage_order") w.stage_order = value != 0;
-    else if (n == "spec_pairs") w.spec_pairs = value > 0 ? value : 1;
-    else if (n == "pair_max") w.pair_max = value;
-    else if (n == "pyr_off") { w.pyr_off = value != 0; replan = true; }
-    else if (n == "tiles") { w.tiles = value != 0; replan = true; }
-    else if (n == "deep_stage") { w.deep_stage = value > 0 ? value : 0; replan = true; }
-    else if (n == "deep_lds") { w.deep_lds = value != 0; replan = true; }
-    else { ctx->set_error("unknown option: " + n); return NVCA_ERR_ARG; }
+    if (!option_set(ctx->sw, name, value, &replan)) { ctx->set_error(std::string("unknown option: ") + name); return NVCA_ERR_ARG; }
+    if (!strcmp(name, "host_threads")) { work_pool_destroy(ctx->pool); ctx->pool = nullptr; ctx->pool_tried = false; }     // the pool is rebuilt at its next use
     if (replan) {
         for (auto &kv : ctx->plans) if (kv.second->inflight) { ctx->set_error("a batch is in flight: collect it before changing a plan option"); return NVCA_ERR_ARG; }
         (void)hipSetDevice(ctx->device);
@@ -141,32 +117,7 @@ int nvca_ctx_get_option(nvca_ctx *ctx, const char *name, int *value)
 try {
     NVCA_LOCK_OR_FAIL(ctx);
     if (!name || !value) return NVCA_ERR_ARG;
-    const std::string n(name);
-    const Switches &w = ctx->sw;
-    if (n == "band") *value = w.band;
-    else if (n == "band_map") *value = w.band_map;
-    else if (n == "group_zerocopy") *value = w.group_zero_copy;
-    else if (n == "host_group") *value = w.host_group;
-    else if (n == "skip_cascade") *value = w.skip_cascade;
-    else if (n == "host_profile") *value = w.host_profile;
-    else if (n == "sparse_ingest") *value = w.sparse_ingest;
-    else if (n == "ingest_chunk") *value = w.ingest_chunk;
-    else if (n == "part_stats") *value = w.part_stats;
-    else if (n == "trk_order") *value = w.trk_order;
-    else if (n == "trk_fold") *value = w.trk_fold;
-    else if (n == "quiet") *value = w.quiet;
-    else if (n == "roi") *value = w.roi;
-    else if (n == "fb_dense") *value = w.fb_dense;
-    else if (n == "host_threads") *value = w.host_threads;
-    else if (n == "plan_debug") *value = w.plan_debug;
-    else if (n == "stage_order") *value = w.stage_order;
-    else if (n == "spec_pairs") *value = w.spec_pairs;
-    else if (n == "pair_max") *value = w.pair_max;
-    else if (n == "pyr_off") *value = w.pyr_off;
-    else if (n == "tiles") *value = w.tiles;
-    else if (n == "deep_stage") *value = w.deep_stage;
-    else if (n == "deep_lds") *value = w.deep_lds;
-    else { ctx->set_error("unknown option: " + n); return NVCA_ERR_ARG; }
+    if (!option_get(ctx->sw, name, value)) { ctx->set_error(std::string("unknown option: ") + name); return NVCA_ERR_ARG; }
     return NVCA_OK;
 }
 NVCA_API_CATCH(ctx)

@@ -1,10 +1,10 @@
-// kernels_cascade.hip -- the Haar cascade evaluator (scale-cascade variant,
+// kernels_cascade_tile.hip -- the Haar cascade evaluator on LDS lattice tiles (scale-cascade variant,
 // flags without CV_HAAR_SCALE_IMAGE): replaces the per-window loop of
 // HaarDetectObjects_ScaleCascade_Invoker + cvRunHaarClassifierCascadeSum
 // (OpenCV 2.4 haar.cpp) behind cascade->detectMultiScale at
 // FACE/kmsfacedetect.cpp:809-811.
 //
-// Launches per batch of frames:
+// Launches per batch of frames (the other kernels: kernels_cascade_gather.hip, kernels_cascade_deep.hip, kernels_group.hip):
 //  K5  k_band        (batches with >= 540 bands in flight, plans.cpp) one workgroup per row of tiles of a
 //                    scale, walking it left to right: per tile (<= 32 x 24 windows, a window per thread) the integral
 //                    samples the windows touch are staged, compacted, in LDS; window variance and
@@ -24,12 +24,10 @@
 // (scalar loads) and per-lane in K5c.  No MFMA: integer rect sums, f32 products, f64 stage sums --
 // exactly the reference's arithmetic (compiled with -ffp-contract=off).
 #include "nvca_internal.h"
+#include "cascade_device.h"
 
 namespace nvca {
 
-// Wave-uniform table records are read through the constant address space: the compiler then issues scalar loads
-// (s_load) for them even though the kernels also store to global memory.  The tables are never written by a kernel.
-typedef const __attribute__((address_space(4))) TStumpRec CTStumpRec;
 // a small plain record at a wave-uniform address, read dword by dword through the constant address space (s_load)
 template <class T> __device__ __forceinline__ T load_const(const T *p)
 {
@@ -43,441 +41,12 @@ template <class T> __device__ __forceinline__ T load_const(const T *p)
     return r;
 }
 
-__device__ __forceinline__ int ldsum(const int *__restrict__ sum, unsigned idx) { return sum[idx]; }
-
-// Squared-pixel sum of the variance window from the squared integral, as the f64 OpenCV computes (every operand and every
-// partial result is an integer below 2^53, so the f64 chain is exact and equals the integer result).  The plane pair is a
-// u32 low-word plane and a u8 high-byte plane (the values stay below 2^40 whenever the i32 sum plane is valid); when the
-// window's sum is known to be below 2^32 the low words alone give it, modulo 2^32.
-__device__ __forceinline__ double window_sqsum(const unsigned *__restrict__ sql, const uint8_t *__restrict__ sqh, bool lo_only,
-                                               unsigned e0, unsigned e1, unsigned e2, unsigned e3)
-{
-    if (lo_only) return (double)(unsigned)(sql[e0] - sql[e1] - sql[e2] + sql[e3]);
-    const unsigned long long q0 = ((unsigned long long)sqh[e0] << 32) | sql[e0], q1 = ((unsigned long long)sqh[e1] << 32) | sql[e1];
-    const unsigned long long q2 = ((unsigned long long)sqh[e2] << 32) | sql[e2], q3 = ((unsigned long long)sqh[e3] << 32) | sql[e3];
-    return (double)q0 - (double)q1 - (double)q2 + (double)q3;
-}
-
-// feature value of one stump on one window (v) against its threshold: returns the vote.  Records hold corner columns /
-// rows relative to the window (geometry-independent tables); the plane offset is row * pitch + column.
-template <bool PAIR, class Rec, bool UNI = false>
-__device__ __forceinline__ double stump_vote(const int *__restrict__ sum, unsigned off, int pitch, double vnf, Rec &f)
-{
-    auto rs = [&](int q) {
-        const unsigned r0 = off + (unsigned)(f.y0[q] * pitch), r1 = off + (unsigned)(f.y1[q] * pitch);
-        return ldsum(sum, r0 + (unsigned)f.x0[q]) - ldsum(sum, r0 + (unsigned)f.x1[q]) - ldsum(sum, r1 + (unsigned)f.x0[q]) +
-               ldsum(sum, r1 + (unsigned)f.x1[q]);
-    };
-    const int s0 = rs(0);
-    const int s1 = rs(1);
-    const double t = f.thr * vnf;                       // node->threshold * variance_norm_factor
-    double v;
-    if (PAIR) {
-        const float fs = (float)s0 * f.w[0] + (float)s1 * f.w[1];     // SSE2 path: f32 add
-        v = (double)fs;
-    } else {
-        v = (double)((float)s0 * f.w[0]);
-        v += (double)((float)s1 * f.w[1]);
-        if ((f.nrect & 255) == 3) {
-            const int s2 = rs(2);
-            v += (double)((float)s2 * f.w[2]);
-        }
-    }
-    double a0 = f.a0, a1 = f.a1;
-    if (UNI) asm("" : "+s"(a0), "+s"(a1));      // wave-uniform record: both votes stay in scalar registers
-    return v >= t ? a1 : a0;
-}
-
-// one stage on one window per lane; recs are wave-uniform (scalar loads)
-template <bool PAIR>
-__device__ __forceinline__ bool eval_stage(const int *__restrict__ sum, unsigned off, int pitch, double vnf,
-                                           CTStumpRec *recs, int count, float stage_thr)
-{
-    double stage_sum = 0.0;
-    for (int j = 0; j < count; j++) stage_sum += stump_vote<PAIR, CTStumpRec, true>(sum, off, pitch, vnf, recs[j]);
-    return !(stage_sum < (double)stage_thr);
-}
-
-__device__ __forceinline__ bool run_stage(const int *__restrict__ sum, unsigned off, int pitch, double vnf,
-                                          CTStumpRec *recs, const StageRec &st, int pair_policy)
-{
-    if (pair_policy && (st.flags & 1)) return eval_stage<true>(sum, off, pitch, vnf, recs + st.first, st.count, st.thr);
-    return eval_stage<false>(sum, off, pitch, vnf, recs + st.first, st.count, st.thr);
-}
-
-// block -> (slot, local index): 1-D grid, frame-major (few integral planes live at a time); within a
-// frame consecutive local indices alternate over 8 contiguous chunks, i.e. blocks that share an XCD
-// (b % 8) walk one contiguous part of the scan (speed only)
-__device__ __forceinline__ bool xcd_chunk_index(int nlocal, int &slot, int &idx)
-{
-    const int per_frame = ((nlocal + 7) / 8) * 8;
-    slot = blockIdx.x / per_frame;
-    const int l = blockIdx.x - slot * per_frame;
-    const int chunk = per_frame / 8;
-    idx = (l & 7) * chunk + (l >> 3);
-    return idx < nlocal;
-}
-
-// ---- K5a: variance + stage 0 for every window --------------------------------
-__global__ __launch_bounds__(256) void k_stage0(CascadeArgs a)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int slot, bidx;
-    if (!xcd_chunk_index((a.ntasks + 3) / 4, slot, bidx)) return;
-    const int t = __builtin_amdgcn_readfirstlane(bidx * 4 + wave);
-    if (t >= a.ntasks) return;
-    const unsigned task = a.tasks[t];
-    const int s = task >> 20, iy = (task >> 7) & 8191, k = task & 127;
-    const ScaleRec &sc = a.scales[s];
-    const int ix = k * 64 + lane;
-    const bool active = ix < sc.endX;
-    const int *__restrict__ sum = a.sum + (size_t)slot * a.sum_slot + sc.plane_off;
-    // squared integral: a u32 low-word plane and a u8 high-byte plane per slot, see k_integral
-    const unsigned *__restrict__ sql = (const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + sc.plane_off;
-    const uint8_t *__restrict__ sqh = (const uint8_t *)((const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + a.sum_slot) + sc.plane_off;
-    bool pass0 = false;
-    double vnf = 1.;
-    if (active) {
-        const unsigned off = (unsigned)(a.pos[sc.ypos_off + iy] * sc.pitch + a.pos[sc.xpos_off + ix]);
-        const unsigned e0 = off + sc.eq[0], e1 = off + sc.eq[1], e2 = off + sc.eq[2], e3 = off + sc.eq[3];
-        const int ws = sum[e0] - sum[e1] - sum[e2] + sum[e3];
-        const double mean = (double)ws * sc.inv_area;
-        vnf = window_sqsum(sql, sqh, sc.sq32 != 0, e0, e1, e2, e3);
-        vnf = vnf * sc.inv_area - mean * mean;
-        vnf = vnf >= 0. ? sqrt(vnf) : 1.;
-        pass0 = run_stage(sum, off, sc.pitch, vnf, (CTStumpRec *)sc.trecs, a.stages[0], a.pair_policy);
-    }
-    const unsigned long long fb = __ballot(active && !pass0);
-    const size_t o = (size_t)slot * a.ntasks + t;
-    if (lane == 0) a.failbits[o] = fb;
-    a.vnf[o * 64 + lane] = vnf;
-}
-
-// visited by OpenCV's adaptive scan?  row_bits: the row's stage-0 reject words
-__device__ __forceinline__ bool visited(const unsigned long long *__restrict__ row_bits, int ix)
-{
-    int d = 0, pos = ix;
-    while (pos > 0) {
-        const int p = pos - 1, b = p & 63;
-        const unsigned long long m = row_bits[p >> 6] << (63 - b);       // bit p at the MSB
-        const int ones = (~m == 0ull) ? 64 : __clzll((long long)~m);
-        const int lim = b + 1;
-        d += ones < lim ? ones : lim;
-        if (ones < lim) break;
-        pos -= lim;
-    }
-    return !(d & 1);
-}
-
-// ---- general cascades: tree-structured weak classifiers and / or tilted features ----------------------------------------
-// cvRunHaarClassifierCascadeSum's general branch: per weak classifier a walk idx = sum < t ? left : right from the root to
-// a leaf, whose value is the vote; a feature's rectangles read the integral image or, for a tilted feature, the tilted
-// integral.  Window per lane, global reads (these cascades run on the part detectors' small working images; the LDS tile
-// machinery above is built around upright stumps).  The stage loop is wave-uniform, so the root of every weak classifier is
-// a scalar record; only the nodes below it are per-lane.
-typedef const __attribute__((address_space(4))) GNodeRec CGNodeRec;
-template <class Rec>
-__device__ __forceinline__ double gen_node_sum(const int *__restrict__ pl, unsigned off, int pitch, const Rec &n, bool pair)
-{
-    auto rs = [&](int q) {
-        return pl[off + (unsigned)(n.dy[q][0] * pitch + n.dx[q][0])] - pl[off + (unsigned)(n.dy[q][1] * pitch + n.dx[q][1])] -
-               pl[off + (unsigned)(n.dy[q][2] * pitch + n.dx[q][2])] + pl[off + (unsigned)(n.dy[q][3] * pitch + n.dx[q][3])];
-    };
-    const int s0 = rs(0), s1 = rs(1);
-    if (pair) return (double)((float)s0 * n.w[0] + (float)s1 * n.w[1]);       // SSE2 path of two-rectangle stump stages
-    double v = (double)((float)s0 * n.w[0]);
-    v += (double)((float)s1 * n.w[1]);
-    if ((n.flags & 255) == 3) v += (double)((float)rs(2) * n.w[2]);
-    return v;
-}
-// The weak classifiers of a stage are independent of one another up to their votes: four roots are evaluated per step -- their
-// 32 to 48 gathers are in flight together instead of one classifier's at a time -- then each walk is finished and the votes are
-// added in stage order (OpenCV's order: the f64 sum is the same).
-__device__ __forceinline__ bool gen_stage(const CascadeArgs &a, const int *__restrict__ sum, const int *__restrict__ tilt, unsigned off, int pitch,
-                                          double vnf, const GNodeRec *recs, const StageRec &st)
-{
-    const bool pair = a.pair_policy && a.stump_based && (st.flags & 1);
-    double stage_sum = 0.0;
-    auto finish = [&](int base, int idx) {                                  // below the root the lanes of a wave part ways
-        while (idx > 0) {
-            const GNodeRec &n = recs[base + idx];
-            const double sn = gen_node_sum((n.flags & 256) ? tilt : sum, off, pitch, n, false);
-            idx = sn < (double)n.thr * vnf ? n.left : n.right;
-        }
-        return (double)a.galpha[-idx];
-    };
-    int j = 0;
-    for (; j + 4 <= st.count; j += 4) {
-        int base[4], idx[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            base[u] = a.gcls_first[st.first + j + u];
-            CGNodeRec &root = ((CGNodeRec *)recs)[base[u]];
-            const double s = gen_node_sum((root.flags & 256) ? tilt : sum, off, pitch, root, pair);
-            idx[u] = s < (double)root.thr * vnf ? root.left : root.right;   // node->threshold * variance_norm_factor
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) stage_sum += finish(base[u], idx[u]);
-    }
-    for (; j < st.count; j++) {
-        const int base = a.gcls_first[st.first + j];
-        CGNodeRec &root = ((CGNodeRec *)recs)[base];
-        const double s = gen_node_sum((root.flags & 256) ? tilt : sum, off, pitch, root, pair);
-        stage_sum += finish(base, s < (double)root.thr * vnf ? root.left : root.right);
-    }
-    return !(stage_sum < (double)st.thr);
-}
-
-__global__ __launch_bounds__(256) void k_gen_stage0(CascadeArgs a)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int slot, bidx;
-    if (!xcd_chunk_index((a.ntasks + 3) / 4, slot, bidx)) return;
-    const int t = __builtin_amdgcn_readfirstlane(bidx * 4 + wave);
-    if (t >= a.ntasks) return;
-    const unsigned task = a.tasks[t];
-    const int s = task >> 20, iy = (task >> 7) & 8191, k = task & 127;
-    const ScaleRec &sc = a.scales[s];
-    const int ix = k * 64 + lane;
-    const bool active = ix < sc.endX;
-    const int *__restrict__ sum = a.sum + (size_t)slot * a.sum_slot + sc.plane_off;
-    const int *__restrict__ tilt = a.tilted ? a.tilted + (size_t)slot * a.sum_slot + sc.plane_off : sum;
-    const unsigned *__restrict__ sql = (const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + sc.plane_off;
-    const uint8_t *__restrict__ sqh = (const uint8_t *)((const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + a.sum_slot) + sc.plane_off;
-    bool pass0 = false;
-    double vnf = 1.;
-    if (active) {
-        const unsigned off = (unsigned)(a.pos[sc.ypos_off + iy] * sc.pitch + a.pos[sc.xpos_off + ix]);
-        const unsigned e0 = off + sc.eq[0], e1 = off + sc.eq[1], e2 = off + sc.eq[2], e3 = off + sc.eq[3];
-        const int ws = sum[e0] - sum[e1] - sum[e2] + sum[e3];
-        const double mean = (double)ws * sc.inv_area;
-        vnf = window_sqsum(sql, sqh, sc.sq32 != 0, e0, e1, e2, e3);
-        vnf = vnf * sc.inv_area - mean * mean;
-        vnf = vnf >= 0. ? sqrt(vnf) : 1.;
-        pass0 = gen_stage(a, sum, tilt, off, sc.pitch, vnf, sc.grecs, a.stages[0]);
-    }
-    const unsigned long long fb = __ballot(active && !pass0);
-    const size_t o = (size_t)slot * a.ntasks + t;
-    if (lane == 0) a.failbits[o] = fb;
-    a.vnf[o * 64 + lane] = vnf;
-}
-
-__global__ __launch_bounds__(256) void k_gen_rest(CascadeArgs a)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int slot, bidx;
-    if (!xcd_chunk_index((a.ntasks + 3) / 4, slot, bidx)) return;
-    const int t = __builtin_amdgcn_readfirstlane(bidx * 4 + wave);
-    if (t >= a.ntasks) return;
-    const unsigned task = a.tasks[t];
-    const int s = task >> 20, iy = (task >> 7) & 8191, k = task & 127;
-    const ScaleRec &sc = a.scales[s];
-    const int ix = k * 64 + lane;
-    const unsigned long long *rb = a.failbits + (size_t)slot * a.ntasks + sc.task_off + (size_t)iy * sc.wpr;
-    bool alive = false;
-    if (ix < sc.endX && !((rb[k] >> lane) & 1ull)) alive = sc.adaptive ? visited(rb, ix) : true;
-    if (!__any(alive)) return;
-    const int *__restrict__ sum = a.sum + (size_t)slot * a.sum_slot + sc.plane_off;
-    const int *__restrict__ tilt = a.tilted ? a.tilted + (size_t)slot * a.sum_slot + sc.plane_off : sum;
-    unsigned off = 0; double vnf = 1.;
-    if (alive) {
-        off = (unsigned)(a.pos[sc.ypos_off + iy] * sc.pitch + a.pos[sc.xpos_off + ix]);
-        vnf = a.vnf[((size_t)slot * a.ntasks + t) * 64 + lane];
-    }
-    for (int st_i = 1; st_i < a.nstages; st_i++) {           // wave-uniform stage loop: lanes that fell out idle
-        if (!__any(alive)) return;
-        if (alive) alive = gen_stage(a, sum, tilt, off, sc.pitch, vnf, sc.grecs, a.stages[st_i]);
-    }
-    const unsigned long long hm = __ballot(alive);
-    if (!hm) return;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(a.hits, (unsigned long long)__popcll(hm));
-    base = __shfl(base, 0);
-    if (alive) {
-        const unsigned long long pos = base + __popcll(hm & ((1ull << lane) - 1ull));
-        const unsigned key = ((unsigned)s << a.key_ss) | ((unsigned)iy << a.key_sy) | (unsigned)ix;
-        if (pos < a.hit_cap) a.hits[1 + pos] = ((unsigned long long)slot << 32) | key;
-    }
-}
-
-void launch_generic(hipStream_t st, const CascadeArgs &a, int batch, int which)
-{
-    if (batch <= 0 || a.ntasks <= 0) return;
-    const int blocks = (((a.ntasks + 3) / 4 + 7) / 8) * 8;
-    if (which == 0) NVCA_LAUNCH(k_gen_stage0, dim3((unsigned)blocks * (unsigned)batch), dim3(256), 0, st, a);
-    else NVCA_LAUNCH(k_gen_rest, dim3((unsigned)blocks * (unsigned)batch), dim3(256), 0, st, a);
-}
-
-// ---- K5b: stages 1 .. deep_stage-1 on strips ---------------------------------
-__global__ __launch_bounds__(256) void k_strip(CascadeArgs a)
-{
-    __shared__ unsigned short q[2][kStripMaxWin];
-    __shared__ double psum[256];
-    __shared__ int qn[2];
-    __shared__ unsigned gbase_s;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int slot = blockIdx.x / a.blocks_per_frame;
-    const int sidx = a.order[blockIdx.x - slot * a.blocks_per_frame];
-    if (sidx < 0) return;
-    const StripRec strip = a.strips[sidx];
-    const ScaleRec &sc = a.scales[strip.scale];
-    // a strip covers columns [ix0, ix0 + ncols) of nrows scan rows (rows longer than a strip are cut into segments)
-    const int endX = strip.ncols, ix0 = strip.ix0, nwin = strip.nrows * endX;
-    const int *__restrict__ sum = a.sum + (size_t)slot * a.sum_slot + sc.plane_off;
-    CTStumpRec *recs = (CTStumpRec *)sc.trecs;
-    const int *__restrict__ xpos = a.pos + sc.xpos_off;
-    const int *__restrict__ ypos = a.pos + sc.ypos_off + strip.iy0;
-    const unsigned long long *__restrict__ bits = a.failbits + (size_t)slot * a.ntasks + sc.task_off + (size_t)strip.iy0 * sc.wpr;
-    const double *__restrict__ vnfp = a.vnf + ((size_t)slot * a.ntasks + sc.task_off + (size_t)strip.iy0 * sc.wpr) * 64;
-
-    if (tid < 2) qn[tid] = 0;
-    __syncthreads();
-
-    // adaptive-step reachability + compaction of visited stage-0 survivors
-    for (int base = 0; base < nwin; base += 256) {
-        const int w = base + tid;
-        bool keep = false;
-        if (w < nwin) {
-            const int r = w / endX, ix = ix0 + (w - r * endX);
-            const unsigned long long *rb = bits + (size_t)r * sc.wpr;
-            if (!((rb[ix >> 6] >> (ix & 63)) & 1ull)) keep = sc.adaptive ? visited(rb, ix) : true;
-        }
-        const unsigned long long km = __ballot(keep);
-        if (km) {
-            int wbase = 0;
-            if (lane == 0) wbase = atomicAdd(&qn[0], __popcll(km));
-            wbase = __shfl(wbase, 0);
-            if (keep) q[0][wbase + __popcll(km & ((1ull << lane) - 1ull))] = (unsigned short)w;
-        }
-    }
-
-    int cur = 0;
-    int last = a.deep_stage < a.nstages ? a.deep_stage : a.nstages;
-    for (int s = 1; s < last; s++) {
-        __syncthreads();
-        const int n = qn[cur];
-        if (n == 0) break;
-        if (tid == 0) qn[cur ^ 1] = 0;
-        __syncthreads();
-        const StageRec st = a.stages[s];
-        if ((st.flags & 2) && n <= 128) {
-            // Few survivors: most lanes would idle while one wave walks the whole stage.  The votes of this stage may be
-            // summed in any order (flag bit 1), so spread its stumps over the idle lanes: thread = (window slot i,
-            // stump partition p); partition p takes stumps p, p+P, ...; partial sums meet in LDS.
-            int lg = 0;
-            while ((1 << lg) < n) lg++;
-            const int npad = 1 << lg;
-            int P = 256 >> lg;
-            if (P > st.count) P = st.count;
-            const int i = tid & (npad - 1), p = tid >> lg;
-            double part = 0.0;
-            int w = 0;
-            if (i < n && p < P) {
-                w = q[cur][i];
-                const int r = w / endX, ix = ix0 + (w - r * endX);
-                const unsigned off = (unsigned)(ypos[r] * sc.pitch + xpos[ix]);
-                const double vnf = vnfp[((size_t)r * sc.wpr + (ix >> 6)) * 64 + (ix & 63)];
-                const bool pair = a.pair_policy && (st.flags & 1);
-                if (lg >= 6) {               // a wave holds one partition: records stay wave-uniform (scalar loads)
-                    const int pu = __builtin_amdgcn_readfirstlane(p);
-                    for (int j = pu; j < st.count; j += P)
-                        part += pair ? stump_vote<true>(sum, off, sc.pitch, vnf, recs[st.first + j]) : stump_vote<false>(sum, off, sc.pitch, vnf, recs[st.first + j]);
-                } else {
-                    for (int j = p; j < st.count; j += P)
-                        part += pair ? stump_vote<true>(sum, off, sc.pitch, vnf, recs[st.first + j]) : stump_vote<false>(sum, off, sc.pitch, vnf, recs[st.first + j]);
-                }
-            }
-            psum[tid] = part;
-            __syncthreads();
-            bool pass = false;
-            if (tid < n) {
-                double tot = 0.0;
-                for (int pp = 0; pp < P; pp++) tot += psum[(pp << lg) + tid];
-                pass = !(tot < (double)st.thr);
-                w = q[cur][tid];
-            }
-            const unsigned long long pm = __ballot(pass);
-            if (pm) {
-                int wbase = 0;
-                if (lane == 0) wbase = atomicAdd(&qn[cur ^ 1], __popcll(pm));
-                wbase = __shfl(wbase, 0);
-                if (pass) q[cur ^ 1][wbase + __popcll(pm & ((1ull << lane) - 1ull))] = (unsigned short)w;
-            }
-        } else
-        for (int base = 0; base < n; base += 256) {
-            const int i = base + tid;
-            bool pass = false; int w = 0;
-            if (i < n) {
-                w = q[cur][i];
-                const int r = w / endX, ix = ix0 + (w - r * endX);
-                const unsigned off = (unsigned)(ypos[r] * sc.pitch + xpos[ix]);
-                const double vnf = vnfp[((size_t)r * sc.wpr + (ix >> 6)) * 64 + (ix & 63)];
-                pass = run_stage(sum, off, sc.pitch, vnf, recs, st, a.pair_policy);
-            }
-            const unsigned long long pm = __ballot(pass);
-            if (pm) {
-                int wbase = 0;
-                if (lane == 0) wbase = atomicAdd(&qn[cur ^ 1], __popcll(pm));
-                wbase = __shfl(wbase, 0);
-                if (pass) q[cur ^ 1][wbase + __popcll(pm & ((1ull << lane) - 1ull))] = (unsigned short)w;
-            }
-        }
-        cur ^= 1;
-    }
-    __syncthreads();
-    const int nh = qn[cur];
-    if (nh == 0) return;
-    // survivors: final candidates if the cascade ends here, otherwise work for k_deep
-    unsigned long long *list = last == a.nstages ? a.hits : a.deep;
-    const unsigned cap = last == a.nstages ? a.hit_cap : a.deep_cap;
-    if (tid == 0) gbase_s = (unsigned)atomicAdd(list, (unsigned long long)nh);
-    __syncthreads();
-    const unsigned gb = gbase_s;
-    for (int i = tid; i < nh; i += 256) {
-        const int w = q[cur][i];
-        const int r = w / endX, ix = ix0 + (w - r * endX);
-        const unsigned key = ((unsigned)strip.scale << a.key_ss) | ((unsigned)(strip.iy0 + r) << a.key_sy) | (unsigned)ix;
-        if (gb + i < cap) list[1 + gb + i] = ((unsigned long long)slot << 32) | key;
-    }
-}
-
 // ---- K5b: stages 1 .. deep_stage-1 on LDS lattice tiles -------------------------------------
 // A tile is nx x ny (<= 32 x 24) windows of one scale.  Window origins and scaled rectangle corners of a scale
 // fall on a near-lattice, so the tile's windows touch only ~2.7 (n + 20) distinct columns and rows of the sum
 // plane whatever the scale.  Those rows x columns are copied, compacted, into LDS once; every rectangle corner
 // is then two u16 map look-ups (column index, row offset) and one LDS read, instead of a global gather whose 64
 // lanes touch up to 64 different cache lines.  Values and arithmetic are unchanged.
-template <bool PAIR, bool UNI = true>
-__device__ __forceinline__ double tile_vote(const int *T, const unsigned short *cmap, const unsigned short *rmap,
-                                            int xw, int yw, double vnf, CTStumpRec &f)
-{
-    // the row map holds WORD offsets of the row starts from T, the column map BYTE offsets: a corner address is one shift-add
-    auto at = [&](int rw, int cb) { return *(const int *)((const char *)T + ((rw << 2) + cb)); };
-    auto rs = [&](int q) {
-        const int c0 = cmap[xw + f.x0[q]], c1 = cmap[xw + f.x1[q]];
-        const int r0 = rmap[yw + f.y0[q]], r1 = rmap[yw + f.y1[q]];
-        return at(r0, c0) - at(r0, c1) - at(r1, c0) + at(r1, c1);
-    };
-    const int s0 = rs(0);
-    const int s1 = rs(1);
-    const double t = f.thr * vnf;
-    double v;
-    if (PAIR) {
-        const float fs = (float)s0 * f.w[0] + (float)s1 * f.w[1];
-        v = (double)fs;
-    } else {
-        v = (double)((float)s0 * f.w[0]);
-        v += (double)((float)s1 * f.w[1]);
-        if ((f.nrect & 255) == 3) {
-            const int s2 = rs(2);
-            v += (double)((float)s2 * f.w[2]);
-        }
-    }
-    double a0 = f.a0, a1 = f.a1;
-    if (UNI) asm("" : "+s"(a0), "+s"(a1));      // wave-uniform record: both votes stay in scalar registers (no dependent load of the selected one)
-    return v >= t ? a1 : a0;
-}
 
 // A wave-uniform record held whole in scalar registers.  Left to itself the compiler fetches a record piecemeal, each
 // piece right before its use (corners; weights; threshold; votes): four dependent scalar-memory round trips per stump on
@@ -1133,264 +702,6 @@ __global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_band(Cascad
     }
 }
 
-// ---- K5c: one wave per surviving window, one stump per lane -------------------
-__device__ __forceinline__ double wave_sum_exact(double v)
-{   // only used where every partial sum is exactly representable (StageRec flag bit 1)
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-__global__ __launch_bounds__(256) void k_deep(CascadeArgs a)
-{
-    // one workgroup per surviving window: every late stage (33..213 stumps) is one step, stump per thread.  The first late
-    // stage reads the sum plane directly; a window that passes it gets the ncol x nrow samples all later stumps can touch
-    // staged in LDS (DeepRec), and the remaining ~1900 stumps x 8-12 corners become LDS reads.
-    __shared__ double part[2][4];
-    __shared__ double votes[256];
-    extern __shared__ int T[];              // the patch: sized by the plan's largest (a.deep_lds) -- the kernel lives on the windows in flight per CU
-    __shared__ unsigned short cmap[kDeepMaxSpan], rmap[kDeepMaxSpan];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long cnt = a.deep[0];
-    if (cnt > a.deep_cap) {                              // list overflowed: poison the hit count (host reports it)
-        if (blockIdx.x == 0 && tid == 0) atomicAdd(a.hits, 1ull << 40);
-        cnt = a.deep_cap;
-    }
-    int flip = 0;                                        // partial-sum buffers alternate across stages AND windows
-    for (unsigned long long i = blockIdx.x; i < cnt; i += gridDim.x) {
-        const unsigned long long e = a.deep[1 + i];
-        const int slot = (int)(e >> 32);
-        const unsigned key = (unsigned)e;
-        const int s = key >> a.key_ss, iy = (key >> a.key_sy) & ((1u << (a.key_ss - a.key_sy)) - 1u), ix = key & ((1u << a.key_sy) - 1u);
-        const ScaleRec &sc = a.scales[s];
-        const int *__restrict__ sum = a.sum + (size_t)slot * a.sum_slot + sc.plane_off;
-        const unsigned off = (unsigned)(a.pos[sc.ypos_off + iy] * sc.pitch + a.pos[sc.xpos_off + ix]);
-        const double vnf = a.vnf[((size_t)slot * a.ntasks + sc.task_off + (size_t)iy * sc.wpr + (ix >> 6)) * 64 + (ix & 63)];
-        DeepRec d; d.ncol = 0;
-        if (a.deeprecs) d = a.deeprecs[s];
-        CTStumpRec *trecs = (CTStumpRec *)sc.trecs;
-        bool alive = true, patch = false;
-        for (int st_i = a.deep_stage; st_i < a.nstages; st_i++) {
-            const StageRec st = a.stages[st_i];
-            const bool pair = a.pair_policy && (st.flags & 1);
-            double stage_sum = 0.0;
-            if (st_i == a.deep_stage + 1 && d.ncol > 0) {           // passed the first late stage: stage the patch
-                const unsigned short *__restrict__ cl = a.tcoords + d.col_off, *__restrict__ rl = a.tcoords + d.row_off;
-                const int pitchP = d.ncol | 1;
-                __syncthreads();                                  // previous window's patch reads are over
-                for (int c = tid; c < d.ncol; c += 256) cmap[cl[c]] = (unsigned short)(c * 4);
-                for (int r = tid; r < d.nrow; r += 256) rmap[rl[r]] = (unsigned short)(r * pitchP);
-                for (int q = tid; q < d.ncol * d.nrow; q += 256) {
-                    const int r = q / d.ncol, c = q - r * d.ncol;
-                    T[r * pitchP + c] = sum[off + (unsigned)rl[r] * (unsigned)sc.pitch + cl[c]];
-                }
-                __syncthreads();
-                patch = true;
-            }
-            auto vote = [&](int j) {
-                if (patch) return pair ? tile_vote<true, false>(T, cmap, rmap, 0, 0, vnf, trecs[st.first + j])
-                                       : tile_vote<false, false>(T, cmap, rmap, 0, 0, vnf, trecs[st.first + j]);
-                return pair ? stump_vote<true>(sum, off, sc.pitch, vnf, trecs[st.first + j]) : stump_vote<false>(sum, off, sc.pitch, vnf, trecs[st.first + j]);
-            };
-            if (st.flags & 2) {                         // any summation order is exact
-                double p = 0.0;
-                for (int j = tid; j < st.count; j += 256) p += vote(j);
-                p = wave_sum_exact(p);
-                if (lane == 0) part[flip][wave] = p;
-                __syncthreads();
-                stage_sum = (part[flip][0] + part[flip][1]) + (part[flip][2] + part[flip][3]);
-                flip ^= 1;
-            } else {                                    // keep OpenCV's left-to-right order
-                for (int c = 0; c < st.count; c += 256) {
-                    const int j = c + tid;
-                    const double v = j < st.count ? vote(j) : 0.0;
-                    __syncthreads();
-                    votes[tid] = v;
-                    __syncthreads();
-                    const int m = st.count - c < 256 ? st.count - c : 256;
-                    for (int l = 0; l < m; l++) stage_sum += votes[l];      // every thread walks the same order
-                }
-            }
-            if (stage_sum < (double)st.thr) { alive = false; break; }
-        }
-        if (alive && tid == 0) {
-            const unsigned long long h = atomicAdd(a.hits, 1ull);
-            if (h < a.hit_cap) a.hits[1 + h] = e;
-        }
-    }
-}
-
-// ---- K6: groupRectangles on the device, one workgroup per frame ----------------------------------
-// cv::groupRectangles(rects, groupThreshold, 0.2) as called at the end of cvHaarDetectObjectsForROC
-// (cascadedetect.cpp / operations.hpp partition()).  The raw candidates of a frame are pulled out of the
-// batch-wide list, sorted by key (= OpenCV's serial scan order: scale, y, x), clustered with a min-index
-// union-find in LDS (class numbering by first member, as cv::partition assigns it), averaged with the same
-// float rounding, filtered, and written as final boxes: the host only receives boxes.
-static constexpr int kGroupMax = 2048;       // raw candidates per frame handled on the device
-
-__device__ __forceinline__ bool similar_rects(const int4 &a, const int4 &b, double eps)
-{
-    const double delta = eps * ((a.z < b.z ? a.z : b.z) + (a.w < b.w ? a.w : b.w)) * 0.5;
-    return abs(a.x - b.x) <= delta && abs(a.y - b.y) <= delta && abs(a.x + a.z - b.x - b.z) <= delta &&
-           abs(a.y + a.w - b.y - b.w) <= delta;
-}
-
-__global__ __launch_bounds__(256) void k_group(CascadeArgs a, const int *__restrict__ group_thr, int *__restrict__ out, int out_cap)
-{
-    __shared__ unsigned keys[kGroupMax];
-    __shared__ int parent[kGroupMax];
-    __shared__ int cls_of[kGroupMax];          // class id of a root; then reused
-    __shared__ int4 rects[kGroupMax];
-    __shared__ int csum[4][256], ccnt[256];    // per-class sums (classes beyond 256 -> fallback)
-    __shared__ int n_s, ncls_s, fallback_s;
-    const int tid = threadIdx.x, slot = blockIdx.x;
-    int *o = out + (size_t)slot * (2 + 4 * out_cap);       // [0] = count (-1: host must group), [1] = raw count
-    if (tid == 0) { n_s = 0; ncls_s = 0; fallback_s = 0; }
-    __syncthreads();
-    unsigned long long total = a.hits[0];
-    if (slot == 0 && tid == 0) {               // the raw candidate count travels with the box table (two words after the last record)
-        int *tail = out + (size_t)gridDim.x * (2 + 4 * out_cap);
-        tail[0] = (int)(unsigned)(total & 0xffffffffull); tail[1] = (int)(unsigned)(total >> 32);
-    }
-    if (total > a.hit_cap) total = a.hit_cap;
-    for (unsigned long long i = tid; i < total; i += 256) {
-        const unsigned long long e = a.hits[1 + i];
-        if ((int)(e >> 32) == slot) {
-            const int k = atomicAdd(&n_s, 1);
-            if (k < kGroupMax) keys[k] = (unsigned)e;
-        }
-    }
-    __syncthreads();
-    const int n = n_s;
-    const int thr = group_thr[slot];
-    if (tid == 0) o[1] = n;
-    if (n > kGroupMax || thr <= 0) { if (tid == 0) o[0] = -1; return; }       // host path (rare / ungrouped)
-    if (n == 0) { if (tid == 0) o[0] = 0; return; }
-    // ---- keys in ascending order.  Up to 256 of them (the usual case: a few dozen candidates per face): every thread counts
-    // the keys below its own (keys are distinct windows; equal keys would be told apart by position) and stores it at that
-    // rank -- two barriers instead of the ~30 of a bitonic network, which is what longer lists go through
-    if (n <= 256) {
-        const unsigned mine = tid < n ? keys[tid] : 0u;
-        int rank = 0;
-        if (tid < n)
-            for (int j = 0; j < n; j++) { const unsigned o = keys[j]; rank += (o < mine || (o == mine && j < tid)) ? 1 : 0; }
-        __syncthreads();
-        if (tid < n) keys[rank] = mine;
-        __syncthreads();
-    } else {
-        int np = 1;
-        while (np < n) np <<= 1;
-        for (int i = n + tid; i < np; i += 256) keys[i] = 0xffffffffu;
-        __syncthreads();
-        for (int k = 2; k <= np; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < np; i += 256) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const unsigned x = keys[i], y = keys[l];
-                        const bool up = (i & k) == 0;
-                        if ((x > y) == up) { keys[i] = y; keys[l] = x; }
-                    }
-                }
-                __syncthreads();
-            }
-    }
-    // ---- rectangles + singleton sets
-    for (int i = tid; i < n; i += 256) {
-        const unsigned key = keys[i];
-        const int s = key >> a.key_ss, iy = (key >> a.key_sy) & ((1u << (a.key_ss - a.key_sy)) - 1u), ix = key & ((1u << a.key_sy) - 1u);
-        const ScaleRec &sc = a.scales[s];
-        rects[i] = make_int4(a.pos[sc.xpos_off + ix], a.pos[sc.ypos_off + iy], sc.winw, sc.winh);
-        parent[i] = i;
-    }
-    __syncthreads();
-    // ---- union of similar pairs (root = smallest member index)
-    const long long npairs = (long long)n * (n - 1) / 2;
-    for (long long p = tid; p < npairs; p += 256) {
-        // unrank p -> (i < j)
-        int j = (int)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-        while ((long long)j * (j - 1) / 2 > p) j--;
-        while ((long long)(j + 1) * j / 2 <= p) j++;
-        const int i = (int)(p - (long long)j * (j - 1) / 2);
-        if (!similar_rects(rects[i], rects[j], 0.2)) continue;
-        int x = i, y = j;
-        for (;;) {
-            while (parent[x] != x) x = parent[x];
-            while (parent[y] != y) y = parent[y];
-            if (x == y) break;
-            if (x > y) { const int t = x; x = y; y = t; }
-            const int old = atomicMin(&parent[y], x);
-            if (old == y) break;
-            y = old;
-        }
-    }
-    __syncthreads();
-    // ---- class ids in order of first member; per-class sums
-    for (int i = tid; i < n; i += 256) {
-        int r = i;
-        while (parent[r] != r) r = parent[r];
-        cls_of[i] = r;                         // root index for now
-    }
-    __syncthreads();
-    if (tid == 0) {                             // number the roots in ascending order (n <= 2048: a short serial pass)
-        int c = 0;
-        for (int i = 0; i < n; i++) if (cls_of[i] == i) { parent[i] = c < 256 ? c : 255; c++; }
-        ncls_s = c;
-        if (c > 256) fallback_s = 1;
-    }
-    for (int i = tid; i < 256; i += 256) { csum[0][i] = csum[1][i] = csum[2][i] = csum[3][i] = 0; ccnt[i] = 0; }
-    __syncthreads();
-    if (fallback_s) { if (tid == 0) o[0] = -1; return; }
-    const int ncls = ncls_s;
-    for (int i = tid; i < n; i += 256) {
-        const int c = parent[cls_of[i]];       // class id of my root
-        atomicAdd(&csum[0][c], rects[i].x); atomicAdd(&csum[1][c], rects[i].y);
-        atomicAdd(&csum[2][c], rects[i].z); atomicAdd(&csum[3][c], rects[i].w);
-        atomicAdd(&ccnt[c], 1);
-    }
-    __syncthreads();
-    // ---- class averages: float s = 1.f / n; saturate_cast<int>(sum * s) (round half to even)
-    int4 avg = make_int4(0, 0, 0, 0); int cnt = 0;
-    if (tid < ncls) {
-        cnt = ccnt[tid];
-        const float sc = 1.f / (float)cnt;
-        avg = make_int4(__float2int_rn((float)csum[0][tid] * sc), __float2int_rn((float)csum[1][tid] * sc),
-                        __float2int_rn((float)csum[2][tid] * sc), __float2int_rn((float)csum[3][tid] * sc));
-    }
-    __syncthreads();
-    if (tid < ncls) { rects[tid] = avg; cls_of[tid] = cnt; }      // reuse LDS: class rects and weights
-    __syncthreads();
-    // ---- keep class i unless too weak or inside a stronger one
-    bool keepc = false;
-    if (tid < ncls && cnt > thr) {
-        keepc = true;
-        for (int j = 0; j < ncls; j++) {
-            const int n2 = cls_of[j];
-            if (j == tid || n2 <= thr) continue;
-            const int4 r2 = rects[j];
-            const int dx = __double2int_rn(r2.z * 0.2), dy = __double2int_rn(r2.w * 0.2);
-            if (avg.x >= r2.x - dx && avg.y >= r2.y - dy && avg.x + avg.z <= r2.x + r2.z + dx && avg.y + avg.w <= r2.y + r2.w + dy &&
-                (n2 > (3 > cnt ? 3 : cnt) || cnt < 3)) { keepc = false; break; }
-        }
-    }
-    // ncls <= 256: one ballot-ordered compaction over the 4 waves, in class order
-    __shared__ int wcount[4];
-    const unsigned long long km = __ballot(keepc);
-    if ((tid & 63) == 0) wcount[tid >> 6] = __popcll(km);
-    __syncthreads();
-    int base = 0;
-    for (int wv = 0; wv < (tid >> 6); wv++) base += wcount[wv];
-    if (keepc) {
-        const int pos = base + __popcll(km & ((1ull << (tid & 63)) - 1ull));
-        if (pos < out_cap) { int *q = o + 2 + 4 * pos; q[0] = avg.x; q[1] = avg.y; q[2] = avg.z; q[3] = avg.w; }
-    }
-    if (tid == 0) o[0] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
-}
-
-void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, int *out, int out_cap, int batch)
-{
-    NVCA_LAUNCH(k_group, dim3(batch), dim3(256), 0, st, a, group_thr, out, out_cap);
-}
-
 // Dynamic LDS above 64 KiB has to be granted per function and device (hipFuncSetAttribute SETS the limit, it does not raise
 // it): the limit only ever grows, under one process-wide lock, so a context that needs less can never lower what another
 // context on the same device was granted.  `granted` is the calling context's own record (skips the lock once it is covered).
@@ -1410,33 +721,19 @@ static int grant_lds(const void *fn, int which, int bytes, int *granted)
     return 0;
 }
 
-int launch_cascade_sc(hipStream_t st, const CascadeArgs &a, int batch, int which, int *lds_grant)
+int launch_tile(hipStream_t st, const CascadeArgs &a, int batch, int *lds_grant)
 {
-    if (batch <= 0 || a.ntasks <= 0) return 0;
-    if (which == 0) {
-        const int s0_blocks = (((a.ntasks + 3) / 4 + 7) / 8) * 8;
-        NVCA_LAUNCH(k_stage0, dim3((unsigned)s0_blocks * (unsigned)batch), dim3(256), 0, st, a);
-    } else if (which == 3) {
-        if (a.tile_blocks_per_frame > 0) {
-            if (int e = grant_lds(reinterpret_cast<const void *>(k_tile), 0, a.tile_lds, &lds_grant[0])) return e;
-            NVCA_LAUNCH(k_tile, dim3((unsigned)a.tile_blocks_per_frame * (unsigned)batch), dim3(kTileThreads), (size_t)a.tile_lds, st, a);
-        }
-    } else if (which == 5) {
-        if (a.band_blocks_per_frame > 0) {
-            if (int e = grant_lds(reinterpret_cast<const void *>(k_band), 1, a.tile_lds, &lds_grant[1])) return e;
-            NVCA_LAUNCH(k_band, dim3((unsigned)a.band_blocks_per_frame * (unsigned)batch), dim3(kTileThreads), (size_t)a.tile_lds, st, a);
-        }
-    } else if (which == 1) {
-        if (a.blocks_per_frame > 0)
-            NVCA_LAUNCH(k_strip, dim3((unsigned)a.blocks_per_frame * (unsigned)batch), dim3(256), 0, st, a);
-    } else if (a.deep_stage < a.nstages) {
-        // grid-stride over the list, one window per workgroup at a time; small jobs (the part detectors' ROI searches) do not
-        // need eight thousand workgroups to find a handful of windows
-        long long wg = (long long)a.ntasks * batch / 2;
-        if (wg < 128) wg = 128;
-        if (wg > 8192) wg = 8192;
-        NVCA_LAUNCH(k_deep, dim3((unsigned)wg), dim3(256), (size_t)(a.deeprecs ? a.deep_lds : 0), st, a);
-    }
+    if (batch <= 0 || a.ntasks <= 0 || a.tile_blocks_per_frame <= 0) return 0;
+    if (int e = grant_lds(reinterpret_cast<const void *>(k_tile), 0, a.tile_lds, &lds_grant[0])) return e;
+    NVCA_LAUNCH(k_tile, dim3((unsigned)a.tile_blocks_per_frame * (unsigned)batch), dim3(kTileThreads), (size_t)a.tile_lds, st, a);
+    return 0;
+}
+
+int launch_band(hipStream_t st, const CascadeArgs &a, int batch, int *lds_grant)
+{
+    if (batch <= 0 || a.ntasks <= 0 || a.band_blocks_per_frame <= 0) return 0;
+    if (int e = grant_lds(reinterpret_cast<const void *>(k_band), 1, a.tile_lds, &lds_grant[1])) return e;
+    NVCA_LAUNCH(k_band, dim3((unsigned)a.band_blocks_per_frame * (unsigned)batch), dim3(kTileThreads), (size_t)a.tile_lds, st, a);
     return 0;
 }
 

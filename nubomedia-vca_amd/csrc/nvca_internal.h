@@ -35,7 +35,7 @@ struct Cascade {
     std::vector<float> alpha;
     bool stump_based = true;
     bool has_tilted = false; // some feature reads the tilted integral
-    bool generic() const { return !stump_based || has_tilted; }   // evaluated by the general kernels (kernels_cascade.hip)
+    bool generic() const { return !stump_based || has_tilted; }   // evaluated by the general kernels (kernels_cascade_gather.hip)
     uint64_t uid = 0;       // identity for plan caching
     mutable std::vector<unsigned char> stage_rec_cache;   // StageRec[] (plan.cpp, built on first use: the summation-order proof is per cascade)
 };
@@ -114,7 +114,7 @@ struct TStumpRec {          // a stump with separate corner columns / rows (wind
     int a0i, a1i;           // the votes as integers (a / 2^vote_exp of the stump's stage) where StageRec flag bit 2 is set
                             // 96 bytes: the tile kernels fetch a record with two wide scalar loads (16 + 8 dwords)
 };
-static_assert(sizeof(TStumpRec) == 96, "TStumpRec layout is read dword by dword in kernels_cascade.hip");
+static_assert(sizeof(TStumpRec) == 96, "TStumpRec layout is read dword by dword in kernels_cascade_tile.hip");
 // The same stump in 48 bytes, for lanes that each evaluate a DIFFERENT stump (the tile kernels once few windows of a wave are
 // left: lane = (window, stump) pair): three 16-byte vector loads per lane instead of a record held in scalar registers.
 // Corner coordinates are window-relative pixels TIMES TWO (byte offsets into the tile's u16 maps), low half = first corner;
@@ -124,7 +124,7 @@ struct alignas(16) LStumpRec {
     unsigned xx0, yy0, xx1, yy1, xx2, yy2;      // per rectangle: xx = 2 x0 | 2 x1 << 16, yy = 2 y0 | 2 y1 << 16
     float w0, w1, w2, thr, a0, a1;
 };
-static_assert(sizeof(LStumpRec) == 48, "LStumpRec is read as three int4 in kernels_cascade.hip");
+static_assert(sizeof(LStumpRec) == 48, "LStumpRec is read as three int4 in kernels_cascade_tile.hip");
 // A band is one row of tiles (<= 32 window rows of one scale, the full scan width): k_band walks it left to right in one
 // workgroup, so stage 0 and OpenCV's adaptive x step (which depends on the stage-0 results to the left) need no pre-pass.
 // Per scale: the distinct corner columns / rows (window-relative pixels) of the late stages' stumps.  k_deep stages that
@@ -149,7 +149,7 @@ static_assert(kTilesPerCu * kTileLdsBudget <= 160 * 1024 && kTilesPerCu * kTileT
 static constexpr int kTileMaxCols = 256;            // staged columns per tile (4 per lane)
 // LDS bytes the tile kernel needs for a tile (host sizing and kernel carve-up agree through these)
 __host__ __device__ inline int tile_pitch(int ncol) { return ncol | 1; }
-// fixed part (carve_tile in kernels_cascade.hip): stage accumulators (8 B a queue slot) | two window queues | window origins |
+// fixed part (carve_tile in kernels_cascade_tile.hip): stage accumulators (8 B a queue slot) | two window queues | window origins |
 // counters and stage statistics (32 words: qn[0 .. 3] queue counters and list base, qn[4 .. 15] two sets of stage statistics,
 // qn[16 .. 20] stump counts) | per-window variance normaliser
 __host__ __device__ inline int tile_lds_fixed()
@@ -175,36 +175,39 @@ struct ResizeTab {
 void build_resize_tab(int sw, int sh, int dw, int dh, ResizeTab &t);
 
 // --------------------------------------------------------------------------
-// Environment switches: A/B and diagnostic knobs, all off-path by default and none of them changes a
+// Switches: A/B and diagnostic knobs, one row each in the table of options.cpp; none of them changes a
 // result.  The environment is read ONCE per process -- when the first context is created (nvca_ctx_create) -- never on a hot
 // entry point.  A context starts from those process defaults; nvca_ctx_set_option changes one of them for that context.
 // --------------------------------------------------------------------------
 struct Switches {
-    bool group_zero_copy = true;     // NVCA_GROUP_ZEROCOPY=0: box tables through a copy instead of direct stores to the host buffer
-    bool skip_cascade = false;       // NVCA_SKIP_CASCADE: timing experiments on the pre-processing kernels only
-    bool host_group = false;         // NVCA_HOST_GROUP: cv::groupRectangles on the host
-    int  band_map = 0;               // NVCA_BAND_MAP=1/2: frame-major band walk
-    int  band = -1;                  // NVCA_BAND=0/1: force pre-pass + tile kernels / band kernel (-1: by batch size)
-    bool host_profile = false;       // NVCA_HOST_PROFILE: host-side timing prints
-    bool sparse_ingest = true;       // NVCA_SPARSE_INGEST=0: whole host frames in shrink-first mode
-    bool pyr_off = false;            // NVCA_PYR_OFF: per-level launches for SCALE_IMAGE
-    int  part_stats = 0;             // NVCA_PART_STATS[=n]: phase timers of part batches with n (default 8) or more streams; 0: off
-    int  ingest_chunk = 8;           // NVCA_INGEST_CHUNK=n: chunk size of host-frame batches, 0 = no chunking
-    int  deep_stage = 0;             // NVCA_DEEP_STAGE=s: first stage of k_deep (0: the plan's default)
-    bool tiles = true;               // NVCA_TILES=0: row-strip kernel
-    bool plan_debug = false;         // NVCA_PLAN_DEBUG: per-scale tile sizes on stderr
-    bool deep_lds = true;            // NVCA_DEEP_LDS_OFF: k_deep without LDS patches
-    bool trk_fold = true;            // NVCA_TRK_FOLD=0: NuboTracker's components through the per-pixel kernels (k_ccl_flatten / _reduce / _collect) instead of the per-tile reduction + fold of tile roots
-    int  trk_order = -1;             // NVCA_TRK_ORDER: visiting order of k_ccl_reduce (-1: decided per frame on the device)
-    int  host_threads = -1;          // NVCA_HOST_THREADS=n: helper threads for per-job host work (-1: min(8, cores / 2) - 1; 0: none)
-    bool fb_dense = true;            // NVCA_FB_DENSE=0: a FIND_BIGGEST search on the small-image path re-scans its narrowed grids in a second launch instead of replaying them on the host from the first launch's dense candidates + stage-0 reject bits
-    bool roi = true;                 // NVCA_ROI=0: small images take the large-image path too (plan + four launches per job)
-    bool stage_order = false;        // NVCA_STAGE_ORDER=1 (0, the default: the cascade's own order on every tile -- the cheapest one for a cascade whose stages each reject about half, as trained ones do; a round then may take two stages at once): the tile kernels walk the early stages 1 .. 5 in the cascade's order on every tile (1: in the order the previous tile of the band found cheapest -- cost per window killed; the set of survivors is the same.  A cascade whose stages each reject about half, as trained ones do, keeps its own order either way)
-    int  pair_max = 32;              // NVCA_PAIR_MAX=n (<= 32): windows up to which a round of the tile kernels runs lane = (window, stump) instead of a window per lane
-    int  spec_pairs = 1536;          // NVCA_SPEC_PAIRS=n: with at most 32 windows left a round takes as many stages as stay within n (window, stump) pairs (768 = one step of the workgroup)
-    bool quiet = false;              // NVCA_QUIET: no one-time notes on stderr (a plan that falls back to the row-strip kernel)
-    const char *stamps_out = nullptr;   // NVCA_STAMPS_OUT (diagnostic build only)
+    bool group_zero_copy = true;     // NVCA_GROUP_ZEROCOPY=0: box tables through a copy instead of direct stores to the host buffer (default 1)
+    bool skip_cascade = false;       // NVCA_SKIP_CASCADE: timing experiments on the pre-processing kernels only (default off)
+    bool host_group = false;         // NVCA_HOST_GROUP: cv::groupRectangles on the host (default off)
+    int  band_map = 0;               // NVCA_BAND_MAP=1/2: frame-major band walk (default 0: off)
+    int  band = -1;                  // NVCA_BAND=0/1: force pre-pass + tile kernels / band kernel (default -1: by batch size)
+    bool host_profile = false;       // NVCA_HOST_PROFILE: host-side timing prints (default off)
+    bool sparse_ingest = true;       // NVCA_SPARSE_INGEST=0: whole host frames in shrink-first mode (default 1)
+    bool pyr_off = false;            // NVCA_PYR_OFF: per-level launches for SCALE_IMAGE (default off)
+    int  part_stats = 0;             // NVCA_PART_STATS[=n]: phase timers of part batches with n (8 when n is not given) or more streams (default 0: off)
+    int  ingest_chunk = 8;           // NVCA_INGEST_CHUNK=n: chunk size of host-frame batches, 0 = no chunking (default 8)
+    int  deep_stage = 0;             // NVCA_DEEP_STAGE=s: first stage of k_deep (default 0: the plan's own choice)
+    bool tiles = true;               // NVCA_TILES=0: row-strip kernel instead of the tile kernels (default 1)
+    bool plan_debug = false;         // NVCA_PLAN_DEBUG: per-scale tile sizes on stderr (default off)
+    bool deep_lds = true;            // NVCA_DEEP_LDS_OFF: k_deep without LDS patches (default: with them)
+    bool trk_fold = true;            // NVCA_TRK_FOLD=0: NuboTracker's components through the per-pixel kernels (k_ccl_flatten / _reduce / _collect) instead of the per-tile reduction + fold of tile roots (default 1)
+    int  trk_order = -1;             // NVCA_TRK_ORDER: visiting order of k_ccl_reduce (default -1: decided per frame on the device)
+    int  host_threads = -1;          // NVCA_HOST_THREADS=n: helper threads for per-job host work, 0: none (default -1: min(8, cores / 2) - 1)
+    bool fb_dense = true;            // NVCA_FB_DENSE=0: a FIND_BIGGEST search on the small-image path re-scans its narrowed grids in a second launch instead of replaying them on the host from the first launch's dense candidates + stage-0 reject bits (default 1)
+    bool roi = true;                 // NVCA_ROI=0: small images take the large-image path too (plan + four launches per job) (default 1)
+    bool stage_order = false;        // NVCA_STAGE_ORDER=1: the tile kernels walk the early stages 1 .. 5 in the order the previous tile of the band found cheapest (cost per window killed) instead of the cascade's own; the set of survivors is the same (default 0)
+    int  pair_max = 32;              // NVCA_PAIR_MAX=n (<= 32): windows up to which a round of the tile kernels runs lane = (window, stump) instead of a window per lane (default 32)
+    int  spec_pairs = 1536;          // NVCA_SPEC_PAIRS=n: with at most 32 windows left a round takes as many stages as stay within n (window, stump) pairs, 768 being one step of the workgroup (default 1536)
+    bool quiet = false;              // NVCA_QUIET: no one-time notes on stderr (a plan that falls back to the row-strip kernel) (default off)
+    const char *stamps_out = nullptr;   // NVCA_STAMPS_OUT (diagnostic build only; not an option)
 };
+Switches read_switches();           // the process defaults from the environment (options.cpp); switches() keeps the first reading
+bool option_set(Switches &w, const char *name, int value, bool *replan);      // false: unknown name; *replan: the cached plans depend on it
+bool option_get(const Switches &w, const char *name, int *value);
 const Switches &switches();
 
 // --------------------------------------------------------------------------
@@ -395,7 +398,7 @@ hipError_t take_launch_error(const char **kernel);     // returns and clears the
     } while (0)
 
 // --------------------------------------------------------------------------
-// Kernel launch wrappers (kernels_pre.hip / kernels_cascade.hip)
+// Kernel launch wrappers (kernels_pre.hip / kernels_cascade_*.hip / kernels_group.hip)
 // --------------------------------------------------------------------------
 struct PreGeom {
     int sw, sh, sstride, cn;      // source frame
@@ -500,7 +503,7 @@ struct CascadeArgs {
     int key_sy, key_ss;            // a candidate's key = scale << key_ss | iy << key_sy | ix: the plan sizes the three fields for its own grids (DetectPlan::key_sy / key_ss), so a ladder of hundreds of scales (multi-scale-factor 1 .. 4) fits next to small grids and a 4K grid next to 25 scales
     unsigned long long *hits;      // hits[0] = running count, hits[1..cap] = (slot << 32) | key
     unsigned hit_cap;
-    // general cascades (kernels_cascade.hip)
+    // general cascades (k_gen_stage0 / k_gen_rest)
     const int *tilted;             // tilted integral planes, laid out like sum (null: the cascade has no tilted feature)
     const float *galpha;           // leaf values of every weak classifier, concatenated
     const int *gcls_first;         // first node of weak classifier c
@@ -509,10 +512,20 @@ struct CascadeArgs {
     unsigned long long *dbg;       // diagnostic build only: per-phase s_memtime stamps of the first workgroups (scripts/stamps.py)
 #endif
 };
-// which: 0 = k_stage0, 1 = k_strip, 2 = k_deep, 3 = k_tile, 5 = k_band
+// One launch per kernel; each is a no-op when the plan has no work for its kernel (no tasks, no tiles / bands / strips, no late stage).
+void launch_stage0(hipStream_t st, const CascadeArgs &a, int batch);        // kernels_cascade_gather.hip
+void launch_strip(hipStream_t st, const CascadeArgs &a, int batch);
+// general cascades: variance + stage 0 for every window (reject bits + normaliser), then the remaining stages on the visited
+// stage-0 survivors, window per lane
+void launch_gen_stage0(hipStream_t st, const CascadeArgs &a, int batch);
+void launch_gen_rest(hipStream_t st, const CascadeArgs &a, int batch);
 // lds_grant: the calling context's record of the dynamic LDS already granted to k_tile ([0]) / k_band ([1]); returns a
 // hipError_t (as int) when the grant is refused, 0 otherwise
-int launch_cascade_sc(hipStream_t st, const CascadeArgs &a, int batch, int which, int *lds_grant);
+int launch_tile(hipStream_t st, const CascadeArgs &a, int batch, int *lds_grant);      // kernels_cascade_tile.hip
+int launch_band(hipStream_t st, const CascadeArgs &a, int batch, int *lds_grant);
+void launch_deep(hipStream_t st, const CascadeArgs &a, int batch);          // kernels_cascade_deep.hip
+// groupRectangles per frame on the device; out: [batch][2 + 4*out_cap] ints: count (-1 = host must group), raw count, boxes
+void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, int *out, int out_cap, int batch);     // kernels_group.hip
 // detectMultiScale calls in halves (detect.cpp): many calls share one wait per round
 // ---- view-* outlines (nvca_draw_shapes): one coverage rule for the host rasteriser and the kernel
 #if defined(__HIPCC__)
@@ -609,9 +622,6 @@ void detect_job_free(DetectJob *j);
 const std::vector<nvca_rect> &detect_job_out(const DetectJob *j, int k);
 constexpr int kJobImages = 32;                                    // images of one geometry that a plain / SCALE_IMAGE job can carry
 int detect_job_add_image(DetectJob *j, const void *image);       // one more image for the job's launch set; returns its index k (detect_job_out), -1: full / not possible
-// general cascades: which = 0: variance + stage 0 for every window (reject bits + normaliser), 1: the remaining stages on the
-// visited stage-0 survivors, window per lane
-void launch_generic(hipStream_t st, const CascadeArgs &a, int batch, int which);
 // tilted integral (cv::integral's third plane) of `batch` images / of every pyramid level: one workgroup per image
 void launch_tilted(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g, int *tilted, int batch);
 void launch_pyr_tilted(hipStream_t st, const uint8_t *aux, size_t aux_slot, const PyrLevelDev *levels, int nlev, int nimg,
@@ -644,8 +654,5 @@ void launch_roi(hipStream_t st, const RoiJobDev *jobs, int nsteps, const RoiStep
 void roi_stamps_dump(const char *path);     // diagnostic build: k_roi's phase sums as text
 #endif
 int roi_grant_lds(int bytes);     // dynamic LDS above 64 KiB is granted per function and device (monotonic, process-wide); returns a hipError_t as int
-
-// groupRectangles per frame on the device; out: [batch][2 + 4*out_cap] ints: count (-1 = host must group), raw count, boxes
-void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, int *out, int out_cap, int batch);
 
 } // namespace nvca

@@ -159,7 +159,7 @@ void build_scale_table(const Cascade &c, double factor, ScaleTable &t)
             if (r.x0[q] == r.x0[0] && r.x1[q] == r.x1[0]) r.nrect |= 512 << (2 * (q - 1));
         }
     }
-    // the compact per-lane form of the same records (kernels_cascade.hip, lane_vote): coordinates as byte offsets into u16 maps
+    // the compact per-lane form of the same records (kernels_cascade_tile.hip, lane_vote): coordinates as byte offsets into u16 maps
     t.lhost.assign(t.host.size(), LStumpRec());
     for (size_t i = 0; i < t.host.size(); i++) {
         const TStumpRec &r = t.host[i];

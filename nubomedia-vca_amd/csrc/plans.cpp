@@ -262,10 +262,10 @@ int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, 
         a.stump_based = dp.generic_stumps ? 1 : 0;
         if (dp.generic) {
             // tree weak classifiers / tilted features: stage-0 pre-pass for every window, then the remaining stages on the
-            // visited survivors, window per lane (kernels_cascade.hip, "general cascades")
+            // visited survivors, window per lane (kernels_cascade_gather.hip, "general cascades")
             if (dp.needs_tilted && !a.tilted) { ctx->set_error("internal: tilted integral missing"); return NVCA_ERR_ARG; }
-            { TimedLaunch t(ctx, NVCA_K_STAGE0); launch_generic(ctx->cs(), a, batch, 0); }
-            { TimedLaunch t(ctx, NVCA_K_STRIP); launch_generic(ctx->cs(), a, batch, 1); }
+            { TimedLaunch t(ctx, NVCA_K_STAGE0); launch_gen_stage0(ctx->cs(), a, batch); }
+            { TimedLaunch t(ctx, NVCA_K_STRIP); launch_gen_rest(ctx->cs(), a, batch); }
         } else {
 #ifdef NVCA_STAMPS
         {   // diagnostic build: the stamps of the last band launch are written to $NVCA_STAMPS_OUT when the context synchronises
@@ -278,20 +278,20 @@ int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, 
         // kTilesPerCu: >= 270 bands per slot of a CU); otherwise stage-0 pre-pass + one workgroup per tile.  NVCA_BAND=0/1 forces the choice.
         const int band_env = ctx->sw.band;
         const bool use_band = !dp.bands.empty() && (band_env >= 0 ? band_env != 0 : (long long)dp.bands.size() * batch >= 270 * kTilesPerCu);     // measured crossover at 1080p with two 24-row tiles per CU (540; 68 bands per frame): 4 frames -21 %, 8 frames +5 %, 12 frames +24 %
-        auto launch = [&](int which) {
-            const int e = launch_cascade_sc(ctx->cs(), a, batch, which, ctx->lds_grant);
+        auto launch = [&](int (*fn)(hipStream_t, const CascadeArgs &, int, int *)) {     // k_tile / k_band: dynamic LDS above 64 KiB has to be granted
+            const int e = fn(ctx->cs(), a, batch, ctx->lds_grant);
             if (e) ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e));
             return e;
         };
-        if (!use_band) { TimedLaunch t(ctx, NVCA_K_STAGE0); if (launch(0)) return NVCA_ERR_HIP; }
+        if (!use_band) { TimedLaunch t(ctx, NVCA_K_STAGE0); launch_stage0(ctx->cs(), a, batch); }
         if (use_band) {
-            TimedLaunch t(ctx, NVCA_K_BAND); if (launch(5)) return NVCA_ERR_HIP;
+            TimedLaunch t(ctx, NVCA_K_BAND); if (launch(launch_band)) return NVCA_ERR_HIP;
         } else {
-            { TimedLaunch t(ctx, NVCA_K_TILE); if (launch(3)) return NVCA_ERR_HIP; }
-            { TimedLaunch t(ctx, NVCA_K_STRIP); if (launch(1)) return NVCA_ERR_HIP; }
+            { TimedLaunch t(ctx, NVCA_K_TILE); if (launch(launch_tile)) return NVCA_ERR_HIP; }
+            { TimedLaunch t(ctx, NVCA_K_STRIP); launch_strip(ctx->cs(), a, batch); }
         }
         if (early_done) NVCA_HIP_CHECK(ctx, hipEventRecord(early_done, ctx->cs()));
-        { TimedLaunch t(ctx, NVCA_K_DEEP); if (launch(2)) return NVCA_ERR_HIP; }
+        { TimedLaunch t(ctx, NVCA_K_DEEP); launch_deep(ctx->cs(), a, batch); }
         }
         // the box tables are small (a few KB per frame): the grouping kernel stores them straight into the page-locked host
         // buffer (plain stores, visible to the host once the stream has drained) -- no copy operation behind the last kernel

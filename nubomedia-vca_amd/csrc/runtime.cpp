@@ -180,37 +180,6 @@ int api_catch(nvca_ctx *ctx) noexcept
     return code;
 }
 
-static Switches read_switches()
-{
-    Switches w;
-    auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-    auto set = [](const char *name) { return getenv(name) != nullptr; };
-    w.group_zero_copy = num("NVCA_GROUP_ZEROCOPY", 1) != 0;
-    w.skip_cascade = set("NVCA_SKIP_CASCADE");
-    w.host_group = set("NVCA_HOST_GROUP");
-    w.band_map = num("NVCA_BAND_MAP", 0);
-    w.band = num("NVCA_BAND", -1);
-    w.host_profile = set("NVCA_HOST_PROFILE");
-    w.sparse_ingest = num("NVCA_SPARSE_INGEST", 1) != 0;
-    w.pyr_off = set("NVCA_PYR_OFF");
-    if (set("NVCA_PART_STATS")) { const int n = num("NVCA_PART_STATS", 0); w.part_stats = n > 0 ? n : 8; }
-    w.ingest_chunk = num("NVCA_INGEST_CHUNK", 8);
-    w.stage_order = num("NVCA_STAGE_ORDER", 0) != 0;
-    w.trk_fold = num("NVCA_TRK_FOLD", 1) != 0;
-    w.spec_pairs = std::max(1, num("NVCA_SPEC_PAIRS", 1536));
-    w.pair_max = num("NVCA_PAIR_MAX", 32);
-    w.deep_stage = set("NVCA_DEEP_STAGE") ? std::max(1, num("NVCA_DEEP_STAGE", 0)) : 0;
-    w.tiles = num("NVCA_TILES", 1) != 0;
-    w.plan_debug = set("NVCA_PLAN_DEBUG");
-    w.deep_lds = !set("NVCA_DEEP_LDS_OFF");
-    w.trk_order = num("NVCA_TRK_ORDER", -1);
-    w.host_threads = num("NVCA_HOST_THREADS", -1);
-    w.roi = num("NVCA_ROI", 1) != 0;
-    w.fb_dense = num("NVCA_FB_DENSE", 1) != 0;
-    w.quiet = set("NVCA_QUIET");
-    w.stamps_out = getenv("NVCA_STAMPS_OUT");
-    return w;
-}
 const Switches &switches()
 {
     static const Switches w = read_switches();      // first use: nvca_ctx_create

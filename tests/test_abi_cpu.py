@@ -87,6 +87,27 @@ def test_every_entry_point_in_every_source_has_the_barrier():
     assert seen == set(capi.SYMBOLS), seen ^ set(capi.SYMBOLS)
 
 
+def test_option_names_agree_everywhere():
+    """the option table of csrc/options.cpp, the name list in nubovca.h's comment and the table of DESIGN.md's appendix name the
+    same options in the same order -- that of struct Switches -- and every option's member carries its one-line comment there"""
+    csrc = os.path.join(ROOT, "nubomedia-vca_amd", "csrc")
+    rows = re.findall(r'^\s*(?:flag|num)_opt\("([a-z_]+)", "(NVCA_[A-Z_]+)", &Switches::([a-z_]+),', open(os.path.join(csrc, "options.cpp")).read(), re.M)
+    names = [r[0] for r in rows]
+    assert len(names) == 23 and len(set(names)) == 23, names
+    hdr = open(os.path.join(ROOT, "include", "nubovca.h")).read()
+    comment = hdr[hdr.index("Measurement / bisecting switches"):hdr.index("int  nvca_ctx_set_option")]
+    assert re.findall(r'"([a-z_]+)"', comment) == names
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    appendix = design[design.index("## Appendix: environment switches"):]
+    table = re.findall(r"^\| `([a-z_]+)` \| `(NVCA_[A-Z_]+)[^`]*` \| [^|]+ \| [^|]+ \|$", appendix, re.M)
+    assert [t[0] for t in table] == names and [t[1] for t in table] == [r[1] for r in rows], (table, rows)
+    internal = open(os.path.join(csrc, "nvca_internal.h")).read()
+    struct = internal[internal.index("struct Switches {"):internal.index("Switches read_switches();")]
+    members = re.findall(r"^    (?:bool|int)\s+([a-z_]+) = [^;]+;\s*// (NVCA_[A-Z_]+)\S* *:? *\S.*\(default[^)]*\)", struct, re.M)
+    assert members == [(r[2], r[1]) for r in rows], (members, rows)
+    assert len(re.findall(r"^    (?:bool|int)\s", struct, re.M)) == 23          # no member without an option
+
+
 def _validate(lib, xml):
     if isinstance(xml, str):
         xml = xml.encode()

@@ -175,3 +175,20 @@ def test_host_range_bookkeeping_under_sanitizers():
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([out], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "ranges ok" in r.stdout, (r.stdout, r.stderr[-3000:])
+
+
+def test_option_table_under_sanitizers():
+    """the one table of the context's switches (csrc/options.cpp), row by row: what each environment variable makes of the process
+    default (presence flags, the inverse flag, 0/1 variables, raw and clamped numbers), what option_set stores and option_get returns
+    for -2 .. 5000, that exactly pyr_off / tiles / deep_stage / deep_lds ask for new plans, and that unknown names are refused"""
+    if not os.path.exists(CLANG):
+        pytest.skip("no clang++ with sanitizer runtimes")
+    out = os.path.join(SAN, "build", "options_driver")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    srcs = [os.path.join(SAN, "options_driver.cpp"), os.path.join(ROOT, "nubomedia-vca_amd", "csrc", "options.cpp")]
+    r = subprocess.run([CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                        "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I", os.path.join(ROOT, "include"), "-w"] + srcs + ["-o", out],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([out], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "options ok" in r.stdout, (r.stdout, r.stderr[-3000:])
