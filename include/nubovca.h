@@ -12,7 +12,7 @@
  * Conventions: plain C types only; opaque handles; the caller owns all frame
  * memory; the library owns device state.  Every function returns an int status
  * (NVCA_OK == 0, < 0 error) and never throws: every entry point is a function-try-block
- * (csrc/nvca_internal.h, NVCA_API_CATCH) that turns std::bad_alloc / std::length_error into NVCA_ERR_NOMEM and anything
+ * (csrc/context.h, NVCA_API_CATCH) that turns std::bad_alloc / std::length_error into NVCA_ERR_NOMEM and anything
  * else into NVCA_ERR_INTERNAL -- the reference never lets a frame error out of the element either
  * (FACE/kmsfacedetect.cpp:897 always returns GST_FLOW_OK).  A handle may be used by one
  * thread at a time; distinct contexts may be used concurrently.  There is no
@@ -21,6 +21,7 @@
 #ifndef NUBOVCA_H
 #define NUBOVCA_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus

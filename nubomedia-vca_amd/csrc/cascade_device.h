@@ -2,7 +2,7 @@
 // kernels_cascade_tile.hip, kernels_cascade_deep.hip): the upright stump's vote from the sum plane and the closed form of
 // OpenCV's adaptive x step.  A helper with callers in one file only lives in that file.
 #pragma once
-#include "nvca_internal.h"
+#include "launch.h"
 
 #if defined(__HIPCC__)
 namespace nvca {

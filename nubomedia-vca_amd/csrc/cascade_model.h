@@ -1,0 +1,41 @@
+// cascade_model.h -- a cascade as the loader (cascade_xml.cpp) leaves it: plain C++, no HIP.
+#pragma once
+#include <stdint.h>
+#include <stddef.h>
+#include <string>
+#include <vector>
+#include "../../include/nubovca.h"
+
+namespace nvca {
+
+// --------------------------------------------------------------------------
+// Cascade as loaded from old-format XML (OpenCV CvHaarClassifierCascade).
+// --------------------------------------------------------------------------
+struct HaarNode {
+    int   rect[3][4];   // x,y,w,h ; zero when absent
+    float weight[3];
+    int   nrect;        // 2 or 3 (icvCreateHidHaarClassifierCascade's rect[2] test)
+    float threshold;
+    int   left, right;  // >0 child node index, <=0 -> alpha[-idx]
+    int   tilted;
+};
+struct HaarClassifier { int first_node, nnodes, first_alpha; };
+struct HaarStage { int first_cls, ncls; float threshold; /* as in the XML */ };
+
+struct Cascade {
+    int ow = 0, oh = 0;
+    std::vector<HaarStage> stages;
+    std::vector<HaarClassifier> cls;
+    std::vector<HaarNode> nodes;
+    std::vector<float> alpha;
+    bool stump_based = true;
+    bool has_tilted = false; // some feature reads the tilted integral
+    bool generic() const { return !stump_based || has_tilted; }   // evaluated by the general kernels (kernels_cascade_gather.hip)
+    uint64_t uid = 0;       // identity for plan caching
+    mutable std::vector<unsigned char> stage_rec_cache;   // StageRec[] (plan.cpp, built on first use: the summation-order proof is per cascade)
+};
+
+// returns NVCA_OK or NVCA_ERR_PARSE / NVCA_ERR_UNSUPPORTED; err gets a message
+int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err);
+
+} // namespace nvca

@@ -4,7 +4,8 @@
 // NOSE/kmsnosedetect.cpp:31-32, MOUTH/kmsmouthdetect.cpp:37-38, EAR/kmseardetect.cpp:29-31.
 // Mirrors what OpenCV 2.4's icvReadHaarClassifier stores: numbers are parsed as
 // double and kept as float; a *_val leaf becomes alpha[last++] with child index -last.
-#include "nvca_internal.h"
+#include "cascade_model.h"
+#include <memory>
 #include <cstring>
 #include <cstdlib>
 #include <cmath>

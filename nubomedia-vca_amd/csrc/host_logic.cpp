@@ -280,7 +280,7 @@ void to_global(RectV &v, const nvca_rect &face, int scale)
 
 // ------------------------------------------------------------ image-to-overlay on a host frame
 // kms_face_detect_display_detections_overlay_img (FACE/kmsfacedetect.cpp:427-502) for every box in order; the arithmetic
-// is nvca_internal.h's resize_sample_cn / overlay_pixel, shared with the kernel
+// is pixel_rules.h's resize_sample_cn / overlay_pixel, shared with the kernel
 void overlay_blend_host(uint8_t *frame, int W, int H, int stride, const nvca_rect *boxes, int n, const nvca_overlay &ov)
 {
     if (ov.height_percent == 0 || ov.width_percent == 0) return;           // :436-439

@@ -1,6 +1,8 @@
 // host_logic.h -- sequential host-side pieces (see host_logic.cpp)
 #pragma once
-#include "nvca_internal.h"
+#include <vector>
+#include "../../include/nubovca.h"
+#include "pixel_rules.h"
 
 namespace nvca {
 

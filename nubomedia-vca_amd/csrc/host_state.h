@@ -3,7 +3,7 @@
 // helpers one source calls in another.  plan.cpp, host_logic.cpp, cascade_xml.cpp and work_pool.cpp do not include it: the CPU
 // drivers under tests/ build those with host doubles of their own.
 #pragma once
-#include "nvca_internal.h"
+#include "context.h"
 #include "plan.h"
 #include <chrono>
 #include <climits>
@@ -124,7 +124,7 @@ int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int str
                   double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out);
 int get_resize_plan(nvca_ctx *ctx, int sw, int sh, int dw, int dh, GeomPlan **out);
 
-// ---- host_copy.cpp (caller_h2d / caller_h2d_rows / caller_d2h_rows: nvca_internal.h)
+// ---- host_copy.cpp
 hipStream_t stream_of_id(const nvca_ctx *ctx, int id);       // the stream a bit of HostRangeTable's stream mask stands for
 void ensure_pool(nvca_ctx *ctx);                             // the context's helper threads, created on first use
 int stage_2d(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width_bytes, size_t height, int mem);

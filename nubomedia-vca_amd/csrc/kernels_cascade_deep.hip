@@ -1,7 +1,7 @@
 // kernels_cascade_deep.hip -- k_deep, the late-stage kernel: one workgroup per window that survived the stages before
 // deep_stage, one stump per thread (the long stages have 33..213 stumps); after the first late stage the window's samples
 // are staged in LDS.  Launched only for plans whose tiles cannot hold the late stages' samples (deep_stage < nstages).
-#include "nvca_internal.h"
+#include "launch.h"
 #include "cascade_device.h"
 
 namespace nvca {

@@ -6,7 +6,7 @@
 //  k_gen_stage0, k_gen_rest   the same two steps for general cascades (tree-structured weak classifiers, tilted features)
 // Stump records are geometry-independent tables per (cascade, factor), wave-uniform (scalar loads).  No MFMA: integer rect
 // sums, f32 products, f64 stage sums -- exactly the reference's arithmetic (compiled with -ffp-contract=off).
-#include "nvca_internal.h"
+#include "launch.h"
 #include "cascade_device.h"
 
 namespace nvca {

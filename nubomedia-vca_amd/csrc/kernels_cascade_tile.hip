@@ -6,7 +6,7 @@
 //
 // Launches per batch of frames (the other kernels: kernels_cascade_gather.hip, kernels_cascade_deep.hip, kernels_group.hip):
 //  K5  k_band        (batches with >= 540 bands in flight, plans.cpp) one workgroup per row of tiles of a
-//                    scale, walking it left to right: per tile (<= 32 x 24 windows, a window per thread) the integral
+//                    scale, walking it left to right: per tile (<= 32 x 16 windows, a window per thread) the integral
 //                    samples the windows touch are staged, compacted, in LDS; window variance and
 //                    stage 0 for every window; OpenCV's adaptive x step (ix += result != 0 ? 1 : 2)
 //                    in closed form -- window j is visited iff the run of stage-0 rejects
@@ -23,8 +23,9 @@
 // Stump records are geometry-independent tables per (cascade, factor), wave-uniform in K5/K5a/K5b
 // (scalar loads) and per-lane in K5c.  No MFMA: integer rect sums, f32 products, f64 stage sums --
 // exactly the reference's arithmetic (compiled with -ffp-contract=off).
-#include "nvca_internal.h"
+#include "launch.h"
 #include "cascade_device.h"
+#include <mutex>
 
 namespace nvca {
 
@@ -42,7 +43,7 @@ template <class T> __device__ __forceinline__ T load_const(const T *p)
 }
 
 // ---- K5b: stages 1 .. deep_stage-1 on LDS lattice tiles -------------------------------------
-// A tile is nx x ny (<= 32 x 24) windows of one scale.  Window origins and scaled rectangle corners of a scale
+// A tile is nx x ny (<= 32 x 16) windows of one scale.  Window origins and scaled rectangle corners of a scale
 // fall on a near-lattice, so the tile's windows touch only ~2.7 (n + 20) distinct columns and rows of the sum
 // plane whatever the scale.  Those rows x columns are copied, compacted, into LDS once; every rectangle corner
 // is then two u16 map look-ups (column index, row offset) and one LDS read, instead of a global gather whose 64

@@ -1,0 +1,327 @@
+// kernels_gray.hip -- gfx950 kernels for the colour conversion and the resizes in front of the cascade: cv::resize +
+// cv::cvtColor as the reference calls them (FACE/kmsfacedetect.cpp:805-811), with the histogram of the cv::equalizeHist that
+// follows; the working images of the part detectors and the levels of a CV_HAAR_SCALE_IMAGE pyramid.  All integer;
+// HBM-bound streaming work.
+#include "launch.h"
+#include "pre_device.h"
+
+namespace nvca {
+
+__device__ __forceinline__ int gray_of(int b, int g, int r)
+{   // RGB2Gray<uchar>: B2Y 1868, G2Y 9617, R2Y 4899, shift 14, rounding 1<<13
+    return (b * 1868 + g * 9617 + r * 4899 + 8192) >> 14;
+}
+
+// ---- K1 generic: one output pixel per thread, any resize mode, any alignment.
+// mode 0 identity, 1 bilinear (fixed point, 11-bit coefficients), 2 area 2x2.
+__global__ __launch_bounds__(256) void k_gray_generic(
+    const uint8_t *const *__restrict__ srcs, PreGeom g, int mode,
+    const int *__restrict__ xofs, const short *__restrict__ ialpha,
+    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    uint8_t *__restrict__ gray, unsigned *__restrict__ hist)
+{
+    __shared__ unsigned lh[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6, slot = blockIdx.z;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    const uint8_t *src = srcs[slot];
+    const int cn = g.cn;
+    const int x = blockIdx.x * 256 + tid;
+    uint8_t *grow = gray + (size_t)slot * g.gray_slot;
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= g.h) break;
+        if (x < g.w) {
+            int B, G, R;
+            if (mode == 0) {
+                const uint8_t *s = src + (size_t)y * g.sstride + (size_t)x * cn;
+                B = s[0]; G = s[1]; R = s[2];
+            } else if (mode == 2) {
+                const uint8_t *s0 = src + (size_t)(2 * y) * g.sstride + (size_t)(2 * x) * cn;
+                const uint8_t *s1 = s0 + g.sstride;
+                B = (s0[0] + s0[cn] + s1[0] + s1[cn] + 2) >> 2;
+                G = (s0[1] + s0[cn + 1] + s1[1] + s1[cn + 1] + 2) >> 2;
+                R = (s0[2] + s0[cn + 2] + s1[2] + s1[cn + 2] + 2) >> 2;
+            } else {
+                int sy0 = yofs[y], sy1 = sy0 + 1;
+                sy0 = sy0 >= 0 ? (sy0 < g.sh ? sy0 : g.sh - 1) : 0;
+                sy1 = sy1 >= 0 ? (sy1 < g.sh ? sy1 : g.sh - 1) : 0;
+                const int sx = xofs[x] * cn;
+                const uint8_t *s0 = src + (size_t)sy0 * g.sstride + sx;
+                const uint8_t *s1 = src + (size_t)sy1 * g.sstride + sx;
+                const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
+                int c[3];
+                if (x < xmax) {
+                    const int a0 = ialpha[2 * x], a1 = ialpha[2 * x + 1];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        int h0 = s0[k] * a0 + s0[cn + k] * a1;
+                        int h1 = s1[k] * a0 + s1[cn + k] * a1;
+                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        int h0 = s0[k] * 2048, h1 = s1[k] * 2048;
+                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                    }
+                }
+                B = c[0] & 255; G = c[1] & 255; R = c[2] & 255;
+            }
+            const int v = gray_of(B, G, R);
+            grow[(size_t)y * g.gpitch + x] = (uint8_t)v;
+            if (hist) atomicAdd(&lh[wave][v], 1u);
+        }
+    }
+    if (hist) hist_flush(lh, hist + slot * 256, tid);
+}
+
+// ---- K1 fast path: identity geometry, rows and base 4-byte aligned: 4 pixels per thread.
+template <int CN>
+__global__ __launch_bounds__(256) void k_gray_fast4(
+    const uint8_t *const *__restrict__ srcs, PreGeom g, uint8_t *__restrict__ gray,
+    unsigned *__restrict__ hist)
+{
+    __shared__ unsigned lh[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6, slot = blockIdx.z;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    const uint8_t *src = srcs[slot];
+    const int x4 = (blockIdx.x * 256 + tid) * 4;
+    uint8_t *grow = gray + (size_t)slot * g.gray_slot;
+    if (x4 < g.w) {
+        for (int ry = 0; ry < kGrayRows; ry++) {
+            const int y = blockIdx.y * kGrayRows + ry;
+            if (y >= g.h) break;
+            const unsigned *s = (const unsigned *)(src + (size_t)y * g.sstride + (size_t)x4 * CN);
+            int v[4];
+            if (x4 + 4 <= g.w) {
+                if (CN == 3) {
+                    const unsigned d0 = s[0], d1 = s[1], d2 = s[2];
+                    v[0] = gray_of(d0 & 255, (d0 >> 8) & 255, (d0 >> 16) & 255);
+                    v[1] = gray_of(d0 >> 24, d1 & 255, (d1 >> 8) & 255);
+                    v[2] = gray_of((d1 >> 16) & 255, d1 >> 24, d2 & 255);
+                    v[3] = gray_of((d2 >> 8) & 255, (d2 >> 16) & 255, d2 >> 24);
+                } else {
+                    const uint4 d = *(const uint4 *)s;
+                    v[0] = gray_of(d.x & 255, (d.x >> 8) & 255, (d.x >> 16) & 255);
+                    v[1] = gray_of(d.y & 255, (d.y >> 8) & 255, (d.y >> 16) & 255);
+                    v[2] = gray_of(d.z & 255, (d.z >> 8) & 255, (d.z >> 16) & 255);
+                    v[3] = gray_of(d.w & 255, (d.w >> 8) & 255, (d.w >> 16) & 255);
+                }
+                *(unsigned *)(grow + (size_t)y * g.gpitch + x4) =
+                    (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+                if (hist) {
+                    atomicAdd(&lh[wave][v[0]], 1u); atomicAdd(&lh[wave][v[1]], 1u);
+                    atomicAdd(&lh[wave][v[2]], 1u); atomicAdd(&lh[wave][v[3]], 1u);
+                }
+            } else {
+                const uint8_t *sb = (const uint8_t *)s;
+                for (int k = 0; x4 + k < g.w; k++) {
+                    const int vv = gray_of(sb[k * CN], sb[k * CN + 1], sb[k * CN + 2]);
+                    grow[(size_t)y * g.gpitch + x4 + k] = (uint8_t)vv;
+                    if (hist) atomicAdd(&lh[wave][vv], 1u);
+                }
+            }
+        }
+    }
+    if (hist) hist_flush(lh, hist + slot * 256, tid);
+}
+
+void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, int mode,
+                 const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+                 uint8_t *gray, unsigned *hist, int batch, bool aligned4)
+{
+    const int gy = (g.h + kGrayRows - 1) / kGrayRows;
+    if (mode == 0 && aligned4 && (g.cn == 3 || g.cn == 4)) {
+        dim3 grid((g.w + 1023) / 1024, gy, batch);
+        if (g.cn == 3) NVCA_LAUNCH(k_gray_fast4<3>, grid, dim3(256), 0, st, d_src, g, gray, hist);
+        else           NVCA_LAUNCH(k_gray_fast4<4>, grid, dim3(256), 0, st, d_src, g, gray, hist);
+    } else {
+        dim3 grid((g.w + 255) / 256, gy, batch);
+        NVCA_LAUNCH(k_gray_generic, grid, dim3(256), 0, st, d_src, g, mode, d_xofs, d_ialpha, d_yofs,
+                           d_ibeta, xmax, gray, hist);
+    }
+}
+
+// ---- 8UC1 resize (gray-then-resize order of the part detectors, pyramid levels)
+// one destination sample of cv::resize(INTER_LINEAR) 8UC1 (mode 0: copy, 2: exact 2x area-fast, 1: fixed-point bilinear)
+// `px(row, col)`: the source sample (a gray byte, a gray byte through a LUT, or the gray value of a BGR pixel)
+template <class Px>
+__device__ __forceinline__ int resize1_sample(Px px, int sh, int mode,
+                                              const int *__restrict__ xofs, const short *__restrict__ ialpha,
+                                              const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax, int x, int y)
+{
+    if (mode == 0) return px(y, x);
+    if (mode == 2) return (px(2 * y, 2 * x) + px(2 * y, 2 * x + 1) + px(2 * y + 1, 2 * x) + px(2 * y + 1, 2 * x + 1) + 2) >> 2;
+    int sy0 = yofs[y], sy1 = sy0 + 1;
+    sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
+    sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
+    const int sx = xofs[x];
+    const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
+    int h0, h1;
+    if (x < xmax) {
+        const int a0 = ialpha[2 * x], a1 = ialpha[2 * x + 1];
+        h0 = px(sy0, sx) * a0 + px(sy0, sx + 1) * a1; h1 = px(sy1, sx) * a0 + px(sy1, sx + 1) * a1;
+    } else { h0 = px(sy0, sx) * 2048; h1 = px(sy1, sx) * 2048; }
+    return ((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 255;
+}
+__device__ __forceinline__ int resize1_value(const uint8_t *__restrict__ src, int sh, int sstride, int mode,
+                                             const int *__restrict__ xofs, const short *__restrict__ ialpha,
+                                             const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax, int x, int y)
+{
+    return resize1_sample([&](int r, int c) { return (int)src[(size_t)r * sstride + c]; }, sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+}
+
+__global__ __launch_bounds__(256) void k_resize1(
+    const uint8_t *__restrict__ src, int sw, int sh, int sstride, int mode,
+    const int *__restrict__ xofs, const short *__restrict__ ialpha,
+    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    uint8_t *__restrict__ dst, int dw, int dh, int dstride, unsigned *__restrict__ hist, size_t src_slot, size_t dst_slot)
+{
+    __shared__ unsigned lh[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    src += (size_t)blockIdx.z * src_slot; dst += (size_t)blockIdx.z * dst_slot;      // several images of one geometry
+    if (hist) hist += (size_t)blockIdx.z * 256;
+    const int x = blockIdx.x * 256 + tid;
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= dh) break;
+        if (x < dw) {
+            const int v = resize1_value(src, sh, sstride, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            dst[(size_t)y * dstride + x] = (uint8_t)v;
+            if (hist) atomicAdd(&lh[wave][v], 1u);
+        }
+    }
+    if (hist) hist_flush(lh, hist, tid);
+}
+
+// ---- 8UC3 resize (cv::resize on the BGR frame, FACE/kmsfacedetect.cpp:805, as a stand-alone primitive;
+// the face stream fuses it with BGR2GRAY in k_gray_generic)
+__global__ __launch_bounds__(256) void k_resize3(
+    const uint8_t *__restrict__ src, int sw, int sh, int sstride, int mode,
+    const int *__restrict__ xofs, const short *__restrict__ ialpha,
+    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    uint8_t *__restrict__ dst, int dw, int dh, int dstride)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= dh || x >= dw) continue;
+        uint8_t *d = dst + (size_t)y * dstride + (size_t)x * 3;
+        if (mode == 0) {
+            const uint8_t *s = src + (size_t)y * sstride + (size_t)x * 3;
+            d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
+        } else if (mode == 2) {
+            const uint8_t *s0 = src + (size_t)(2 * y) * sstride + (size_t)(2 * x) * 3, *s1 = s0 + sstride;
+#pragma unroll
+            for (int k = 0; k < 3; k++) d[k] = (uint8_t)((s0[k] + s0[3 + k] + s1[k] + s1[3 + k] + 2) >> 2);
+        } else {
+            int sy0 = yofs[y], sy1 = sy0 + 1;
+            sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
+            sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
+            const int sx = xofs[x] * 3;
+            const uint8_t *s0 = src + (size_t)sy0 * sstride + sx, *s1 = src + (size_t)sy1 * sstride + sx;
+            const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
+            const bool inner = x < xmax;
+            const int a0 = inner ? ialpha[2 * x] : 2048, a1 = inner ? ialpha[2 * x + 1] : 0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const int h0 = s0[k] * a0 + (inner ? s0[3 + k] * a1 : 0), h1 = s1[k] * a0 + (inner ? s1[3 + k] * a1 : 0);
+                d[k] = (uint8_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+            }
+        }
+    }
+}
+void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
+                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
+                    int xmax, uint8_t *dst, int dw, int dh, int dstride)
+{
+    dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, 1);
+    NVCA_LAUNCH(k_resize3, grid, dim3(256), 0, st, src, sw, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax,
+                       dst, dw, dh, dstride);
+}
+
+void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
+                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
+                    int xmax, uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch, size_t src_slot, size_t dst_slot)
+{
+    dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, batch);
+    NVCA_LAUNCH(k_resize1, grid, dim3(256), 0, st, src, sw, sh, sstride, mode, d_xofs, d_ialpha, d_yofs,
+                       d_ibeta, xmax, dst, dw, dh, dstride, hist, src_slot, dst_slot);
+}
+
+// ---- working images of the part detectors, all frames of a batched call in one launch: image z of the launch is
+// resize(gray(frame z)) (BGR = true: the gray value of a source pixel is computed where the resize reads it -- cvtColor then
+// resize, EYE/kmseyedetect.cpp:948-956, NOSE/kmsnosedetect.cpp:836-841 -- without writing the full-size gray image) or
+// resize(lut[gray z]) (the eye detector equalizes the full-size gray image first, EYE :950), plus its histogram.
+template <bool BGR>
+__global__ __launch_bounds__(256) void k_work_resize(
+    const uint8_t *const *__restrict__ srcs, const int *__restrict__ lut_idx, const uint8_t *__restrict__ luts,
+    int sh, int sstride, int mode, const int *__restrict__ xofs, const short *__restrict__ ialpha,
+    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    uint8_t *__restrict__ dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *__restrict__ hist)
+{
+    __shared__ unsigned lh[4][256];
+    __shared__ uint8_t sl[256];
+    const int tid = threadIdx.x, wave = tid >> 6, z = blockIdx.z;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    const uint8_t *__restrict__ src = srcs[z];
+    const bool use_lut = !BGR && lut_idx != nullptr;
+    if (use_lut) sl[tid] = luts[(size_t)lut_idx[z] * 256 + tid];
+    __syncthreads();
+    dst += (size_t)z * dst_slot;
+    const int x = blockIdx.x * 256 + tid;
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= dh) break;
+        if (x < dw) {
+            int v;
+            if (BGR) v = resize1_sample([&](int r, int c) { const uint8_t *p = src + (size_t)r * sstride + (size_t)c * 3; return gray_of(p[0], p[1], p[2]); },
+                                        sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            else if (use_lut) v = resize1_sample([&](int r, int c) { return (int)sl[src[(size_t)r * sstride + c]]; }, sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            else v = resize1_value(src, sh, sstride, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            dst[(size_t)y * dstride + x] = (uint8_t)v;
+            if (hist) atomicAdd(&lh[wave][v], 1u);
+        }
+    }
+    if (hist) hist_flush(lh, hist + (size_t)z * 256, tid);
+}
+void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, const int *d_lut_idx, const uint8_t *d_luts, int sh, int sstride,
+                        int mode, const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch)
+{
+    dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, batch);
+    if (bgr) NVCA_LAUNCH(k_work_resize<true>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax,
+                         dst, dw, dh, dstride, dst_slot, hist);
+    else NVCA_LAUNCH(k_work_resize<false>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax,
+                     dst, dw, dh, dstride, dst_slot, hist);
+}
+
+// ---- CV_HAAR_SCALE_IMAGE pyramids: every level of every image in one launch (k_pyr_integral, kernels_integral.hip, takes them from here)
+__global__ __launch_bounds__(256) void k_pyr_resize(const uint8_t *__restrict__ src, int sw, int sh, int sstride, size_t src_slot,
+                                                    const PyrLevelDev *__restrict__ levels, int nimg,
+                                                    uint8_t *__restrict__ aux, size_t aux_slot)
+{
+    const int lev = blockIdx.z / nimg, img = blockIdx.z - lev * nimg;
+    const PyrLevelDev L = levels[lev];
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x * 256 >= L.szw || blockIdx.y * kGrayRows >= L.szh) return;
+    const uint8_t *s = src + (size_t)img * src_slot;
+    uint8_t *d = aux + (size_t)img * aux_slot + L.gray_off;
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= L.szh) break;
+        if (x < L.szw) d[(size_t)y * L.gpitch + x] = (uint8_t)resize1_value(s, sh, sstride, L.mode, L.xofs, L.ialpha, L.yofs, L.ibeta, L.xmax, x, y);
+    }
+}
+void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,
+                       int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot)
+{
+    dim3 grid((maxw + 255) / 256, (maxh + kGrayRows - 1) / kGrayRows, nlev * nimg);
+    NVCA_LAUNCH(k_pyr_resize, grid, dim3(256), 0, st, src, sw, sh, sstride, src_slot, levels, nimg, aux, aux_slot);
+}
+
+} // namespace nvca

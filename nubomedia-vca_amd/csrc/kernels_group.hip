@@ -1,5 +1,5 @@
 // kernels_group.hip -- k_group: cv::groupRectangles per frame on the candidate list the cascade kernels leave.
-#include "nvca_internal.h"
+#include "launch.h"
 
 namespace nvca {
 

@@ -17,7 +17,9 @@
 // Same arithmetic as the large-image kernels: i32 rectangle sums, f32 products, f64 variance / thresholds / stage sums in
 // OpenCV's order (one lane walks a window's stumps in order; a stage whose partial sums are exact in any order may be split over
 // lanes and summed in LDS), contraction off.  Stump cascades with upright features only.
-#include "nvca_internal.h"
+#include "launch.h"
+#include <stdio.h>
+#include <mutex>
 
 namespace nvca {
 

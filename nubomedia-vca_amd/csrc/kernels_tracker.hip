@@ -15,7 +15,8 @@
 //    k_ccl_reduce: bounding box + first seed per root (atomics once per horizontal run);
 //    k_ccl_collect: roots that own a seed -> component list (host sorts by first seed).
 // All HBM-bound streaming / atomic work; no MFMA.
-#include "nvca_internal.h"
+#include "launch.h"
+#include <stdlib.h>
 
 namespace nvca {
 

@@ -1,0 +1,104 @@
+// launch.h -- what a kernel file sees of the library: the launch macro and the launch_* function of every kernel, over the
+// device records and the pixel rules.  Nothing of the context.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+#include "device_records.h"
+#include "pixel_rules.h"
+
+namespace nvca {
+
+bool launch_events(hipEvent_t *a, hipEvent_t *b);      // event pair for the next launch of the current scope, if any
+// A refused launch (bad configuration, LDS grant missing) is not sticky: the status is read right behind the launch and the
+// FIRST failure of the calling thread is kept, with the kernel's name, until the entry point's next NVCA_LAUNCH_CHECK turns it
+// into NVCA_ERR_HIP -- a kernel that did not run never hands stale buffers to the host logic as if they were results.
+void note_launch(const char *kernel);                  // reads hipGetLastError()
+hipError_t take_launch_error(const char **kernel);     // returns and clears the thread's first recorded failure
+#define NVCA_LAUNCH(kern, grid, block, shmem, st, ...)                                                            \
+    do {                                                                                                          \
+        hipEvent_t ea__, eb__;                                                                                    \
+        if (nvca::launch_events(&ea__, &eb__)) hipExtLaunchKernelGGL(kern, grid, block, shmem, st, ea__, eb__, 0, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kern, grid, block, shmem, st, __VA_ARGS__);                                       \
+        nvca::note_launch(#kern);                                                                                 \
+    } while (0)
+
+// --------------------------------------------------------------------------
+// Kernel launch wrappers (kernels_gray.hip / kernels_equalize.hip / kernels_integral.hip / kernels_cascade_*.hip / kernels_group.hip)
+// --------------------------------------------------------------------------
+// src[b] pointers are passed as a device array of pointers (frames need not be contiguous)
+void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, int mode,
+                 const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+                 uint8_t *gray, unsigned *hist, int batch, bool aligned4);
+void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,
+                       int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot);
+void launch_pyr_integral(hipStream_t st, const uint8_t *aux, size_t aux_slot, const PyrLevelDev *levels, int nlev, int nimg,
+                         int *sum, unsigned *sq32, size_t sum_slot, int P);
+void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
+                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
+                    int xmax, uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0);
+void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
+                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
+                    int xmax, uint8_t *dst, int dw, int dh, int dstride);
+void launch_flip_h(hipStream_t st, const uint8_t *src, int w, int h, int spitch, uint8_t *dst, int dpitch, int batch = 1, size_t src_slot = 0,
+                   size_t dst_slot = 0);
+void launch_hist(hipStream_t st, const uint8_t *gray, int w, int h, int pitch, unsigned *hist);
+void launch_lut(hipStream_t st, unsigned *hist, int total, uint8_t *lut, int batch, int rezero = 0,
+                unsigned long long *zero_a = nullptr, unsigned long long *zero_b = nullptr);
+void launch_apply_lut(hipStream_t st, const uint8_t *src, int w, int h, int spitch, const uint8_t *lut,
+                      uint8_t *dst, int dpitch, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0);
+void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, const int *d_lut_idx, const uint8_t *d_luts, int sh, int sstride,
+                        int mode, const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch);
+void launch_colsum(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g,
+                   unsigned *bandsum, unsigned *bandsq, int batch);
+void launch_bandscan(hipStream_t st, const PreGeom &g, unsigned *bandsum, unsigned *bandsq, int batch);
+void launch_integral(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g,
+                     const unsigned *bandsum, const unsigned *bandsq, int *sum, unsigned long long *sqsum,
+                     int batch);
+
+// integral pair of small images (rows x cols fit 64 KiB of LDS) in one launch, one workgroup per image
+bool small_integral_fits(const PreGeom &g);
+void launch_small_integral(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g, int *sum,
+                           unsigned long long *sqsum, int batch);
+
+// ---- tracker (kernels_tracker.hip)
+// out: [0] = component count, [1] unused, then 6 ints per component: slot, first seed index, x, y, w, h
+// flags: one byte per 256-pixel row segment and slot, set by the pixel pass where the motion history holds anything -- the
+// component kernels leave the other segments alone (a static scene with a few moving objects is mostly such segments)
+// roots: [0] = tile roots listed, [1] = the list overflowed, then one entry (slot * w * h + pixel) per tile root; mode: 0 folded component
+// path, 1 per-pixel component kernels, 2 the latter without the pixel pass (fallback behind an overflow of mode 0's list)
+void launch_tracker(hipStream_t st, const void *d_slots, int batch, int w, int h, bool vec4, int *labels, void *acc,
+                    int *out, int cap, bool run_ccl, uint8_t *flags, int order /* Switches::trk_order */, int *roots, int roots_cap, int mode, int *tiles, int tick);
+
+// One launch per kernel; each is a no-op when the plan has no work for its kernel (no tasks, no tiles / bands / strips, no late stage).
+void launch_stage0(hipStream_t st, const CascadeArgs &a, int batch);        // kernels_cascade_gather.hip
+void launch_strip(hipStream_t st, const CascadeArgs &a, int batch);
+// general cascades: variance + stage 0 for every window (reject bits + normaliser), then the remaining stages on the visited
+// stage-0 survivors, window per lane
+void launch_gen_stage0(hipStream_t st, const CascadeArgs &a, int batch);
+void launch_gen_rest(hipStream_t st, const CascadeArgs &a, int batch);
+// lds_grant: the calling context's record of the dynamic LDS already granted to k_tile ([0]) / k_band ([1]); returns a
+// hipError_t (as int) when the grant is refused, 0 otherwise
+int launch_tile(hipStream_t st, const CascadeArgs &a, int batch, int *lds_grant);      // kernels_cascade_tile.hip
+int launch_band(hipStream_t st, const CascadeArgs &a, int batch, int *lds_grant);
+void launch_deep(hipStream_t st, const CascadeArgs &a, int batch);          // kernels_cascade_deep.hip
+// groupRectangles per frame on the device; out: [batch][2 + 4*out_cap] ints: count (-1 = host must group), raw count, boxes
+void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, int *out, int out_cap, int batch);     // kernels_group.hip
+// ---- image-to-overlay and view-* outlines on a device frame (kernels_draw.hip)
+void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const uint8_t *img, int ih, int istride, int cn,
+                    int mode, const int *xofs, const short *ialpha, const int *yofs, const short *ibeta, int xmax);
+void launch_draw_shapes(hipStream_t st, uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *d_shapes, int n,
+                        int bx0, int by0, int bx1, int by1);
+// tilted integral (cv::integral's third plane) of `batch` images / of every pyramid level: one workgroup per image
+void launch_tilted(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g, int *tilted, int batch);
+void launch_pyr_tilted(hipStream_t st, const uint8_t *aux, size_t aux_slot, const PyrLevelDev *levels, int nlev, int nimg,
+                       int *tilted, size_t sum_slot, int P, int maxw, int maxh);
+// ---- detectMultiScale on a small image in one workgroup (kernels_roi.hip)
+void launch_roi(hipStream_t st, const RoiJobDev *jobs, int nsteps, const RoiStep *steps, const unsigned char *tabs, unsigned long long *hits,
+                unsigned hit_cap, int plane_words, int lds_bytes, unsigned long long *rej);
+#ifdef NVCA_STAMPS
+void roi_stamps_dump(const char *path);     // diagnostic build: k_roi's phase sums as text
+#endif
+int roi_grant_lds(int bytes);     // dynamic LDS above 64 KiB is granted per function and device (monotonic, process-wide); returns a hipError_t as int
+
+} // namespace nvca

@@ -1,7 +1,7 @@
-// options.cpp -- the context's switches (struct Switches, nvca_internal.h): ONE table, a row per switch in the order of the
+// options.cpp -- the context's switches (struct Switches, switches.h): ONE table, a row per switch in the order of the
 // struct, that says how the environment sets its process default and how nvca_ctx_set_option / _get_option reach it.  Pure
 // host logic, no HIP calls.  nubovca.h's option list and DESIGN.md's appendix follow this table (tests/test_abi_cpu.py).
-#include "nvca_internal.h"
+#include "switches.h"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>

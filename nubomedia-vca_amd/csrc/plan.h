@@ -1,6 +1,6 @@
 // plan.h -- per-(cascade, geometry) tables, host copy + device copy.
 #pragma once
-#include "nvca_internal.h"
+#include "context.h"
 
 namespace nvca {
 

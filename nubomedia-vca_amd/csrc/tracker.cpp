@@ -2,7 +2,7 @@
 // gst_nubo_tracker_process (TRK/gstnubotracker.cpp:202-237, 339-421).  Per stream the
 // device keeps the previous gray frame and the motion-history image; every frame runs
 // k_trk_pixel + the connected-component kernels, then __join_objects on the host.
-#include "nvca_internal.h"
+#include "context.h"
 #include "host_logic.h"
 #include <chrono>
 #include <algorithm>

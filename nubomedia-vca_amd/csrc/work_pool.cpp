@@ -1,4 +1,4 @@
-// work_pool.cpp -- a few helper threads for host work that is independent per job (nvca_internal.h: WorkPool).
+// work_pool.cpp -- a few helper threads for host work that is independent per job (work_pool.h).
 // Pure C++ (no HIP): also built under ThreadSanitizer by tests/test_host_sanitizers.py.
 #include <algorithm>
 #include <atomic>
@@ -10,14 +10,9 @@
 #include <new>
 #include <thread>
 #include <vector>
+#include "work_pool.h"
 
 namespace nvca {
-
-struct WorkPool;
-WorkPool *work_pool_create(int threads);
-void work_pool_destroy(WorkPool *p);
-void work_pool_run(WorkPool *p, int n, void (*fn)(void *arg, int i), void *arg);
-int work_pool_threads(const WorkPool *p);
 
 // A run is opened by the calling thread (gen goes odd), worked on by the caller and by whichever helpers get there, and closed
 // (gen goes even) as soon as every index has been handled: the caller never waits for a helper to WAKE, only for the ones that

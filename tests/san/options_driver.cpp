@@ -6,7 +6,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "../../nubomedia-vca_amd/csrc/nvca_internal.h"
+#include "../../nubomedia-vca_amd/csrc/switches.h"
 using nvca::Switches;
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "options_driver: check failed at line %d: %s [%s]\n", __LINE__, #c, what.c_str()); return 1; } } while (0)
 

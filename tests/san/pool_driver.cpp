@@ -4,12 +4,7 @@
 #include <atomic>
 #include <cstdio>
 #include <vector>
-namespace nvca {
-struct WorkPool;
-WorkPool *work_pool_create(int threads);
-void work_pool_destroy(WorkPool *p);
-void work_pool_run(WorkPool *p, int n, void (*fn)(void *arg, int i), void *arg);
-}
+#include "../../nubomedia-vca_amd/csrc/work_pool.h"
 struct Arg { std::vector<std::atomic<int>> *hits; int tag; std::atomic<long long> *sum; };
 int main()
 {

@@ -101,7 +101,7 @@ def test_option_names_agree_everywhere():
     appendix = design[design.index("## Appendix: environment switches"):]
     table = re.findall(r"^\| `([a-z_]+)` \| `(NVCA_[A-Z_]+)[^`]*` \| [^|]+ \| [^|]+ \|$", appendix, re.M)
     assert [t[0] for t in table] == names and [t[1] for t in table] == [r[1] for r in rows], (table, rows)
-    internal = open(os.path.join(csrc, "nvca_internal.h")).read()
+    internal = open(os.path.join(csrc, "switches.h")).read()
     struct = internal[internal.index("struct Switches {"):internal.index("Switches read_switches();")]
     members = re.findall(r"^    (?:bool|int)\s+([a-z_]+) = [^;]+;\s*// (NVCA_[A-Z_]+)\S* *:? *\S.*\(default[^)]*\)", struct, re.M)
     assert members == [(r[2], r[1]) for r in rows], (members, rows)
