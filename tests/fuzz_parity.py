@@ -1,5 +1,5 @@
-"""Randomised parity run: the HIP path against the CPU oracle on random configurations (frame sizes, properties,
-host / device frames, synchronous / per-stream / submit-collect calls, the three detectMultiScale variants with random
+"""Randomised parity run: the HIP path against the CPU oracle on random configurations (frame sizes, properties -- min_neighbors
+0 .. 4: 0 returns the tracked raw candidates --, host / device frames, synchronous / per-stream / submit-collect calls, the three detectMultiScale variants with random
 size limits) for a given number of seconds.  Test tool (lives under tests/ because it loads oracle/).
 Usage: python tests/fuzz_parity.py [seconds] [seed]; tests/test_gpu_fuzz.py runs a short burst of it."""
 import os, sys, time
@@ -25,6 +25,7 @@ part_dev = {n: ctx.load_cascade_xml(x) for n, x in part_xml.items()}
 part_cpu = {n: orc.parse_cascade_xml(x) for n, x in part_xml.items()}
 KINDS = {0: ("righteye", "lefteye"), 1: ("nose", None), 2: ("mouth", None), 3: ("leftear", "rightear")}
 gen_cache = {}
+FACE_CAP = 256          # faces per frame asked of either side (ungrouped streams return dozens)
 
 
 def generic_pair(ow, oh, seed, tilt, tree):
@@ -184,11 +185,19 @@ while time.time() < t_end:
             p = {"width_to_process": int(W // rng.randint(1, 4)), "multi_scale_factor": int(rng.choice([10, 15, 20, 25, 40])),
                  "min_neighbors": int(rng.randint(1, 5)), "process_x_every_4_frames": int(rng.randint(1, 5))}
             props.append(p)
-        gs = [capi.FaceStream(ctx, gc, **p) for p in props]
-        os_ = [orc.FaceStream(oc, **{KW[k]: v for k, v in p.items()}) for p in props]
         mode = int(rng.randint(0, 3))
         frames = [[synth.make_bgr(W, H, int(rng.randint(1 << 30)), "natural", [(int(rng.randint(0, W // 2)), int(rng.randint(0, H // 3)), int(min(W, H) * rng.uniform(0.3, 0.6)))] if rng.rand() < 0.7 else [])
                    for _ in range(ns)] for _ in range(ticks)]
+        # min_neighbors 0 (no grouping: the stream tracks the raw candidates) for about a fifth of the streams, where every raw list
+        # of the stream stays within the 256 faces an oracle stream keeps (ORC_MAX_FACES, oracle/orc_pipe.c); otherwise the drawn 1 .. 4 stays
+        for i, p in enumerate(props):
+            if rng.rand() < 0.2:
+                probe = orc.FaceStream(oc, **{KW[k]: v for k, v in dict(p, min_neighbors=0).items()})
+                if all(len(probe.frame_detect(frames[t][i], cap=1024)) <= FACE_CAP for t in range(ticks)):
+                    p["min_neighbors"] = 0
+                    rounds["face_ungrouped"] = rounds.get("face_ungrouped", 0) + 1
+        gs = [capi.FaceStream(ctx, gc, **p) for p in props]
+        os_ = [orc.FaceStream(oc, **{KW[k]: v for k, v in p.items()}) for p in props]
         keep = []
         def fr(t):
             out = []
@@ -202,17 +211,17 @@ while time.time() < t_end:
             return out
         got = []
         if mode == 0:
-            for t in range(ticks): got.append(ctx.face_batch_process(gs, fr(t)))
+            for t in range(ticks): got.append(ctx.face_batch_process(gs, fr(t), cap=FACE_CAP))
         elif mode == 1:
-            for t in range(ticks): got.append([gs[i].process(frames[t][i]) for i in range(ns)])
+            for t in range(ticks): got.append([gs[i].process(frames[t][i], cap=FACE_CAP) for i in range(ns)])
         else:
             pend = ctx.face_batch_submit(gs, fr(0))
             for t in range(1, ticks):
-                nxt = ctx.face_batch_submit(gs, fr(t)); got.append(ctx.face_batch_collect(pend)); pend = nxt
-            got.append(ctx.face_batch_collect(pend))
+                nxt = ctx.face_batch_submit(gs, fr(t)); got.append(ctx.face_batch_collect(pend, cap=FACE_CAP)); pend = nxt
+            got.append(ctx.face_batch_collect(pend, cap=FACE_CAP))
         for t in range(ticks):
             for i in range(ns):
-                eb, eid = os_[i].process(frames[t][i])
+                eb, eid = os_[i].process(frames[t][i], cap=FACE_CAP)
                 if not (np.array_equal(got[t][i][0], eb) and np.array_equal(got[t][i][1], eid)):
                     print("MISMATCH face", W, H, props[i], "mode", mode, "tick", t, got[t][i], eb, eid); sys.exit(1)
         for s in gs: s.close()

@@ -1,6 +1,7 @@
 // tile_geom_driver.cpp -- test infrastructure (never shipped): builds a detection plan with the product's plan.cpp on the CPU and
 // prints the tile geometry of every scale as JSON lines, for tests/test_tile_geometry_cpu.py (the LDS budget of the tile kernels
-// and the tile sides the plan gives each scale).  Like tests/san/san_driver.cpp it links no HIP library: the few runtime calls
+// and the tile sides the plan gives each scale; "xs" / "ys": the first window column / row of every tile column / row of the scale's
+// grid, for tests/prefix_cascades.py, which sorts raw candidates into tile cells).  Like tests/san/san_driver.cpp it links no HIP library: the few runtime calls
 // of plan.cpp get host doubles, a "device" buffer is a malloc'd block, nothing runs a kernel.
 //
 //   tile_geom_driver <cascade.xml> <cols> <rows> <scaleFactor> <minw> <minh>
@@ -10,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <set>
 #include <sstream>
 
 extern "C" hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) { memcpy(dst, src, n); return hipSuccess; }
@@ -49,14 +51,24 @@ int main(int argc, char **argv)
            dp.tiles.size(), dp.bands.size(), dp.strips.size());
     for (size_t s = 0; s < dp.scales.size(); s++) {
         int side = 0, th = 0, ncol = 0, nrow = 0, bytes = 0;
+        std::set<int> xs, ys;
+        size_t cells = 0;
         for (const TileRec &t : dp.tiles) {
             if (t.scale != (int)s) continue;
+            xs.insert(t.ix0); ys.insert(t.iy0); cells++;
             side = std::max(side, t.nx); th = std::max(th, t.ny);
             ncol = std::max(ncol, t.ncol); nrow = std::max(nrow, t.nrow);
             bytes = std::max(bytes, tile_lds_bytes(t.ncol, t.nrow, t.span_x, t.span_y));
         }
-        printf("{\"scale\": %zu, \"factor\": %.6f, \"windows\": [%d, %d], \"tile\": [%d, %d], \"samples\": [%d, %d], \"bytes\": %d}\n", s,
-               dp.scales[s].factor, dp.scales[s].endX, dp.scales[s].endY, side, th, ncol, nrow, bytes);
+        if (cells != xs.size() * ys.size()) { fprintf(stderr, "scale %zu: %zu tiles are no %zu x %zu grid\n", s, cells, xs.size(), ys.size()); return 1; }
+        printf("{\"scale\": %zu, \"factor\": %.17g, \"window\": [%d, %d], \"windows\": [%d, %d], \"tile\": [%d, %d], \"samples\": [%d, %d], \"bytes\": %d, \"xs\": [", s,
+               dp.scales[s].factor, dp.scales[s].winw, dp.scales[s].winh, dp.scales[s].endX, dp.scales[s].endY, side, th, ncol, nrow, bytes);
+        const char *sep = "";
+        for (int v : xs) { printf("%s%d", sep, v); sep = ", "; }
+        printf("], \"ys\": [");
+        sep = "";
+        for (int v : ys) { printf("%s%d", sep, v); sep = ", "; }
+        printf("]}\n");
     }
     return 0;
 }
