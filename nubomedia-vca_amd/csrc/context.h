@@ -11,6 +11,7 @@
 #include "work_pool.h"
 #include "launch.h"
 #include "host_ranges.h"
+#include "part_stats.h"
 
 namespace nvca {
 
@@ -141,6 +142,7 @@ struct nvca_ctx {
     RoiBuffers &rbuf() { return roi_bufs[roi_set]; }
     size_t roi_first_hint = 0;              // candidates of the recent small-image rounds (+ a quarter): what the launch copies back with itself
     nvca::WorkPool *pool = nullptr; bool pool_tried = false;
+    nvca::PartStats stats;            // NVCA_PART_STATS: this context's phase timers
     std::mutex err_mu;                // set_error may be called from the helper threads
 #ifdef NVCA_STAMPS
     unsigned long long *stamps = nullptr;
@@ -191,7 +193,7 @@ struct DetectJob;
 int make_detect_job(nvca_ctx *ctx, DetectJob &j, const nvca_cascade *casc, const void *gray, int w, int h, int stride, int mem,
                     double sf, int min_neighbors, int flags, int minw, int minh, int maxw, int maxh, bool raw_only);
 int run_detect_jobs(nvca_ctx *ctx, DetectJob *const *jobs, int n, const int *lanes);      // lanes: per job, or null (current lane)
-// ... in two halves: the first round queued and left in flight, then the rest (detect.cpp)
+// ... in two halves: the first round queued and left in flight, then the rest (detect_rounds.cpp)
 struct JobRound;
 JobRound *job_round_new();
 void job_round_free(JobRound *r);

@@ -1,23 +1,15 @@
 // host_state.h -- host-side state and helpers that the library's host sources share (not part of the ABI): the workspace, the
-// cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect.cpp, roi_batch.cpp), and the
-// helpers one source calls in another.  plan.cpp, host_logic.cpp, cascade_xml.cpp and work_pool.cpp do not include it: the CPU
-// drivers under tests/ build those with host doubles of their own.
+// cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect_job.cpp, detect_rounds.cpp,
+// roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, fb_search.cpp, part_stats.cpp, options.cpp,
+// cascade_xml.cpp and work_pool.cpp do not include it: the CPU drivers under tests/ build those without it (fb_search.cpp,
+// part_stats.cpp and options.cpp without any HIP header, the others with host doubles of their own).
 #pragma once
 #include "context.h"
 #include "plan.h"
-#include <chrono>
-#include <climits>
-#include <cmath>
+#include "fb_search.h"
+#include "host_math.h"
 
 namespace nvca {
-
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int cv_round(double v)
-{
-    if (!(v > -2147483648.5 && v < 2147483647.5)) return INT_MIN;   // _mm_cvtsd_si32 on overflow / inf
-    return (int)lrint(v);
-}
-inline double mono_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- runtime.cpp
 bool alloc_log();                                            // NVCA_ALLOC_LOG=1: allocations and host registrations on stderr
@@ -136,45 +128,45 @@ int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n,
                  size_t *off_io = nullptr, const RowCopy *rows = nullptr);
 bool frames_aligned4(const nvca_frame *frames, const int *idx, int n);
 
-// ---- detectMultiScale jobs (detect.cpp) and their small-image batches (roi_batch.cpp)
-struct FbStep { double factor, ystep; int winw, winh; };
+// ---- detectMultiScale jobs (detect_job.cpp, detect_rounds.cpp) and their small-image batches (roi_batch.cpp)
+enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT
+enum JobPhase { kJobNew = 0, kJobFirstQueued = 1, kJobNarrowedQueued = 2, kJobDone = 3 };      // (narrowed: the second set of a FIND_BIGGEST search)
 
 struct DetectJob {
-    // ---- request
-    int kind = 0;                                    // 0: scale-cascade scan, 1: CV_HAAR_SCALE_IMAGE, 2: CV_HAAR_FIND_BIGGEST_OBJECT
-    const nvca_cascade *casc = nullptr;
-    const void *img[kJobImages] = {nullptr}; int nimg = 1;       // plain scan / SCALE_IMAGE: images of one geometry share the launches
-    int cols = 0, rows = 0, stride = 0, mem = 0;
-    double sf = 1.1; int min_neighbors = 0, flags = 0, minw = 0, minh = 0, maxw = 0, maxh = 0;
-    bool raw_only = false;
-    // ---- result
-    std::vector<nvca_rect> out[kJobImages];
-    // ---- progress
-    int phase = 0;                                   // 0: new, 1: first launch set queued, 2: narrowed set queued, 3: done
-    int slots() const { return nimg; }
-    GeomPlan *gp = nullptr;                          // cached plan of the queued set (kept from eviction while queued)
-    std::unique_ptr<DetectPlan> own;                 // FIND_BIGGEST: this call's narrowed plan
-    DetectPlan *dp = nullptr;                        // plan of the queued set (null: nothing was queued)
-    CascadeJob cj; int gthr = 0;
-    // FIND_BIGGEST: the serial loop's state between the two sets
-    std::vector<FbStep> ladder; std::vector<std::vector<nvca_rect>> hits; std::vector<char> have; std::vector<int> ladder_of;
-    std::vector<nvca_rect> all; nvca_rect scanROI{0, 0, 0, 0}; bool narrowed_done = false; size_t fb_i = 0; int cur_minw = 0, cur_minh = 0;
-    int regrown = 0;                                 // launch sets re-run with a larger candidate list (at most one per set)
+    struct Request {
+        JobKind kind = kJobPlain;
+        const nvca_cascade *casc = nullptr;
+        const void *img[kJobImages] = {nullptr}; int nimg = 1;       // plain scan / SCALE_IMAGE: images of one geometry share the launches
+        int cols = 0, rows = 0, stride = 0, mem = 0;
+        double sf = 1.1; int min_neighbors = 0, flags = 0, minw = 0, minh = 0, maxw = 0, maxh = 0;
+        bool raw_only = false;
+    } rq;
+    std::vector<nvca_rect> out[kJobImages];          // the result, per image
+    // progress of the queued launch set
+    struct Queued {
+        JobPhase phase = kJobNew;
+        GeomPlan *gp = nullptr;                          // cached plan of the queued set (kept from eviction while queued)
+        std::unique_ptr<DetectPlan> own;                 // FIND_BIGGEST: this call's narrowed plan
+        DetectPlan *dp = nullptr;                        // plan of the queued set (null: nothing was queued)
+        CascadeJob cj; int gthr = 0;
+        int regrown = 0;                                 // launch sets re-run with a larger candidate list (at most one per set)
+    } q;
+    int slots() const { return rq.nimg; }
+    FbSearch fb;                                     // FIND_BIGGEST: the serial loop between the two sets
     // small-image path (kernels_roi.hip): the job's steps of the queued launch and the candidates that came back
     struct RoiStepInfo { double ystep, out_factor; int winw, winh, ladder; };
-    bool small = false;                              // the job runs on the small-image path (decided at its first round)
-    int roi_prev_phase = 0;                          // its phase before the queued set (a set that overflowed the list is queued again)
-    bool fused = false;                              // the queued set went into the round's k_roi launch
-    std::vector<RoiStepInfo> rinfo;
-    std::vector<unsigned> rkeys[kJobImages];         // per image: step << 26 | iy << 13 | ix, ascending (= OpenCV's serial order)
-    // FIND_BIGGEST on the small-image path, dense first launch (Switches::fb_dense): per step of the queued launch where its stage-0 reject bits
-    // lie in the launch's bitmap (word offset, words per grid row, grid size); per LADDER step what came back -- every window that passes the whole
-    // cascade, visited by the serial walk or not (iy << 13 | ix, ascending), and the reject bits of the step's full grid
-    struct RejInfo { int off, wpr, nx, ny; };
-    bool dense = false;                              // the queued launch was a dense one
-    std::vector<RejInfo> rej_info;                   // [step of the launch]
-    std::vector<std::vector<unsigned>> dense_hits;   // [ladder step]
-    std::vector<const unsigned long long *> rej_bits; std::vector<int> rej_wpr, rej_rows;      // [ladder step]: into the launch's page-locked bitmap (valid until the next launch of its buffer set: the job is advanced before)
+    struct RejInfo { int off, wpr, nx, ny; };        // where a step's stage-0 reject bits lie in the launch's bitmap (word offset, words per grid row, grid size)
+    struct SmallPath {
+        bool small = false;                              // the job runs on the small-image path (decided at its first round)
+        bool fused = false;                              // the queued set went into the round's k_roi launch
+        int roi_prev_phase = 0;                          // its phase before the queued set (a set that overflowed the list is queued again); -1: advanced by a helper thread
+        std::vector<RoiStepInfo> rinfo;                  // [step of the launch]
+        std::vector<unsigned> rkeys[kJobImages];         // per image: step << 26 | iy << 13 | ix, ascending (= OpenCV's serial order)
+        // FIND_BIGGEST with Switches::fb_dense: the queued launch was a dense one (FbSearch: dense first set).  The reject bits it hands to
+        // the search stay in the launch's page-locked bitmap: valid until the next launch of its buffer set, and the job is advanced before
+        bool dense = false;
+        std::vector<RejInfo> rej_info;                   // [step of the launch]
+    } sm;
 };
 
 struct RoiBatch {
@@ -192,13 +184,15 @@ struct RoiBatch {
 
 // ---- roi_batch.cpp
 bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round);
-bool roi_grid(int cols, int rows, double ystep, int winw, int winh, int startX, int endX, int startY, int endY, RoiStep &st);
 int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j);
 int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap);
 int roi_collect(nvca_ctx *ctx, RoiBatch &rb);
 
-// ---- detect.cpp: NVCA_PART_STATS (diagnostic, one context at a time) -- where run_detect_jobs spends the host's time (parts.cpp prints them)
-extern double g_jobs_fine_s[6];        // roi_add_job, roi_launch, roi_collect, helper-thread advance, serial advance, small-path jobs (count)
-extern double g_jobs_enqueue_s, g_jobs_wait_s, g_jobs_advance_s;
+// ---- detect_job.cpp
+// the pyramid levels of a CV_HAAR_SCALE_IMAGE call, smallest factor first, at most `cap` of them
+struct SiLevel { double factor; int szw, szh, winw, winh; };
+std::vector<SiLevel> si_levels(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t cap);
+int detect_job_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total);       // queue the job's next launch set
+int detect_job_advance(nvca_ctx *ctx, DetectJob &j);                          // after the stream has drained: consume what the set produced
 
 } // namespace nvca

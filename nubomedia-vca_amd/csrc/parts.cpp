@@ -317,7 +317,6 @@ int part_images_done(nvca_ctx *ctx, const int *lanes, int n)
 // in flight: each uses the working-image set, candidate buffers and lanes of its ticket's parity).
 namespace {
 struct StreamSnap { nvca_part_stream *s; RectV faces, la, lb; int num_frame, to_process, no_a, no_b; bool popped; RectV front; };
-static double g_total_acc = 0, g_phase3_acc = 0;          // NVCA_PART_STATS (diagnostic, one context at a time)
 static constexpr int kCallLanes = 3;                      // lanes of one call: images on the first, face passes and part searches side by side on all three
 struct PartCall {
     nvca_ctx *ctx = nullptr; int n = 0, parity = 0, seq = 0;
@@ -589,11 +588,12 @@ int part_back(nvca_ctx *ctx, PartCall &c, nvca_rect *out_a, int cap_a, int *n_a,
     int rc = NVCA_OK;
 #define CK(e) do { if ((rc = (e))) return rc; } while (0)
     const bool stats = ctx->sw.part_stats > 0;    // diagnostic: the host's time per phase of calls with n (default 8) or more streams, every 8 such calls
-    static double acc[4] = {0, 0, 0, 0}; static int calls = 0;
+    PartStats &ps = ctx->stats;
     const int stats_min = stats ? ctx->sw.part_stats : 8;
     const bool whole_on = stats && n >= ctx->sw.part_stats;
     const double ts0 = c.t0, ts1 = c.t1, tb0 = stats ? mono_s() : 0;
-    struct Whole { bool on; double t0, front; ~Whole() { if (on) g_total_acc += mono_s() - t0 + front; } } whole{whole_on, tb0, ts1 - ts0};
+    PartStats::Timer whole(whole_on, ps.whole);
+    whole.t0 -= ts1 - ts0;                            // (with the front half's time)
     // Every face pass waits for the images (part_images_done), so draining the passes' lanes drains the image lane's work
     // too.  A call without any face pass (detect-event streams: the faces were pushed) has nobody waiting for it: the H2D
     // copies of the caller's frames and the image kernels are drained here, before the call can return -- the caller may
@@ -665,23 +665,14 @@ int part_back(nvca_ctx *ctx, PartCall &c, nvca_rect *out_a, int cap_a, int *n_a,
     CK(run_detect_jobs(ctx, jobs.data(), (int)jobs.size(), job_lane.data()));          // wait 2 (+ one more for searches that narrowed)
     if (stats) {
         const double ts4 = mono_s();
-        if (n >= stats_min) { acc[0] += ts1 - ts0; acc[1] += ts2 - tb0; acc[2] += ts3 - ts2; acc[3] += ts4 - ts3; }
-        else { g_jobs_enqueue_s = g_jobs_wait_s = g_jobs_advance_s = 0; for (double &v : g_jobs_fine_s) v = 0; }
-        if (n >= stats_min && ++calls % 8 == 0) {
-            fprintf(stderr, "nubovca part batch (ms per call): image chains %.3f, face passes %.3f, roi set-up %.3f, roi searches %.3f | in the job rounds: enqueue %.3f, wait %.3f, advance %.3f | merging (previous calls) %.3f, whole call (previous 8) %.3f\n",
-                    acc[0] / 8 * 1e3, acc[1] / 8 * 1e3, acc[2] / 8 * 1e3, acc[3] / 8 * 1e3, g_jobs_enqueue_s / 8 * 1e3, g_jobs_wait_s / 8 * 1e3, g_jobs_advance_s / 8 * 1e3,
-                    g_phase3_acc / 8 * 1e3, g_total_acc / 8 * 1e3);
-            fprintf(stderr, "nubovca part batch, job rounds in detail (ms per call): adding jobs %.3f (%.0f jobs), launch %.3f, collect %.3f, advance on the helpers %.3f, advance serial %.3f\n",
-                    g_jobs_fine_s[0] / 8 * 1e3, g_jobs_fine_s[5] / 8, g_jobs_fine_s[1] / 8 * 1e3, g_jobs_fine_s[2] / 8 * 1e3, g_jobs_fine_s[3] / 8 * 1e3, g_jobs_fine_s[4] / 8 * 1e3);
-            for (double &v : g_jobs_fine_s) v = 0;
-            acc[0] = acc[1] = acc[2] = acc[3] = 0; g_jobs_enqueue_s = g_jobs_wait_s = g_jobs_advance_s = 0; g_phase3_acc = 0; g_total_acc = 0;
-        }
+        if (n >= stats_min) { ps.chains += ts1 - ts0; ps.face_passes += ts2 - tb0; ps.roi_setup += ts3 - ts2; ps.roi_searches += ts4 - ts3; ps.report(); }
+        else ps.clear_rounds();
     }
 #undef CK
     c.armed = false;                // nothing below can fail short of an exception -- which the containers' strong guarantee
                                            // and the ABI barrier turn into an error code; the device work is complete
     // ---- phase 3: merging heuristics, hysteresis, emission -- in stream order
-    struct P3 { bool on; double t0; ~P3() { if (on) g_phase3_acc += mono_s() - t0; } } p3{whole_on, whole_on ? mono_s() : 0};
+    PartStats::Timer p3(whole_on, ps.merging);
     for (int i = 0; i < n; i++) {
         PartWork &w = work[i];
         nvca_part_stream *s = w.s;

@@ -16,11 +16,11 @@ namespace nvca {
 static constexpr int kRoiMaxWords = 14848;          // (cols + 1) * (rows + 2) words per plane: the part detectors' 160 x 90 face-pass image still fits (two planes + queues + a level image = 157 KB of the 160 KB of LDS)
 bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round)
 {
-    const Cascade &c = j.casc->c;
+    const Cascade &c = j.rq.casc->c;
     if (!ctx->sw.roi) return false;
-    if (!c.stump_based || c.has_tilted || (j.nimg != 1 && j.mem != NVCA_MEM_DEVICE)) return false;
-    if ((long long)(j.cols + 1) * (j.rows + 2) > kRoiMaxWords || j.cols < 1 || j.rows < 1) return false;
-    if (j.mem != NVCA_MEM_DEVICE && njobs_in_round != 1) return false;       // a host image is staged in the lane's one gray buffer
+    if (!c.stump_based || c.has_tilted || (j.rq.nimg != 1 && j.rq.mem != NVCA_MEM_DEVICE)) return false;
+    if ((long long)(j.rq.cols + 1) * (j.rq.rows + 2) > kRoiMaxWords || j.rq.cols < 1 || j.rq.rows < 1) return false;
+    if (j.rq.mem != NVCA_MEM_DEVICE && njobs_in_round != 1) return false;       // a host image is staged in the lane's one gray buffer
     return true;
 }
 static const StageRec *roi_stage_recs(nvca_ctx *ctx, const Cascade &c)
@@ -47,43 +47,28 @@ static void roi_step_common(RoiStep &st, const ScaleTable &t)
     memset(&st, 0, sizeof(st));
     st.trecs = t.dev.as<TStumpRec>(); st.ex = t.ex; st.ey = t.ey; st.ew = t.ew; st.eh = t.eh; st.inv_area = t.inv_area; st.step = 1;
 }
-// scale-cascade grid of one ladder step, limits as indices: false = nothing to scan (fb_make_spec's rules: grid points whose
-// window would leave the image -- cvRunHaarClassifierCascadeSum returns -1 there -- are dropped from the end, a negative origin voids the step)
-bool roi_grid(int cols, int rows, double ystep, int winw, int winh, int startX, int endX, int startY, int endY, RoiStep &st)
-{
-    if (!(endX > startX && endY > startY)) return false;
-    while (endX > startX && cv_round((endX - 1) * ystep) + winw >= cols + 1) endX--;
-    while (endY > startY && cv_round((endY - 1) * ystep) + winh >= rows + 1) endY--;
-    if (!(endX > startX && endY > startY)) return false;
-    if (cv_round(startX * ystep) < 0 || cv_round(startY * ystep) < 0 || endX > 8191 || endY > 8191) return false;
-    st.startX = startX; st.endX = endX; st.startY = startY; st.endY = endY; st.ystep = ystep; st.adaptive = 1;
-    return true;
-}
-// returns NVCA_OK with j.fused set when the job's next set went into the batch, NVCA_OK with j.fused clear when it has to take
+// returns NVCA_OK with j.sm.fused set when the job's next set went into the batch, NVCA_OK with j.sm.fused clear when it has to take
 // the large-image path after all (too many steps), or an error
 int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
 {
-    const Cascade &c = j.casc->c;
-    const int cols = j.cols, rows = j.rows;
-    j.fused = false;
+    const Cascade &c = j.rq.casc->c;
+    const int cols = j.rq.cols, rows = j.rq.rows;
+    j.sm.fused = false;
     const StageRec *d_stages = roi_stage_recs(ctx, c);
     if (!d_stages) return NVCA_ERR_NOMEM;
     std::vector<RoiStep> steps; std::vector<DetectJob::RoiStepInfo> info; std::vector<unsigned char> tabs;
     const size_t tab0 = rb.tabs.size();
     int lev_bytes = 0;
-    const bool dense = j.kind == 2 && j.phase == 0 && ctx->sw.fb_dense && j.nimg == 1;
+    const bool dense = j.rq.kind == kJobBiggest && j.q.phase == kJobNew && ctx->sw.fb_dense && j.rq.nimg == 1;
     std::vector<DetectJob::RejInfo> rej; size_t rej_local = 0;
-    if (j.phase == 0) for (int k = 0; k < kJobImages; k++) j.out[k].clear();
-    if (j.kind == 1) {
-        // the pyramid levels of si_plan, each with its cv::resize tables
+    if (j.q.phase == kJobNew) for (int k = 0; k < kJobImages; k++) j.out[k].clear();
+    if (j.rq.kind == kJobScaleImage) {
+        // the pyramid levels of si_plan, each with its cv::resize tables.  (No cap on their number here: with more of them than the key
+        // holds the job takes the large-image path, below)
         ScaleTable *t1 = nullptr;
-        for (double factor = 1;; factor *= j.sf) {
-            const int winw = cv_round(c.ow * factor), winh = cv_round(c.oh * factor);
-            const int szw = cv_round(cols / factor), szh = cv_round(rows / factor);
-            if (szw - c.ow + 1 <= 0 || szh - c.oh + 1 <= 0) break;
-            if (winw > j.maxw || winh > j.maxh) break;
-            if (winw < j.minw || winh < j.minh) continue;
-            if (szw + 1 <= 1 + c.ow) continue;
+        for (const SiLevel &sl : si_levels(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, (size_t)-1)) {
+            const double factor = sl.factor;
+            const int szw = sl.szw, szh = sl.szh, winw = sl.winw, winh = sl.winh;
             if (!t1 && !(t1 = roi_table(ctx, rb, c, 1.))) return NVCA_ERR_NOMEM;
             RoiStep st; roi_step_common(st, *t1);
             st.szw = szw; st.szh = szh; st.step = factor > 2 ? 1 : 2; st.startX = 0; st.endX = szw - c.ow; st.startY = 0; st.endY = szh - c.oh;
@@ -96,59 +81,41 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
             steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{0., factor, winw, winh, -1});
             lev_bytes = std::max(lev_bytes, szw * szh);
         }
-        j.phase = 1;
-    } else if (j.kind == 0) {
+        j.q.phase = kJobFirstQueued;
+    } else if (j.rq.kind == kJobPlain) {
         std::vector<double> factors;
-        scale_grid(c.ow, c.oh, cols, rows, j.sf, j.minw, j.minh, j.maxw, j.maxh, false, factors);
+        scale_grid(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, false, factors);
         for (double factor : factors) {
             const double ystep = std::max(2., factor);
             ScaleTable *t = roi_table(ctx, rb, c, factor);
             if (!t) return NVCA_ERR_NOMEM;
             RoiStep st; roi_step_common(st, *t);
-            if (!roi_grid(cols, rows, ystep, t->winw, t->winh, 0, cv_round((cols - t->winw) / ystep), 0, cv_round((rows - t->winh) / ystep), st)) continue;
+            ScanGrid sg;
+            if (!full_grid(cols, rows, ystep, t->winw, t->winh, sg) || !roi_grid(sg, ystep, st)) continue;
             steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{ystep, 0., t->winw, t->winh, -1});
         }
-        j.gthr = (!j.raw_only && j.min_neighbors != 0) ? std::max(j.min_neighbors, 1) : 0;
-        j.phase = 1;
+        j.q.gthr = (!j.rq.raw_only && j.rq.min_neighbors != 0) ? std::max(j.rq.min_neighbors, 1) : 0;
+        j.q.phase = kJobFirstQueued;
     } else {
-        if (j.phase == 0) {
-            // the ladder of factors, largest first, exactly as the serial loop walks it (fb_enqueue_first)
-            j.ladder.clear();
-            int n_factors = 0; double factor;
-            for (n_factors = 0, factor = 1; factor * c.ow < cols - 10 && factor * c.oh < rows - 10; n_factors++, factor *= j.sf)
-                ;
-            const double inv = 1. / j.sf; factor *= inv;
-            for (; n_factors-- > 0; factor *= inv) j.ladder.push_back(FbStep{factor, std::max(2., factor), cv_round(c.ow * factor), cv_round(c.oh * factor)});
-            j.hits.assign(j.ladder.size(), {}); j.have.assign(j.ladder.size(), 1);
-            j.all.clear(); j.scanROI = nvca_rect{0, 0, 0, 0}; j.narrowed_done = false; j.fb_i = 0; j.cur_minw = j.minw; j.cur_minh = j.minh;
-            j.ladder_of.clear();
-            for (size_t i = 0; i < j.ladder.size(); i++) {
-                const FbStep &fs = j.ladder[i];
-                if (fs.winw < j.minw || fs.winh < j.minh) break;
-                if (fs.winw > j.maxw || fs.winh > j.maxh) continue;
-                ScaleTable *t = roi_table(ctx, rb, c, fs.factor);
-                if (!t) return NVCA_ERR_NOMEM;
-                RoiStep st; roi_step_common(st, *t);
-                if (!roi_grid(cols, rows, fs.ystep, fs.winw, fs.winh, 0, cv_round((cols - fs.winw) / fs.ystep), 0, cv_round((rows - fs.winh) / fs.ystep), st)) continue;
-                if (dense) {                     // every stage-0 passer of the full grid + the grid's reject bits: a narrowed re-scan is replayed on the host
-                    st.adaptive = 2; st.rej_wpr = (st.endX + 63) / 64; st.rej_off = (int)(rb.rej_words + rej_local);
-                    rej.push_back(DetectJob::RejInfo{st.rej_off, st.rej_wpr, st.endX, st.endY});
-                    rej_local += (size_t)st.rej_wpr * st.endY;
-                }
-                steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{fs.ystep, 0., fs.winw, fs.winh, (int)i}); j.ladder_of.push_back((int)i);
+        // the first set (every step of the call's sizes on its full grid) or the narrowed set the replay asked for: fb.ladder_of on fb.grids
+        if (j.q.phase == kJobNew) {
+            j.fb.start(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh);
+            j.fb.first_set();
+            j.q.phase = kJobFirstQueued;
+        }
+        for (size_t k = 0; k < j.fb.ladder_of.size(); k++) {
+            const int li = j.fb.ladder_of[k];
+            const FbStep &fs = j.fb.ladder[li];
+            ScaleTable *t = roi_table(ctx, rb, c, fs.factor);
+            if (!t) return NVCA_ERR_NOMEM;
+            RoiStep st; roi_step_common(st, *t);
+            if (!roi_grid(j.fb.grids[k], fs.ystep, st)) continue;
+            if (dense) {                     // every stage-0 passer of the full grid + the grid's reject bits: a narrowed re-scan is replayed on the host
+                st.adaptive = 2; st.rej_wpr = (st.endX + 63) / 64; st.rej_off = (int)(rb.rej_words + rej_local);
+                rej.push_back(DetectJob::RejInfo{st.rej_off, st.rej_wpr, st.endX, st.endY});
+                rej_local += (size_t)st.rej_wpr * st.endY;
             }
-            j.phase = 1;
-        } else {
-            // the narrowed set fb_replay asked for: steps fb_i .. on their narrowed grids (j.ladder_of / j.have were set by the replay)
-            for (int li : j.ladder_of) {
-                const FbStep &fs = j.ladder[li];
-                ScaleTable *t = roi_table(ctx, rb, c, fs.factor);
-                if (!t) return NVCA_ERR_NOMEM;
-                RoiStep st; roi_step_common(st, *t);
-                if (!roi_grid(cols, rows, fs.ystep, fs.winw, fs.winh, cv_round(j.scanROI.x / fs.ystep), cv_round((j.scanROI.x + j.scanROI.w - fs.winw) / fs.ystep),
-                              cv_round(j.scanROI.y / fs.ystep), cv_round((j.scanROI.y + j.scanROI.h - fs.winh) / fs.ystep), st)) continue;
-                steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{fs.ystep, 0., fs.winw, fs.winh, li});
-            }
+            steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{fs.ystep, 0., fs.winw, fs.winh, li});
         }
     }
     bool fits = steps.size() <= 63;                                  // the key holds 6 bits of step
@@ -175,25 +142,25 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
         }
         steps.swap(bands);
     }
-    if (!fits && j.roi_prev_phase == 2) { ctx->set_error("internal: a narrowed search outgrew the small-image path"); return NVCA_ERR_INTERNAL; }   // (its full grids fitted)
-    if (!fits) { j.phase = j.roi_prev_phase; return NVCA_OK; }       // this one takes the large-image path
-    j.fused = true; j.rinfo.swap(info); j.dp = nullptr;
-    j.dense = dense && !rej.empty(); j.rej_info.swap(rej);
-    if (j.dense) rb.rej_words += rej_local;
-    for (int k = 0; k < kJobImages; k++) j.rkeys[k].clear();
+    if (!fits && j.sm.roi_prev_phase == kJobNarrowedQueued) { ctx->set_error("internal: a narrowed search outgrew the small-image path"); return NVCA_ERR_INTERNAL; }   // (its full grids fitted)
+    if (!fits) { j.q.phase = (JobPhase)j.sm.roi_prev_phase; return NVCA_OK; }       // this one takes the large-image path
+    j.sm.fused = true; j.sm.rinfo.swap(info); j.q.dp = nullptr;
+    j.sm.dense = dense && !rej.empty(); j.sm.rej_info.swap(rej);
+    if (j.sm.dense) rb.rej_words += rej_local;
+    for (int k = 0; k < kJobImages; k++) j.sm.rkeys[k].clear();
     if (steps.empty()) return NVCA_OK;                               // nothing to scan: the job completes with what it has
     rb.tabs.insert(rb.tabs.end(), tabs.begin(), tabs.end());
-    for (int k = 0; k < j.nimg; k++) {            // every image of the job: its own records (the steps name their image), the same tables
+    for (int k = 0; k < j.rq.nimg; k++) {            // every image of the job: its own records (the steps name their image), the same tables
         RoiJobDev d; memset(&d, 0, sizeof(d));
-        d.w = cols; d.h = rows; d.stride = j.stride; d.img = (const uint8_t *)j.img[k];
-        if (j.mem != NVCA_MEM_DEVICE) {
-            PreGeom g; make_geom(g, cols, rows, j.stride, 1, cols, rows);
+        d.w = cols; d.h = rows; d.stride = j.rq.stride; d.img = (const uint8_t *)j.rq.img[k];
+        if (j.rq.mem != NVCA_MEM_DEVICE) {
+            PreGeom g; make_geom(g, cols, rows, j.rq.stride, 1, cols, rows);
             int rc;
             if ((rc = ensure_ws(ctx, g, 1))) return rc;
-            if ((rc = stage_2d(ctx, ctx->ws->ln().gray.p, g.gpitch, j.img[0], j.stride, cols, rows, j.mem))) return rc;
+            if ((rc = stage_2d(ctx, ctx->ws->ln().gray.p, g.gpitch, j.rq.img[0], j.rq.stride, cols, rows, j.rq.mem))) return rc;
             d.img = ctx->ws->ln().gray.as<uint8_t>(); d.stride = g.gpitch;
         }
-        d.first_step = (int)rb.steps.size(); d.nsteps = (int)steps.size(); d.scale_image = j.kind == 1;
+        d.first_step = (int)rb.steps.size(); d.nsteps = (int)steps.size(); d.scale_image = j.rq.kind == kJobScaleImage;
         d.stages = d_stages; d.nstages = (int)c.stages.size(); d.pair_policy = ctx->policy == NVCA_SUM_F32PAIR; d.slot = (int)rb.jobs.size();
         for (RoiStep &st : steps) st.job = d.slot;
         rb.steps.insert(rb.steps.end(), steps.begin(), steps.end());
@@ -255,26 +222,26 @@ int roi_collect(nvca_ctx *ctx, RoiBatch &rb)
         NVCA_HIP_CHECK(ctx, hipMemcpyAsync(hh + 1 + first, ctx->rbuf().hits.as<unsigned long long>() + 1 + first, (total - first) * 8, hipMemcpyDeviceToHost, ctx->cs()));
         NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
     }
-    // the dense jobs' reject bits: per ladder step of the job (detect.cpp, fb_replay)
+    // the dense jobs' reject bits: per ladder step of the job (FbSearch)
     for (DetectJob *o : rb.owners) {
-        if (!o->dense) continue;
+        if (!o->sm.dense) continue;
         const unsigned long long *hr = ctx->rbuf().h_rej.as<unsigned long long>();
-        o->rej_bits.assign(o->ladder.size(), nullptr); o->rej_wpr.assign(o->ladder.size(), 0); o->rej_rows.assign(o->ladder.size(), 0); o->dense_hits.assign(o->ladder.size(), {});
-        for (size_t k = 0; k < o->rej_info.size() && k < o->rinfo.size(); k++) {
-            const DetectJob::RejInfo &ri = o->rej_info[k];
-            const int li = o->rinfo[k].ladder;
-            if (li < 0 || (size_t)li >= o->ladder.size() || (size_t)ri.off + (size_t)ri.wpr * ri.ny > rb.rej_words) { ctx->set_error("internal: reject bitmap of an unknown ladder step"); return NVCA_ERR_INTERNAL; }
-            o->rej_bits[li] = hr + ri.off; o->rej_wpr[li] = ri.wpr; o->rej_rows[li] = ri.ny;
+        o->fb.dense_begin();
+        for (size_t k = 0; k < o->sm.rej_info.size() && k < o->sm.rinfo.size(); k++) {
+            const DetectJob::RejInfo &ri = o->sm.rej_info[k];
+            const int li = o->sm.rinfo[k].ladder;
+            if (li < 0 || (size_t)li >= o->fb.ladder.size() || (size_t)ri.off + (size_t)ri.wpr * ri.ny > rb.rej_words) { ctx->set_error("internal: reject bitmap of an unknown ladder step"); return NVCA_ERR_INTERNAL; }
+            o->fb.dense_step((size_t)li, hr + ri.off, ri.wpr, ri.ny);
         }
     }
     // (the list is in the order the workgroups appended: every job sorts its own keys into the serial order when it advances)
     for (unsigned long long i = 0; i < total; i++) {
         const unsigned long long slot = hh[1 + i] >> 32;
         const unsigned key = (unsigned)hh[1 + i];
-        if (slot >= (unsigned long long)nj || (key >> 26) >= rb.owners[slot]->rinfo.size()) {
+        if (slot >= (unsigned long long)nj || (key >> 26) >= rb.owners[slot]->sm.rinfo.size()) {
             ctx->set_error("internal: candidate of an unknown job / step (device result rejected)"); return NVCA_ERR_INTERNAL;
         }
-        rb.owners[slot]->rkeys[rb.owner_img[slot]].push_back(key);
+        rb.owners[slot]->sm.rkeys[rb.owner_img[slot]].push_back(key);
     }
     return NVCA_OK;
 }

@@ -1,7 +1,7 @@
 // san_driver.cpp -- test infrastructure (never shipped): runs the product's pure-host sources -- cascade_xml.cpp (the loader),
-// plan.cpp (table builders) and host_logic.cpp (groupRectangles, track_faces, __join_objects, the part detectors' merging
-// heuristics) -- under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  tests/test_host_sanitizers.py builds it
-// (clang++ -fsanitize=address,undefined, the three product sources compiled as they are) and checks what it prints against the
+// plan.cpp (table builders), host_logic.cpp (groupRectangles, track_faces, __join_objects, the part detectors' merging
+// heuristics) and fb_search.cpp (the FIND_BIGGEST search) -- under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  tests/test_host_sanitizers.py builds it
+// (clang++ -fsanitize=address,undefined, the product sources compiled as they are) and checks what it prints against the
 // oracle.  The GPU pool has no sanitizer support (ASan / XNACK are refused there), so this is where memory errors of the host
 // code are looked for.
 //
@@ -9,12 +9,14 @@
 // supplies host doubles for exactly those calls: a "device" buffer is a malloc'd block.  Nothing here runs a kernel.
 #include "../../nubomedia-vca_amd/csrc/plan.h"
 #include "../../nubomedia-vca_amd/csrc/host_logic.h"
+#include "../../nubomedia-vca_amd/csrc/fb_search.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
 #include <set>
+#include <algorithm>
 
 // ---- host doubles of what runtime.cpp / plans.cpp / api.cpp / the HIP runtime provide to these sources -------------------
 extern "C" hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) { memcpy(dst, src, n); return hipSuccess; }
@@ -82,6 +84,238 @@ static int run_loader(int argc, char **argv)
         }
         printf("{\"loader_fuzz\": \"%s\", \"ok\": %d, \"parse\": %d, \"other\": %d}\n", argv[i], statuses[0], statuses[1], statuses[2]);
     }
+    return 0;
+}
+
+// ---- fbsearch ----------------------------------------------------------------------------------------------------------
+// FbSearch (fb_search.cpp) fed the three ways the library feeds it, against a plain serial restatement of the FIND_BIGGEST loop of
+// cvHaarDetectObjectsForROC -- over a synthetic window predicate instead of a cascade.
+struct FbObj { int x, y, w, h; };
+struct FbCase {
+    int ow, oh, cols, rows; double sf; int minw, minh, maxw, maxh, mn; bool rough;
+    unsigned seed; double p_rej0, p_noise; std::vector<FbObj> objs;
+};
+struct FbCounts { int narrowed = 0, narrowed_steps = 0, narrowed_hits = 0, below_min = 0; };
+
+// the window predicate, a deterministic function of (ladder step, ix, iy): 0 = rejected by stage 0, -1 = rejected later, 1 = passes.
+// Around a planted object (origin within 12 % of its size, width 0.85 .. 1.2 of its width) most windows pass and some are rejected
+// by stage 0, so that groups form and a walk that starts at another column sees other windows.
+static int fb_pred(const FbCase &c, int step, int ix, int iy, int x, int y, int winw)
+{
+    unsigned long long h = c.seed * 0x9E3779B97F4A7C15ull + (unsigned long long)step * 0xC2B2AE3D27D4EB4Full + (unsigned long long)ix * 0x165667B19E3779F9ull + (unsigned long long)iy * 0x27D4EB2F165667C5ull;
+    h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32; h *= 0x94D049BB133111EBull; h ^= h >> 29;
+    const double u = (double)(h >> 11) / 9007199254740992.0;
+    for (const FbObj &o : c.objs)
+        if (winw >= 0.85 * o.w && winw <= 1.2 * o.w && abs(x - o.x) <= 0.12 * o.w && abs(y - o.y) <= 0.12 * o.h) return u < 0.70 ? 1 : (u < 0.85 ? 0 : -1);
+    return u < c.p_rej0 ? 0 : (u > 1. - c.p_noise ? 1 : -1);
+}
+
+static int fb_cvr(double v) { return (int)lrint(v); }
+static std::vector<nvca_rect> fb_biggest(std::vector<nvca_rect> &all, int mn)
+{
+    group_rectangles(all, std::max(mn, 1), 0.2);
+    std::vector<nvca_rect> out;
+    if (!all.empty()) {
+        nvca_rect best{0, 0, 0, 0};
+        for (const nvca_rect &r : all) if (r.w * r.h > best.w * best.h) best = r;
+        out.push_back(best);
+    }
+    return out;
+}
+
+// the loop itself, as OpenCV runs it: one step after the other, from the largest factor down
+static std::vector<nvca_rect> fb_serial(const FbCase &c, FbCounts &n, std::vector<nvca_rect> &all)
+{
+    all.clear(); nvca_rect scanROI{0, 0, 0, 0};
+    int minw = c.minw, minh = c.minh, n_factors = 0; double factor = 1;
+    for (; factor * c.ow < c.cols - 10 && factor * c.oh < c.rows - 10; n_factors++, factor *= c.sf)
+        ;
+    const double sf = 1. / c.sf; factor *= sf;
+    for (int step = 0; n_factors-- > 0; factor *= sf, step++) {
+        const double ystep = std::max(2., factor);
+        const int winw = fb_cvr(c.ow * factor), winh = fb_cvr(c.oh * factor);
+        int startX = 0, startY = 0, endX = fb_cvr((c.cols - winw) / ystep), endY = fb_cvr((c.rows - winh) / ystep);
+        if (winw < minw || winh < minh) break;
+        if (winw > c.maxw || winh > c.maxh) continue;
+        const bool narrowed = scanROI.w * scanROI.h > 0;
+        if (narrowed) {
+            startY = fb_cvr(scanROI.y / ystep); endY = fb_cvr((scanROI.y + scanROI.h - winh) / ystep);
+            startX = fb_cvr(scanROI.x / ystep); endX = fb_cvr((scanROI.x + scanROI.w - winw) / ystep);
+        }
+        int windows = 0, found = 0;
+        for (int iy = startY; iy < endY; iy++)
+            for (int ix = startX; ix < endX;) {
+                const int x = fb_cvr(ix * ystep), y = fb_cvr(iy * ystep);
+                int result = -1;                    // cvRunHaarClassifierCascadeSum outside the image
+                if (!(x < 0 || y < 0 || x + winw >= c.cols + 1 || y + winh >= c.rows + 1)) { result = fb_pred(c, step, ix, iy, x, y, winw); windows++; }
+                if (result > 0) { all.push_back(nvca_rect{x, y, winw, winh}); found++; }
+                ix += result != 0 ? 1 : 2;
+            }
+        if (narrowed && windows) { n.narrowed_steps++; n.narrowed_hits += found; if (winw < c.minw || winh < c.minh) n.below_min = 1; }
+        if (!all.empty() && scanROI.w * scanROI.h == 0) {
+            std::vector<nvca_rect> tmp(all);
+            group_rectangles(tmp, std::max(c.mn, 1), 0.2);
+            if (!tmp.empty()) {
+                nvca_rect maxRect{0, 0, 0, 0};
+                for (const nvca_rect &r : tmp) if (r.w * r.h > maxRect.w * maxRect.h) maxRect = r;
+                all.push_back(maxRect);
+                scanROI = maxRect;
+                const int dx = fb_cvr(maxRect.w * 0.2), dy = fb_cvr(maxRect.h * 0.2);
+                scanROI.x = std::max(scanROI.x - dx, 0); scanROI.y = std::max(scanROI.y - dy, 0);
+                scanROI.w = std::min(scanROI.w + dx * 2, c.cols - 1 - scanROI.x);
+                scanROI.h = std::min(scanROI.h + dy * 2, c.rows - 1 - scanROI.y);
+                const double minScale = c.rough ? 0.6 : 0.4;
+                minw = fb_cvr(maxRect.w * minScale); minh = fb_cvr(maxRect.h * minScale);
+                n.narrowed = 1;
+            }
+        }
+    }
+    return fb_biggest(all, c.mn);
+}
+
+// what a launch of the library reports for one grid: the hits of the serial walk of every row (`tag` numbers the scale)
+static void fb_walk(const FbCase &c, const FbStep &st, int li, const ScanGrid &g, int tag, std::vector<nvca_rect> &raw, std::vector<int> &sc)
+{
+    for (int iy = g.startY; iy < g.endY; iy++)
+        for (int ix = g.startX; ix < g.endX;) {
+            const int x = fb_cvr(ix * st.ystep), y = fb_cvr(iy * st.ystep);
+            const int result = fb_pred(c, li, ix, iy, x, y, st.winw);
+            if (result > 0) { raw.push_back(nvca_rect{x, y, st.winw, st.winh}); sc.push_back(tag); }
+            ix += result != 0 ? 1 : 2;
+        }
+}
+
+enum { kFeedPlan, kFeedSmall, kFeedDense };
+static bool fb_fed(const FbCase &c, int feed, std::vector<nvca_rect> &out, std::vector<nvca_rect> &groups, int *second_set)
+{
+    FbSearch fb;
+    struct Groups { FbSearch &fb; std::vector<nvca_rect> &to; ~Groups() { to = fb.all; } } keep{fb, groups};          // (after the last replay: the grouped list)
+    fb.start(c.ow, c.oh, c.cols, c.rows, c.sf, c.minw, c.minh, c.maxw, c.maxh);
+    fb.first_set();
+    const std::vector<int> first = fb.ladder_of; const std::vector<ScanGrid> full = fb.grids;
+    std::vector<std::vector<unsigned long long>> bits(fb.ladder.size());          // (live until the last replay)
+    std::vector<nvca_rect> raw; std::vector<int> sc;
+    if (feed == kFeedDense) {
+        // every passing window of the full grids and the grids' stage-0 reject bits; the full walk's hits are picked from them
+        fb.dense_begin();
+        for (size_t k = 0; k < first.size(); k++) {
+            const int li = first[k];
+            const FbStep &st = fb.ladder[li];
+            const ScanGrid g = full[k];
+            if (g.startX || g.startY) return false;
+            const int wpr = (g.endX + 63) / 64;
+            bits[li].assign((size_t)wpr * g.endY, 0);
+            fb.dense_step(li, bits[li].data(), wpr, g.endY);
+            std::vector<unsigned> pass;
+            for (int iy = 0; iy < g.endY; iy++)
+                for (int ix = 0; ix < g.endX; ix++) {
+                    const int result = fb_pred(c, li, ix, iy, fb_cvr(ix * st.ystep), fb_cvr(iy * st.ystep), st.winw);
+                    if (result == 0) bits[li][(size_t)iy * wpr + (ix >> 6)] |= 1ull << (ix & 63);
+                    if (result > 0) pass.push_back((unsigned)(iy << 13 | ix));
+                }
+            for (unsigned key : pass) {
+                const int iy = (int)(key >> 13), ix = (int)(key & 8191);
+                const int seen = fb.dense_candidate(li, ix, iy);
+                if (seen < 0) return false;
+                if (seen) { raw.push_back(nvca_rect{fb_cvr(ix * st.ystep), fb_cvr(iy * st.ystep), st.winw, st.winh}); sc.push_back(li); }
+            }
+        }
+    } else
+        for (size_t k = 0; k < first.size(); k++) {
+            fb_walk(c, fb.ladder[first[k]], first[k], full[k], feed == kFeedPlan ? (int)k : first[k], raw, sc);
+        }
+    if (!fb.take(raw, sc, feed != kFeedPlan)) return false;
+    *second_set = 0;
+    if (fb.replay(c.mn, c.rough, out)) return true;
+    // the narrowed set it asks for
+    raw.clear(); sc.clear();
+    *second_set = (int)fb.ladder_of.size();
+    for (size_t k = 0; k < fb.ladder_of.size(); k++) {
+        const int li = fb.ladder_of[k];
+        const ScanGrid g = fb.grids[k];
+        if (!(g.endX > g.startX && g.endY > g.startY)) return false;          // (an empty grid is not asked for)
+        if (feed == kFeedDense && std::find(first.begin(), first.end(), li) != first.end()) return false;   // the first set held this step
+        fb_walk(c, fb.ladder[li], li, g, feed == kFeedPlan ? (int)k : li, raw, sc);
+    }
+    if (!fb.take(raw, sc, feed != kFeedPlan)) return false;
+    return fb.replay(c.mn, c.rough, out);          // (false: a third set -- the loop narrows once)
+}
+
+// The clipping rule on its own.  With ystep >= 2 neither formula of cvHaarDetectObjectsForROC puts a window outside the image
+// ((endX - 1) * ystep <= cols - winw - ystep / 2), so no search case reaches it: hand-made grids do
+static int check_clip_grid()
+{
+    ScanGrid g{0, 6, 0, 6};          // origins 0, 2 .. 10, window 10: on a 20 x 19 image x = 10 fits exactly, y = 10 is one too far
+    if (!clip_grid(20, 19, 2., 10, 10, g) || g.endX != 6 || g.endY != 5) return fail("clip_grid: x + winw == cols stays, y + winh == rows + 1 goes");
+    g = ScanGrid{0, 6, 0, 6};
+    if (!clip_grid(19, 20, 2., 10, 10, g) || g.endX != 5 || g.endY != 6) return fail("clip_grid: x + winw == cols + 1 goes, y + winh == rows stays");
+    g = ScanGrid{0, 8, 0, 3};
+    if (!clip_grid(20, 19, 2., 10, 10, g) || g.endX != 6 || g.endY != 3) return fail("clip_grid: dropped from the end only while the window leaves the image");
+    g = ScanGrid{6, 9, 0, 3};
+    if (clip_grid(20, 19, 2., 10, 10, g)) return fail("clip_grid: a grid wholly outside the image has nothing to scan");
+    g = ScanGrid{-2, 3, 0, 3};
+    if (clip_grid(20, 19, 2., 10, 10, g)) return fail("clip_grid: a negative origin voids the grid");
+    g = ScanGrid{3, 3, 0, 3};
+    if (clip_grid(20, 19, 2., 10, 10, g)) return fail("clip_grid: an empty grid");
+    if (!full_grid(20, 19, 2., 10, 10, g) || g.startX || g.startY || g.endX != 5 || g.endY != 4) return fail("full_grid: cvRound((cols - winw) / ystep)");
+    return 0;
+}
+
+static int run_fbsearch()
+{
+    if (check_clip_grid()) return 1;
+    const int kCases = 360;          // the last 120: objects that hug the right / bottom edge, with a smaller one nested in them
+    static const int wins[4][2] = {{20, 20}, {18, 15}, {25, 15}, {24, 24}};
+    static const double sfs[4] = {1.1, 1.2, 1.25, 1.3}, rej0[3] = {0.2, 0.5, 0.8}, noise[3] = {0., 0.001, 0.01};
+    for (int id = 0; id < kCases; id++) {
+        FbCase c;
+        const int wi = rnd_in(0, 3);
+        c.ow = wins[wi][0]; c.oh = wins[wi][1]; c.cols = rnd_in(60, 200); c.rows = rnd_in(50, 160); c.sf = sfs[rnd_in(0, 3)];
+        c.mn = rnd_in(0, 3); c.rough = rnd() & 1; c.seed = rnd(); c.p_rej0 = rej0[rnd_in(0, 2)]; c.p_noise = noise[rnd_in(0, 2)];
+        c.minw = c.minh = 1; c.maxw = c.cols; c.maxh = c.rows;
+        if (rnd_in(0, 2) == 0) { c.minw = rnd_in(c.ow, 2 * c.ow); c.minh = rnd_in(c.oh, 2 * c.oh); }
+        if (rnd_in(0, 3) == 0) { c.maxw = rnd_in(2 * c.ow, c.cols); c.maxh = rnd_in(2 * c.oh, c.rows); }
+        const double fmax = std::min((c.cols - 10.) / c.ow, (c.rows - 10.) / c.oh);
+        int nobj = rnd_in(0, 3);
+        const bool edge = id >= 240;
+        if (edge) nobj = std::max(nobj, 1);
+        else if (id % 8 == 7) { nobj = 0; c.p_noise = 0; }          // nothing to find
+        for (int k = 0; k < nobj && fmax > 1.2; k++) {
+            const double f = 1. + (fmax - 1.) * rnd_in(10, 90) / 100.;
+            FbObj o; o.w = (int)(c.ow * f); o.h = (int)(c.oh * f);
+            o.x = rnd_in(0, std::max(0, c.cols - o.w - 1)); o.y = rnd_in(0, std::max(0, c.rows - o.h - 1));
+            c.objs.push_back(o);
+            if (id % 6 == 5 && k == 0) { c.minw = o.w * rnd_in(50, 80) / 100; c.minh = o.h * rnd_in(50, 80) / 100; c.maxw = c.cols; c.maxh = c.rows; }   // an object above minSize, a narrowed search that goes below it
+        }
+        if (edge && !c.objs.empty()) {
+            // the found box widened by 20 % meets the clamp to cols - 1 / rows - 1; a nested object of 0.42 .. 0.58 of its size sits
+            // astride the lowered minimum size (0.4 / 0.6 of the box found)
+            FbObj &o = c.objs[0];
+            if (id % 3 != 1) o.x = std::max(0, c.cols - o.w - rnd_in(0, 2));
+            if (id % 3 != 2) o.y = std::max(0, c.rows - o.h - rnd_in(0, 2));
+            const int pct = rnd_in(42, 58);
+            FbObj in; in.w = o.w * pct / 100; in.h = o.h * pct / 100; in.x = o.x + rnd_in(0, std::max(0, o.w - in.w)); in.y = o.y + rnd_in(0, std::max(0, o.h - in.h));
+            if (in.w >= c.ow && in.h >= c.oh) c.objs.push_back(in);
+            c.minw = c.minh = 1; c.maxw = c.cols; c.maxh = c.rows;
+        }
+        FbCounts n;
+        std::vector<nvca_rect> want_all, got_all[3];
+        const std::vector<nvca_rect> want = fb_serial(c, n, want_all);
+        std::vector<nvca_rect> got[3]; int second[3] = {0, 0, 0};
+        for (int feed = 0; feed < 3; feed++)
+            if (!fb_fed(c, feed, got[feed], got_all[feed], &second[feed])) { fprintf(stderr, "case %d, feed %d\n", id, feed); return fail("FbSearch refused its input or asked for a set it must not need"); }
+        auto put = [](const char *name, const std::vector<nvca_rect> &v) {
+            printf(", \"%s\": [", name);
+            for (size_t i = 0; i < v.size(); i++) printf("%s[%d, %d, %d, %d]", i ? ", " : "", v[i].x, v[i].y, v[i].w, v[i].h);
+            printf("]");
+        };
+        printf("{\"fbsearch\": %d", id);
+        put("serial", want); put("plan", got[0]); put("small", got[1]); put("dense", got[2]);
+        put("serial_groups", want_all); put("plan_groups", got_all[0]); put("small_groups", got_all[1]); put("dense_groups", got_all[2]);
+        printf(", \"narrowed\": %d, \"narrowed_steps\": %d, \"narrowed_hits\": %d, \"below_min\": %d, \"second_set\": [%d, %d, %d]}\n",
+               n.narrowed, n.narrowed_steps, n.narrowed_hits, n.below_min, second[0], second[1], second[2]);
+    }
+    printf("{\"fbsearch_cases\": %d}\n", kCases);
     return 0;
 }
 
@@ -269,7 +503,8 @@ static int run_glue(const char *cases_path)
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: san_driver loader <xml>... | plans <xml> | glue <cases>\n"); return 2; }
+    if (argc >= 2 && std::string(argv[1]) == "fbsearch") return run_fbsearch();
+    if (argc < 3) { fprintf(stderr, "usage: san_driver loader <xml>... | plans <xml> | glue <cases> | fbsearch\n"); return 2; }
     const std::string mode = argv[1];
     if (mode == "loader") return run_loader(argc - 2, argv + 2);
     if (mode == "plans") return run_plans(argv[2]);

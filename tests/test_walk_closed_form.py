@@ -1,7 +1,7 @@
 """OpenCV's adaptive x step (cvHaarDetectObjectsForROC: `ix += result != 0 ? 1 : 2`, result == 0 = rejected by stage 0) as the closed
 form every evaluator of this repository uses instead of the serial walk -- the band / tile / small-image kernels per 64-window chunk
 with a carried parity, and the host when it replays a FIND_BIGGEST search's narrowed re-scan from the stage-0 reject bits of the full
-grid (detect.cpp, fb_visited): window ix is visited iff the run of stage-0 rejects immediately left of it, not reaching below the walk's
+grid (fb_search.cpp: fb_visited, FbSearch::replay): window ix is visited iff the run of stage-0 rejects immediately left of it, not reaching below the walk's
 start column, has even length.  Checked here against the walk itself on random reject patterns, start columns and row lengths
 (pure Python: the statement the GPU parity tests rely on, separated from any kernel)."""
 import numpy as np
