@@ -63,13 +63,29 @@ typedef struct nvca_tracker nvca_tracker;
 typedef struct nvca_rect { int x, y, w, h; } nvca_rect;
 
 typedef struct nvca_frame {
-    const void *data;     /* packed rows, BGR (3 B/px) or BGRA (4 B/px)              */
-    int width, height;
+    const void *data;     /* packed rows, BGR (3 B/px) or BGRA (4 B/px); frames of a
+                             4:2:0 face stream (nvca_face_stream_set_input): the
+                             buffer base the stream's plane offsets count from      */
+    int width, height;    /* (4:2:0 streams: the luma size)                          */
     int stride;           /* bytes per row; the reference assumes align4(width*bpp),
-                             FACE/kmsfacedetect.cpp:300-305                          */
+                             FACE/kmsfacedetect.cpp:300-305 (4:2:0 streams: the
+                             layout's stride[0])                                    */
     int mem;              /* NVCA_MEM_HOST or NVCA_MEM_DEVICE                        */
     uint64_t pts;
 } nvca_frame;
+
+/* Pixel format of a face stream's frames (a property of the stream, as caps are in GStreamer; the plane table mirrors
+ * GstVideoInfo's offset[] / stride[]).  4:2:0 frames are what decoders emit: a stream that takes them stands for the
+ * videoconvert in front of the element plus the element, cv::cvtColor(CV_YUV2BGR_NV12 / CV_YUV2BGR_I420) in front of
+ * FACE/kmsfacedetect.cpp:805 (SURVEY.md A.13 states the arithmetic). */
+#define NVCA_PIX_BGR  0   /* packed, as nvca_frame describes it */
+#define NVCA_PIX_NV12 1   /* plane 0: Y, w x h; plane 1: U,V interleaved, w bytes x h/2 rows */
+#define NVCA_PIX_I420 2   /* plane 0: Y; plane 1: U, w/2 x h/2; plane 2: V, w/2 x h/2 */
+typedef struct nvca_pixel_layout {
+    int    format;          /* NVCA_PIX_* */
+    size_t offset[3];       /* byte offset of each plane from nvca_frame.data */
+    int    stride[3];       /* bytes per row of each plane */
+} nvca_pixel_layout;
 
 /* ---- context ----------------------------------------------------------- */
 /* HIP devices visible to the process (the GStreamer shim spreads its elements over them, one context per GPU) */
@@ -167,6 +183,12 @@ int nvca_bgr2gray(nvca_ctx *ctx, const void *src, int w, int h, int stride, int 
 /* cv::resize(INTER_LINEAR) FACE/kmsfacedetect.cpp:805 (3 ch), EYE/kmseyedetect.cpp:956,963 (1 ch) */
 int nvca_resize_linear(nvca_ctx *ctx, const void *src, int sw, int sh, int sstride, int channels,
                        int mem, void *dst, int dw, int dh, int dstride);
+/* cv::cvtColor(CV_YUV2BGR_NV12 / CV_YUV2BGR_I420) in front of FACE/kmsfacedetect.cpp:805 (the element's caps ask for BGR, :129-133;
+ * the conversion is the pipeline's videoconvert): BT.601 limited range, integer, SURVEY.md A.13.  base: the buffer the
+ * layout's offsets count from; w x h: the luma size, both even; src and dst are both host or both device memory (mem);
+ * dst_bgr: packed BGR rows dst_stride bytes apart. */
+int nvca_yuv420_to_bgr(nvca_ctx *ctx, const void *base, int w, int h, const nvca_pixel_layout *layout, int mem,
+                       void *dst_bgr, int dst_stride);
 /* cv::equalizeHist FACE/kmsfacedetect.cpp:807 */
 int nvca_equalize_hist(nvca_ctx *ctx, const void *src_gray, int w, int h, int stride, int mem,
                        void *dst_gray, int dst_stride);
@@ -249,6 +271,13 @@ int  nvca_face_stream_create(nvca_ctx *ctx, const nvca_cascade *cascade,
                              const nvca_face_params *params, nvca_face_stream **out);
 void nvca_face_stream_destroy(nvca_face_stream *s);
 int  nvca_face_stream_set_params(nvca_face_stream *s, const nvca_face_params *params);
+/* The pixel format of the stream's frames from the next frame on: NV12 / I420 frames as a decoder produced them, converted
+ * where the first kernel reads them (cv::cvtColor(CV_YUV2BGR_NV12 / _I420) in front of FACE/kmsfacedetect.cpp:805, then the
+ * reference's order: resize on BGR, BGR2GRAY, equalizeHist).  layout == NULL or format NVCA_PIX_BGR: back to packed BGR.
+ * A frame of a 4:2:0 stream is refused with NVCA_ERR_ARG -- before any stream's frame gate advances -- when its width or
+ * height is odd, its stride is not the layout's stride[0], a plane's stride is shorter than its row, or planes overlap;
+ * planes may have gaps between them (1080 rows in a 1088-row allocation).  BGR and 4:2:0 streams mix in one batch. */
+int  nvca_face_stream_set_input(nvca_face_stream *s, const nvca_pixel_layout *layout);
 /* a "motion" custom event arrived (FACE/kmsfacedetect.cpp:680-755): analyse the
  * next NUM_FRAMES_TO_PROCESS (10) frames */
 int  nvca_face_stream_motion_event(nvca_face_stream *s);

@@ -141,6 +141,12 @@ struct PreGeom {
     int nbands;
     size_t src_slot, gray_slot, sum_slot, band_slot;   // strides between batch slots (elements of each plane)
 };
+// planes of a 4:2:0 source frame (nvca_pixel_layout as the kernels read it): fmt 0 = packed BGR (nothing else is used), 1 = NV12
+// (off_u: the U,V plane; off_v unused), 2 = I420.  Offsets count from the frame's base pointer; the luma stride is PreGeom::sstride.
+struct YuvPlanes {
+    int fmt, cstride, vstride, pad;      // chroma stride (NV12: of the interleaved plane; I420: of U), I420's V stride
+    long long off_y, off_u, off_v;
+};
 // one pyramid level of a CV_HAAR_SCALE_IMAGE scan (device copy): all levels are resized / integrated by one launch each
 struct PyrLevelDev {
     int szw, szh, gpitch, mode, xmax, plane_off, pad0, pad1;

@@ -3,6 +3,7 @@
 #include "host_state.h"
 #include "host_logic.h"
 #include <algorithm>
+#include <cstdio>
 #include <new>
 
 using namespace nvca;
@@ -17,6 +18,8 @@ struct nvca_face_stream {
     Faces faces;
     int num_frame = 0, num_iter = 0, frames_with_no_detection = 0, num_frames_to_process = 0;
     int pending_events = 0;
+    nvca_pixel_layout input{};        // format NVCA_PIX_BGR: packed frames; else the planes of its 4:2:0 frames (nvca_face_stream_set_input)
+    const nvca_pixel_layout *yuv() const { return input.format != NVCA_PIX_BGR ? &input : nullptr; }
 };
 
 namespace {
@@ -29,6 +32,13 @@ struct FrameWork {
     int cols = 0, rows = 0, norm_scale = 0;
     std::vector<nvca_rect> det;
 };
+
+bool same_layout(const nvca_pixel_layout &a, const nvca_pixel_layout &b)
+{
+    if (a.format != b.format) return false;
+    for (int p = 0; p < 3; p++) if (a.offset[p] != b.offset[p] || a.stride[p] != b.stride[p]) return false;
+    return true;
+}
 
 // the frame gating of kms_face_detect_process_frame (:794-803, :829-830); independent of detection results
 bool face_gate(nvca_face_stream *s)
@@ -77,6 +87,23 @@ int nvca_face_stream_set_params(nvca_face_stream *s, const nvca_face_params *par
 try {
     if (!s || !params) return NVCA_ERR_ARG;
     s->p = *params;
+    return NVCA_OK;
+}
+NVCA_API_CATCH((s ? s->ctx : nullptr))
+int nvca_face_stream_set_input(nvca_face_stream *s, const nvca_pixel_layout *layout)
+try {
+    if (!s) return NVCA_ERR_ARG;
+    nvca_pixel_layout in{};
+    if (layout && layout->format != NVCA_PIX_BGR) {
+        if (layout->format != NVCA_PIX_NV12 && layout->format != NVCA_PIX_I420) { s->ctx->set_error("pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420"); return NVCA_ERR_ARG; }
+        const int np = layout->format == NVCA_PIX_NV12 ? 2 : 3;
+        in.format = layout->format;
+        for (int p = 0; p < np; p++) {           // what the format does not use stays zero: layouts compare by value
+            if (layout->stride[p] <= 0) { s->ctx->set_error("pixel layout: plane strides must be positive"); return NVCA_ERR_ARG; }
+            in.offset[p] = layout->offset[p]; in.stride[p] = layout->stride[p];
+        }
+    }
+    s->input = in;                               // frames of a batch in flight keep the layout they were submitted with (its plan holds it)
     return NVCA_OK;
 }
 NVCA_API_CATCH((s ? s->ctx : nullptr))
@@ -138,7 +165,12 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
     for (int i = 0; i < n; i++) {
         nvca_face_stream *s = streams[i];
         const nvca_frame &f = frames[i];
-        if (!s || s->ctx != ctx || check_img(ctx, f.data, f.width, f.height, f.stride, 3, f.mem)) return NVCA_ERR_ARG;
+        if (!s || s->ctx != ctx) return NVCA_ERR_ARG;
+        if (const nvca_pixel_layout *yuv = s->yuv()) {
+            if (!f.data || (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+            if (check_yuv_layout(ctx, *yuv, f.width, f.height)) return NVCA_ERR_ARG;
+            if (f.stride != yuv->stride[0]) { ctx->set_error("4:2:0 frame: its stride is not the stride[0] of the stream's layout"); return NVCA_ERR_ARG; }
+        } else if (check_img(ctx, f.data, f.width, f.height, f.stride, 3, f.mem)) return NVCA_ERR_ARG;
         if (s->p.width_to_process <= 0) { ctx->set_error("width-to-process must be > 0"); return NVCA_ERR_ARG; }
     }
     // The gates advance per-stream counters; plans and buffers are resolved after them and may still fail (too many scales,
@@ -175,7 +207,7 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
     {
         ResultBufs &rb = ws.res[ws.cur_res];
         size_t need = 0; int na = 0;
-        for (int i = 0; i < n; i++) if (work[i].analysed) { na++; need += staging_need(frames + i, nullptr, 1); }
+        for (int i = 0; i < n; i++) if (work[i].analysed) { na++; need += staging_need(frames + i, nullptr, 1, streams[i]->yuv()); }
         if (rb.srcptrs.ensure((size_t)std::max(na, 1) * sizeof(void *)) || rb.h_srcptrs.ensure((size_t)std::max(na, 1) * sizeof(void *)) ||
             (need && rb.staging.ensure(need))) { ctx->set_error("allocation failed (frame staging)"); return NVCA_ERR_NOMEM; }
     }
@@ -191,13 +223,13 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
             const nvca_frame &fj = frames[j];
             if (work[j].analysed && !done[j] && sj->cascade == s0->cascade && fj.width == f0.width && fj.height == f0.height &&
                 fj.stride == f0.stride && work[j].cols == work[i].cols && work[j].rows == work[i].rows &&
-                sj->p.scale_factor_pct == s0->p.scale_factor_pct) { idx.push_back(j); done[j] = 1; }
+                sj->p.scale_factor_pct == s0->p.scale_factor_pct && same_layout(sj->input, s0->input)) { idx.push_back(j); done[j] = 1; }
         }
         const int batch = (int)idx.size();
         const int cols = work[i].cols, rows = work[i].rows;
         GeomPlan *gp = nullptr;
         const double sf = 1 + s0->p.scale_factor_pct * 1.0 / 100;      // MULTI_SCALE_FACTOR :142
-        int rc = get_face_plan(ctx, s0->cascade, f0.width, f0.height, f0.stride, 3, cols, rows, sf, cols / 20, rows / 20, 0, 0, &gp);
+        int rc = get_face_plan(ctx, s0->cascade, f0.width, f0.height, f0.stride, s0->yuv() ? 1 : 3, cols, rows, sf, cols / 20, rows / 20, 0, 0, &gp, s0->yuv());
         if (rc) return rc;
         grp.gp = gp; gp->inflight++;
         // Host frames: the batch goes through in chunks -- chunk c+1's H2D copies run on the copy stream while the
@@ -210,13 +242,14 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
         const bool piped = chunk < batch;
         if ((rc = ensure_ws(ctx, gp->g, chunk))) return rc;
 
+        const nvca_pixel_layout *yuv = s0->yuv();
         std::vector<int> &gthr = grp.gthr;
         gthr.resize(batch);
         for (int b = 0; b < batch; b++) { const int mn = streams[idx[b]]->p.min_neighbors; gthr[b] = mn != 0 ? std::max(mn, 1) : 0; }
         std::vector<CascadeJob> &jobs = grp.jobs;
         for (int s0 = 0; s0 < batch; s0 += chunk) {
             const int nc = std::min(chunk, batch - s0);
-            if ((rc = stage_frames(ctx, frames, idx.data() + s0, nc, 3, gbase + s0, piped ? ctx->copy_stream : ctx->cs(), &stage_off, &gp->rowcopy))) return rc;
+            if ((rc = stage_frames(ctx, frames, idx.data() + s0, nc, 3, gbase + s0, piped ? ctx->copy_stream : ctx->cs(), &stage_off, &gp->rowcopy, yuv))) return rc;
             if (piped) {
                 while (ctx->chunk_events.size() <= jobs.size()) {
                     hipEvent_t ev; NVCA_HIP_CHECK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -234,6 +267,13 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
             CascadeJob job; job.r0 = gbase + s0; job.n = nc; job.total = n;
             unsigned long long *z_hits = nullptr, *z_deep = nullptr;
             if ((rc = cascade_counters(ctx, gp->det, job, &z_hits, &z_deep))) return rc;
+            if (yuv) {
+              TimedLaunch t(ctx, NVCA_K_GRAY);                             // cvtColor(YUV2BGR) + cv::resize + cvtColor :805-806 (+ histogram)
+              const bool wide = launch_gray_yuv(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, yuv_planes(yuv), gp->tab.mode, gp->d_xofs.as<int>(),
+                              gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,
+                              ws.ln().gray.as<uint8_t>(), ws.ln().hist.as<unsigned>(), nc, frames_yuv_aligned16(frames, idx.data() + s0, nc, *yuv));
+              if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 gray of %d frame(s) %d x %d -> %d x %d: %s\n", nc, f0.width, f0.height, cols, rows, wide ? "k_gray_yuv16" : "k_gray_yuv_generic");
+            } else
             { TimedLaunch t(ctx, NVCA_K_GRAY);                             // cv::resize + cvtColor :805-806 (+ histogram)
               launch_gray(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, gp->tab.mode, gp->d_xofs.as<int>(),
                           gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,

@@ -201,21 +201,98 @@ int check_img(nvca_ctx *ctx, const void *p, int w, int h, int stride, int bpp, i
     return NVCA_OK;
 }
 
+// ---- 4:2:0 layouts (nvca_pixel_layout): plane p of a w x h frame has yuv_plane_rows() rows of yuv_plane_row_bytes() bytes
+static int yuv_planes_of(const nvca_pixel_layout &l) { return l.format == NVCA_PIX_NV12 ? 2 : 3; }
+static size_t yuv_plane_rows(int p, int h) { return p == 0 ? (size_t)h : (size_t)h / 2; }
+static size_t yuv_plane_row_bytes(const nvca_pixel_layout &l, int p, int w) { return (p == 0 || l.format == NVCA_PIX_NV12) ? (size_t)w : (size_t)w / 2; }
+static size_t yuv_plane_bytes(const nvca_pixel_layout &l, int p, int w, int h)
+{
+    return (size_t)l.stride[p] * (yuv_plane_rows(p, h) - 1) + yuv_plane_row_bytes(l, p, w);
+}
+// bytes from the frame's base to the end of its last plane
+size_t yuv_extent(const nvca_pixel_layout &l, int w, int h)
+{
+    size_t e = 0;
+    for (int p = 0; p < yuv_planes_of(l); p++) e = std::max(e, l.offset[p] + yuv_plane_bytes(l, p, w, h));
+    return e;
+}
+int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h)
+{
+    if (l.format != NVCA_PIX_NV12 && l.format != NVCA_PIX_I420) { ctx->set_error("pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420"); return NVCA_ERR_ARG; }
+    if (w <= 0 || h <= 0) { ctx->set_error("4:2:0 frame: width and height must be positive"); return NVCA_ERR_ARG; }
+    if ((w | h) & 1) { ctx->set_error("4:2:0 frame: width and height must be even (OpenCV's 4:2:0 conversions assert it)"); return NVCA_ERR_ARG; }
+    const int np = yuv_planes_of(l);
+    for (int p = 0; p < np; p++) {
+        if (l.stride[p] <= 0 || (size_t)l.stride[p] < yuv_plane_row_bytes(l, p, w)) { ctx->set_error("4:2:0 frame: a plane's stride is shorter than its row"); return NVCA_ERR_ARG; }
+        if (l.offset[p] > ((size_t)1 << 40)) { ctx->set_error("4:2:0 frame: plane offset out of range"); return NVCA_ERR_ARG; }
+    }
+    for (int p = 0; p < np; p++)
+        for (int q = p + 1; q < np; q++) {
+            const size_t a0 = l.offset[p], a1 = a0 + yuv_plane_bytes(l, p, w, h), b0 = l.offset[q], b1 = b0 + yuv_plane_bytes(l, q, w, h);
+            if (a0 < b1 && b0 < a1) { ctx->set_error("4:2:0 frame: planes overlap"); return NVCA_ERR_ARG; }
+        }
+    return NVCA_OK;
+}
+YuvPlanes yuv_planes(const nvca_pixel_layout *l)
+{
+    YuvPlanes p{};
+    if (!l || l->format == NVCA_PIX_BGR) return p;
+    p.fmt = l->format; p.cstride = l->stride[1]; p.vstride = l->stride[2];
+    p.off_y = (long long)l->offset[0]; p.off_u = (long long)l->offset[1]; p.off_v = (long long)l->offset[2];
+    return p;
+}
+
 // stage `n` source frames (host or device) and return device pointers in ws.srcptrs
-size_t staging_need(const nvca_frame *frames, const int *idx, int n)
+// yuv: the frames are 4:2:0 buffers of this layout (staged with their planes at the caller's offsets)
+size_t staging_need(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout *yuv)
 {
     size_t need = 0;
     for (int i = 0; i < n; i++) {
         const nvca_frame &f = frames[idx ? idx[i] : i];
-        if (f.mem == NVCA_MEM_HOST) need += round_up((size_t)f.stride * f.height, 256);
+        if (f.mem == NVCA_MEM_HOST) need += round_up(yuv ? yuv_extent(*yuv, f.width, f.height) : (size_t)f.stride * f.height, 256);
     }
     return need;
+}
+
+// Rows [first + k * period, + run), k < count, of a host image plane (`rows` rows of `row_bytes` bytes, `stride` apart) to the same
+// places of its staged copy: one strided 2-D copy; a run that ends on the plane's last row is copied without the row padding (the
+// caller's buffer need not extend past the last pixel)
+static int copy_row_runs(nvca_ctx *ctx, uint8_t *d, const uint8_t *s, size_t stride, size_t row_bytes, size_t rows,
+                         size_t first, size_t period, size_t run, size_t count, hipStream_t st)
+{
+    int rc;
+    const size_t pitch = period * stride, start = first * stride;
+    const bool tail = first + (count - 1) * period + run == rows;
+    const size_t full = tail ? count - 1 : count;
+    if (full == 1) { if ((rc = caller_h2d(ctx, d + start, s + start, run * stride, st))) return rc; }       // one run: no pitch to speak of
+    else if (full > 0 && (rc = caller_h2d_rows(ctx, d + start, pitch, s + start, pitch, run * stride, full, st))) return rc;
+    if (tail) {
+        const size_t o = start + full * pitch;
+        if ((rc = caller_h2d(ctx, d + o, s + o, (run - 1) * stride + row_bytes, st))) return rc;
+    }
+    return NVCA_OK;
+}
+// the chroma rows that the luma rows of `rows` use, of one chroma plane: row r uses chroma row r >> 1
+static int copy_chroma_runs(nvca_ctx *ctx, uint8_t *d, const uint8_t *s, size_t stride, size_t row_bytes, size_t plane_rows,
+                            const RowCopy &rows, hipStream_t st)
+{
+    const int c0 = rows.first >> 1, c1 = (rows.first + rows.run - 1) >> 1;
+    if (!(rows.period & 1) || rows.count == 1)              // an even period: the chroma runs are as regular as the luma runs
+        return copy_row_runs(ctx, d, s, stride, row_bytes, plane_rows, (size_t)c0, (size_t)std::max(rows.period / 2, 1), (size_t)(c1 - c0 + 1), (size_t)rows.count, st);
+    int done = -1, rc;                                       // an odd period: run by run, no chroma row twice
+    for (int k = 0; k < rows.count; k++) {
+        const int a = std::max((rows.first + k * rows.period) >> 1, done + 1), b = (rows.first + k * rows.period + rows.run - 1) >> 1;
+        if (b < a) continue;
+        if ((rc = copy_row_runs(ctx, d, s, stride, row_bytes, plane_rows, (size_t)a, 1, (size_t)(b - a + 1), 1, st))) return rc;
+        done = b;
+    }
+    return NVCA_OK;
 }
 
 // frame pointers of n frames -> device pointer array entries [r0, r0 + n); host frames are copied into the staging
 // buffer first (from byte offset *off on, advanced).  `st`: the stream the copies are queued on.
 int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n, int bpp, int r0, hipStream_t st, size_t *off_io,
-                 const RowCopy *rows)
+                 const RowCopy *rows, const nvca_pixel_layout *yuv)
 {
     const bool sparse_off = !ctx->sw.sparse_ingest;
     if (sparse_off || (rows && !rows->on)) rows = nullptr;
@@ -225,7 +302,7 @@ int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n,
         if (ws.res[ws.cur_res].srcptrs.ensure((size_t)(r0 + n) * sizeof(void *)) || ws.res[ws.cur_res].h_srcptrs.ensure((size_t)(r0 + n) * sizeof(void *))) {
             ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM;
         }
-        const size_t need = staging_need(frames, idx, n);
+        const size_t need = staging_need(frames, idx, n, yuv);
         if (need && ws.res[ws.cur_res].staging.ensure(need)) { ctx->set_error("allocation failed (frame staging)"); return NVCA_ERR_NOMEM; }
     }
     const void **hp = ws.res[ws.cur_res].h_srcptrs.as<const void *>() + r0;
@@ -235,17 +312,25 @@ int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n,
         if (f.mem == NVCA_MEM_HOST) {
             uint8_t *d = ws.res[ws.cur_res].staging.as<uint8_t>() + off;
             int rc;
-            if (rows) {
-                // only the rows the resize reads; a run that ends on the frame's last row is copied without the row padding
-                // (the caller's buffer need not extend past the last pixel)
-                const size_t pitch = (size_t)rows->period * f.stride, start = (size_t)rows->first * f.stride;
-                const bool tail = rows->first + (rows->count - 1) * rows->period + rows->run == f.height;
-                const int full = tail ? rows->count - 1 : rows->count;
-                if (full > 0 && (rc = caller_h2d_rows(ctx, d + start, pitch, (const uint8_t *)f.data + start, pitch, (size_t)rows->run * f.stride, (size_t)full, st))) return rc;
-                if (tail) {
-                    const size_t o = start + (size_t)full * pitch;
-                    if ((rc = caller_h2d(ctx, d + o, (const uint8_t *)f.data + o, (size_t)(rows->run - 1) * f.stride + (size_t)f.width * bpp, st))) return rc;
+            if (yuv) {
+                // plane by plane, each at the caller's offset: the luma rows the resize reads and exactly the chroma rows those use
+                for (int p = 0; p < yuv_planes_of(*yuv); p++) {
+                    uint8_t *dp = d + yuv->offset[p];
+                    const uint8_t *sp = (const uint8_t *)f.data + yuv->offset[p];
+                    const size_t stride = (size_t)yuv->stride[p], rb = yuv_plane_row_bytes(*yuv, p, f.width), pr = yuv_plane_rows(p, f.height);
+                    if (!rows) rc = caller_h2d(ctx, dp, sp, yuv_plane_bytes(*yuv, p, f.width, f.height), st);
+                    else if (p == 0) rc = copy_row_runs(ctx, dp, sp, stride, rb, pr, (size_t)rows->first, (size_t)rows->period, (size_t)rows->run, (size_t)rows->count, st);
+                    else rc = copy_chroma_runs(ctx, dp, sp, stride, rb, pr, *rows, st);
+                    if (rc) return rc;
                 }
+                hp[i] = d;
+                off += round_up(yuv_extent(*yuv, f.width, f.height), 256);
+                continue;
+            }
+            if (rows) {
+                // only the rows the resize reads
+                if ((rc = copy_row_runs(ctx, d, (const uint8_t *)f.data, (size_t)f.stride, (size_t)f.width * bpp, (size_t)f.height,
+                                        (size_t)rows->first, (size_t)rows->period, (size_t)rows->run, (size_t)rows->count, st))) return rc;
             } else if ((rc = caller_h2d(ctx, d, f.data, (size_t)f.stride * (f.height - 1) + (size_t)f.width * bpp, st))) return rc;
             hp[i] = d;
             off += round_up((size_t)f.stride * f.height, 256);
@@ -262,6 +347,20 @@ bool frames_aligned4(const nvca_frame *frames, const int *idx, int n)
     for (int i = 0; i < n; i++) {
         const nvca_frame &f = frames[idx ? idx[i] : i];
         if ((f.stride & 3) || (f.mem == NVCA_MEM_DEVICE && ((uintptr_t)f.data & 15))) return false;
+    }
+    return true;
+}
+
+// 4:2:0 frames of one layout: every plane and stride takes k_gray_yuv16's loads (staged host frames start on 256 bytes)
+bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l)
+{
+    const bool nv12 = l.format == NVCA_PIX_NV12;
+    const size_t cmask = nv12 ? 15 : 7;
+    if ((l.offset[0] & 15) || (l.stride[0] & 15) || (l.offset[1] & cmask) || ((size_t)l.stride[1] & cmask)) return false;
+    if (!nv12 && ((l.offset[2] & 7) || (l.stride[2] & 7))) return false;
+    for (int i = 0; i < n; i++) {
+        const nvca_frame &f = frames[idx ? idx[i] : i];
+        if (f.mem == NVCA_MEM_DEVICE && ((uintptr_t)f.data & 15)) return false;
     }
     return true;
 }

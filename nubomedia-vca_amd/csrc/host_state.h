@@ -113,7 +113,7 @@ void group_all(std::vector<std::vector<nvca_rect>> &raw, int min_neighbors);
 GeomPlan *find_plan(nvca_ctx *ctx, const std::string &key);
 GeomPlan *store_plan(nvca_ctx *ctx, const std::string &key, std::unique_ptr<GeomPlan> gp);
 int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int stride, int cn, int cols, int rows,
-                  double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out);
+                  double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out, const nvca_pixel_layout *yuv = nullptr);
 int get_resize_plan(nvca_ctx *ctx, int sw, int sh, int dw, int dh, GeomPlan **out);
 
 // ---- host_copy.cpp
@@ -123,10 +123,16 @@ int stage_2d(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t sp
 int unstage_2d(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width_bytes, size_t height, int mem);
 int finish_device_op(nvca_ctx *ctx);
 int check_img(nvca_ctx *ctx, const void *p, int w, int h, int stride, int bpp, int mem);
-size_t staging_need(const nvca_frame *frames, const int *idx, int n);
+// 4:2:0 frames (nvca_pixel_layout): a w x h frame against its layout (NVCA_ERR_ARG with an error text), the bytes from its base to
+// the end of its last plane, and the layout as the kernels read it (null / BGR: fmt 0)
+int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h);
+size_t yuv_extent(const nvca_pixel_layout &l, int w, int h);
+YuvPlanes yuv_planes(const nvca_pixel_layout *l);
+size_t staging_need(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout *yuv = nullptr);
 int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n, int bpp, int r0 = 0, hipStream_t st = nullptr,
-                 size_t *off_io = nullptr, const RowCopy *rows = nullptr);
+                 size_t *off_io = nullptr, const RowCopy *rows = nullptr, const nvca_pixel_layout *yuv = nullptr);
 bool frames_aligned4(const nvca_frame *frames, const int *idx, int n);
+bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l);
 
 // ---- detectMultiScale jobs (detect_job.cpp, detect_rounds.cpp) and their small-image batches (roi_batch.cpp)
 enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT

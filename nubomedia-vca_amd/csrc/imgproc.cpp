@@ -44,6 +44,31 @@ try {
 }
 NVCA_API_CATCH(ctx)
 
+int nvca_yuv420_to_bgr(nvca_ctx *ctx, const void *base, int w, int h, const nvca_pixel_layout *layout, int mem, void *dst, int dst_stride)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    if (!base || !layout || !dst || (mem != NVCA_MEM_HOST && mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+    int rc = check_yuv_layout(ctx, *layout, w, h);
+    if (rc) return rc;
+    if (dst_stride < w * 3) return NVCA_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    const YuvPlanes planes = yuv_planes(layout);
+    if (mem == NVCA_MEM_DEVICE) {          // read and written where they are (ordered on the context's stream)
+        { TimedLaunch t(ctx, NVCA_K_GRAY);
+          launch_yuv420_to_bgr(ctx->cs(), (const uint8_t *)base, w, h, layout->stride[0], planes, (uint8_t *)dst, dst_stride); }
+        return finish_device_op(ctx);
+    }
+    Workspace &ws = *ctx->ws;
+    const size_t dp = round_up((size_t)w * 3, 64);
+    if (ws.ln().aux.ensure(dp * h + 64)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+    nvca_frame f{base, w, h, layout->stride[0], mem, 0};
+    if ((rc = stage_frames(ctx, &f, nullptr, 1, 1, 0, nullptr, nullptr, nullptr, layout))) return rc;
+    { TimedLaunch t(ctx, NVCA_K_GRAY);
+      launch_yuv420_to_bgr(ctx->cs(), ws.res[ws.cur_res].staging.as<uint8_t>(), w, h, layout->stride[0], planes, ws.ln().aux.as<uint8_t>(), (int)dp); }
+    return unstage_2d(ctx, dst, dst_stride, ws.ln().aux.p, dp, (size_t)w * 3, h, mem);
+}
+NVCA_API_CATCH(ctx)
+
 int nvca_resize_linear(nvca_ctx *ctx, const void *src, int sw, int sh, int sstride, int channels, int mem, void *dst,
                        int dw, int dh, int dstride)
 try {

@@ -144,6 +144,217 @@ void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, 
     }
 }
 
+// ---- 4:2:0 sources (NV12 / I420 face streams, nvca_yuv420_to_bgr): cv::cvtColor(CV_YUV2BGR_NV12 / _I420) in front of
+// FACE/kmsfacedetect.cpp:805, computed where the frame is read.  OpenCV 2.4 color.cpp, BT.601 limited range, shift 20:
+// pixel (x, y) takes the chroma sample (x >> 1, y >> 1); all int32, the shift arithmetic.
+struct ChromaTerm { int r, g, b; };                      // what a chroma sample adds to every pixel of its 2 x 2 block, rounding included
+__device__ __forceinline__ ChromaTerm chroma_term(int U, int V)
+{
+    const int u = U - 128, v = V - 128;
+    ChromaTerm c;
+    c.r = (1 << 19) + 1673527 * v;
+    c.g = (1 << 19) - 852492 * v - 409993 * u;
+    c.b = (1 << 19) + 2116026 * u;
+    return c;
+}
+__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+__device__ __forceinline__ void yuv_bgr(int Y, const ChromaTerm &c, int &B, int &G, int &R)
+{
+    const int y = (Y > 16 ? Y - 16 : 0) * 1220542;
+    B = sat8((y + c.b) >> 20); G = sat8((y + c.g) >> 20); R = sat8((y + c.r) >> 20);
+}
+__device__ __forceinline__ int yuv_gray(int Y, const ChromaTerm &c)
+{
+    int B, G, R;
+    yuv_bgr(Y, c, B, G, R);
+    return gray_of(B, G, R);
+}
+template <int FMT>
+__device__ __forceinline__ ChromaTerm chroma_at(const uint8_t *__restrict__ src, const YuvPlanes &p, int cx, int cy)
+{
+    if (FMT == 1) { const uint8_t *c = src + p.off_u + (size_t)cy * p.cstride + 2 * cx; return chroma_term(c[0], c[1]); }
+    return chroma_term(src[p.off_u + (size_t)cy * p.cstride + cx], src[p.off_v + (size_t)cy * p.vstride + cx]);
+}
+
+// ---- K1 for 4:2:0 frames at full resolution, beside k_gray_fast4: a thread owns 16 pixels of two rows -- the block one row of
+// chroma samples serves -- and reads them with one 16-byte load per luma row and 16 bytes of chroma (NV12: 8 U,V pairs; I420: 8
+// bytes of each plane).  Units are numbered along the rows and on from one row pair to the next, so every lane of a launch but
+// the last few has work whatever the width.  The unit at the end of a row that holds fewer than 16 pixels goes byte by byte.
+// Wants every plane and its stride aligned to the loads (launch_gray_yuv sends anything else to k_gray_yuv_generic).
+template <int FMT>
+__global__ __launch_bounds__(256) void k_gray_yuv16(
+    const uint8_t *const *__restrict__ srcs, PreGeom g, YuvPlanes p, uint8_t *__restrict__ gray, unsigned *__restrict__ hist)
+{
+    __shared__ unsigned lh[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6, slot = blockIdx.z;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    const uint8_t *__restrict__ src = srcs[slot];
+    const int upr = (g.w + 15) >> 4;                        // units per row pair
+    const int unit = blockIdx.x * 256 + tid;
+    if (unit < upr * (g.h >> 1)) {
+        const int ry = unit / upr, x = (unit - ry * upr) << 4;
+        const uint8_t *y0 = src + p.off_y + (size_t)(2 * ry) * g.sstride + x, *y1 = y0 + g.sstride;
+        uint8_t *g0 = gray + (size_t)slot * g.gray_slot + (size_t)(2 * ry) * g.gpitch + x, *g1 = g0 + g.gpitch;
+        if (x + 16 <= g.w) {
+            const uint4 a = *(const uint4 *)y0, b = *(const uint4 *)y1;
+            const unsigned yw0[4] = {a.x, a.y, a.z, a.w}, yw1[4] = {b.x, b.y, b.z, b.w};
+            unsigned cw[4];                                 // NV12: U,V pairs; I420: cw[0..1] U, cw[2..3] V
+            if (FMT == 1) {
+                const uint4 c = *(const uint4 *)(src + p.off_u + (size_t)ry * p.cstride + x);
+                cw[0] = c.x; cw[1] = c.y; cw[2] = c.z; cw[3] = c.w;
+            } else {
+                const uint2 u = *(const uint2 *)(src + p.off_u + (size_t)ry * p.cstride + (x >> 1));
+                const uint2 v = *(const uint2 *)(src + p.off_v + (size_t)ry * p.vstride + (x >> 1));
+                cw[0] = u.x; cw[1] = u.y; cw[2] = v.x; cw[3] = v.y;
+            }
+            unsigned o0[4] = {0, 0, 0, 0}, o1[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                int U, V;
+                if (FMT == 1) { const unsigned w = cw[k >> 1] >> ((k & 1) * 16); U = w & 255; V = (w >> 8) & 255; }
+                else { U = (cw[k >> 2] >> ((k & 3) * 8)) & 255; V = (cw[2 + (k >> 2)] >> ((k & 3) * 8)) & 255; }
+                const ChromaTerm c = chroma_term(U, V);
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const int wi = (2 * k + j) >> 2, sh = ((2 * k + j) & 3) * 8;
+                    const int v0 = yuv_gray((yw0[wi] >> sh) & 255, c), v1 = yuv_gray((yw1[wi] >> sh) & 255, c);
+                    o0[wi] |= (unsigned)v0 << sh; o1[wi] |= (unsigned)v1 << sh;
+                    if (hist) { atomicAdd(&lh[wave][v0], 1u); atomicAdd(&lh[wave][v1], 1u); }
+                }
+            }
+            *(uint4 *)g0 = make_uint4(o0[0], o0[1], o0[2], o0[3]);
+            *(uint4 *)g1 = make_uint4(o1[0], o1[1], o1[2], o1[3]);
+        } else {
+            for (int k = 0; x + k < g.w; k += 2) {          // the width is even: whole chroma pairs
+                const ChromaTerm c = chroma_at<FMT>(src, p, (x + k) >> 1, ry);
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const int v0 = yuv_gray(y0[k + j], c), v1 = yuv_gray(y1[k + j], c);
+                    g0[k + j] = (uint8_t)v0; g1[k + j] = (uint8_t)v1;
+                    if (hist) { atomicAdd(&lh[wave][v0], 1u); atomicAdd(&lh[wave][v1], 1u); }
+                }
+            }
+        }
+    }
+    if (hist) hist_flush(lh, hist + slot * 256, tid);
+}
+
+// ---- K1 generic for 4:2:0 frames: one output pixel per thread, any resize mode, any alignment.  The reference's order
+// (convert, cv::resize on BGR, BGR2GRAY): every tap of the resize is a converted pixel, the resize runs per channel with
+// k_gray_generic's arithmetic.
+template <int FMT>
+__global__ __launch_bounds__(256) void k_gray_yuv_generic(
+    const uint8_t *const *__restrict__ srcs, PreGeom g, YuvPlanes p, int mode,
+    const int *__restrict__ xofs, const short *__restrict__ ialpha,
+    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    uint8_t *__restrict__ gray, unsigned *__restrict__ hist)
+{
+    __shared__ unsigned lh[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6, slot = blockIdx.z;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    const uint8_t *__restrict__ src = srcs[slot];
+    const int x = blockIdx.x * 256 + tid;
+    uint8_t *grow = gray + (size_t)slot * g.gray_slot;
+    auto tap = [&](int r, int c, int &B, int &G, int &R) {
+        yuv_bgr(src[p.off_y + (size_t)r * g.sstride + c], chroma_at<FMT>(src, p, c >> 1, r >> 1), B, G, R);
+    };
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= g.h) break;
+        if (x < g.w) {
+            int B, G, R;
+            if (mode == 0) tap(y, x, B, G, R);
+            else if (mode == 2) {
+                int b[4], gg[4], r[4];
+                tap(2 * y, 2 * x, b[0], gg[0], r[0]); tap(2 * y, 2 * x + 1, b[1], gg[1], r[1]);
+                tap(2 * y + 1, 2 * x, b[2], gg[2], r[2]); tap(2 * y + 1, 2 * x + 1, b[3], gg[3], r[3]);
+                B = (b[0] + b[1] + b[2] + b[3] + 2) >> 2; G = (gg[0] + gg[1] + gg[2] + gg[3] + 2) >> 2; R = (r[0] + r[1] + r[2] + r[3] + 2) >> 2;
+            } else {
+                int sy0 = yofs[y], sy1 = sy0 + 1;
+                sy0 = sy0 >= 0 ? (sy0 < g.sh ? sy0 : g.sh - 1) : 0;
+                sy1 = sy1 >= 0 ? (sy1 < g.sh ? sy1 : g.sh - 1) : 0;
+                const int sx = xofs[x];
+                const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
+                int t0[3], t1[3], c[3];
+                tap(sy0, sx, t0[0], t0[1], t0[2]); tap(sy1, sx, t1[0], t1[1], t1[2]);
+                if (x < xmax) {
+                    const int a0 = ialpha[2 * x], a1 = ialpha[2 * x + 1];
+                    int n0[3], n1[3];
+                    tap(sy0, sx + 1, n0[0], n0[1], n0[2]); tap(sy1, sx + 1, n1[0], n1[1], n1[2]);
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        const int h0 = t0[k] * a0 + n0[k] * a1, h1 = t1[k] * a0 + n1[k] * a1;
+                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        const int h0 = t0[k] * 2048, h1 = t1[k] * 2048;
+                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                    }
+                }
+                B = c[0] & 255; G = c[1] & 255; R = c[2] & 255;
+            }
+            const int v = gray_of(B, G, R);
+            grow[(size_t)y * g.gpitch + x] = (uint8_t)v;
+            if (hist) atomicAdd(&lh[wave][v], 1u);
+        }
+    }
+    if (hist) hist_flush(lh, hist + slot * 256, tid);
+}
+
+bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, int mode,
+                     const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+                     uint8_t *gray, unsigned *hist, int batch, bool aligned16)
+{
+    if (mode == 0 && aligned16) {
+        const int units = ((g.w + 15) >> 4) * (g.h >> 1);
+        dim3 grid((units + 255) / 256, 1, batch);
+        if (p.fmt == 1) NVCA_LAUNCH(k_gray_yuv16<1>, grid, dim3(256), 0, st, d_src, g, p, gray, hist);
+        else            NVCA_LAUNCH(k_gray_yuv16<2>, grid, dim3(256), 0, st, d_src, g, p, gray, hist);
+        return true;
+    } else {
+        dim3 grid((g.w + 255) / 256, (g.h + kGrayRows - 1) / kGrayRows, batch);
+        if (p.fmt == 1) NVCA_LAUNCH(k_gray_yuv_generic<1>, grid, dim3(256), 0, st, d_src, g, p, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax, gray, hist);
+        else            NVCA_LAUNCH(k_gray_yuv_generic<2>, grid, dim3(256), 0, st, d_src, g, p, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax, gray, hist);
+        return false;
+    }
+}
+
+// ---- cv::cvtColor(CV_YUV2BGR_NV12 / _I420) as a primitive (nvca_yuv420_to_bgr): a thread converts the 2 x 2 blocks of one
+// chroma column, kGrayRows chroma rows of it
+template <int FMT>
+__global__ __launch_bounds__(256) void k_yuv420_to_bgr(const uint8_t *__restrict__ src, int w, int h, int ystride, YuvPlanes p,
+                                                       uint8_t *__restrict__ dst, int dstride)
+{
+    const int cx = blockIdx.x * 256 + threadIdx.x;
+    if (2 * cx >= w) return;
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int cy = blockIdx.y * kGrayRows + ry;
+        if (2 * cy >= h) break;
+        const ChromaTerm c = chroma_at<FMT>(src, p, cx, cy);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const uint8_t *y = src + p.off_y + (size_t)(2 * cy + j) * ystride + 2 * cx;
+            uint8_t *d = dst + (size_t)(2 * cy + j) * dstride + (size_t)cx * 6;
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                int B, G, R;
+                yuv_bgr(y[i], c, B, G, R);
+                d[3 * i] = (uint8_t)B; d[3 * i + 1] = (uint8_t)G; d[3 * i + 2] = (uint8_t)R;
+            }
+        }
+    }
+}
+void launch_yuv420_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int ystride, const YuvPlanes &p, uint8_t *dst, int dstride)
+{
+    dim3 grid((w / 2 + 255) / 256, (h / 2 + kGrayRows - 1) / kGrayRows, 1);
+    if (p.fmt == 1) NVCA_LAUNCH(k_yuv420_to_bgr<1>, grid, dim3(256), 0, st, src, w, h, ystride, p, dst, dstride);
+    else            NVCA_LAUNCH(k_yuv420_to_bgr<2>, grid, dim3(256), 0, st, src, w, h, ystride, p, dst, dstride);
+}
+
 // ---- 8UC1 resize (gray-then-resize order of the part detectors, pyramid levels)
 // one destination sample of cv::resize(INTER_LINEAR) 8UC1 (mode 0: copy, 2: exact 2x area-fast, 1: fixed-point bilinear)
 // `px(row, col)`: the source sample (a gray byte, a gray byte through a LUT, or the gray value of a BGR pixel)

@@ -29,6 +29,12 @@ hipError_t take_launch_error(const char **kernel);     // returns and clears the
 void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, int mode,
                  const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
                  uint8_t *gray, unsigned *hist, int batch, bool aligned4);
+// the same for a 4:2:0 frame (planes `p`); aligned16: every plane and stride of every frame takes 16-byte (I420 chroma: 8-byte) loads.
+// Returns whether k_gray_yuv16 took the launch (identity geometry and aligned16) and not k_gray_yuv_generic.
+bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, int mode,
+                     const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+                     uint8_t *gray, unsigned *hist, int batch, bool aligned16);
+void launch_yuv420_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int ystride, const YuvPlanes &p, uint8_t *dst, int dstride);
 void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,
                        int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot);
 void launch_pyr_integral(hipStream_t st, const uint8_t *aux, size_t aux_slot, const PyrLevelDev *levels, int nlev, int nimg,

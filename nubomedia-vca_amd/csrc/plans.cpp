@@ -411,15 +411,18 @@ GeomPlan *store_plan(nvca_ctx *ctx, const std::string &key, std::unique_ptr<Geom
 }
 
 // plan for "BGR frame -> working image -> scale-cascade scan"
+// (yuv: the frames are 4:2:0 buffers of this layout; stride is their luma stride, cn 1)
 int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int stride, int cn, int cols, int rows,
-                  double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out)
+                  double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out, const nvca_pixel_layout *yuv)
 {
     // multi-scale-factor 0 (scaleFactor 1.0): OpenCV's assertion fires in detectMultiScale, the reference logs it and passes the frame on
     // untouched (FACE/kmsfacedetect.cpp:540-542 installs the property with range 0 .. 51); every other value is a ladder that ends
     if (!(sf > 1.0)) { ctx->set_error("scaleFactor must be greater than 1 (multi-scale-factor 0)"); return NVCA_ERR_ARG; }
-    char key[256];
-    snprintf(key, sizeof(key), "F|%llu|%d|%d|%d|%d|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)casc->c.uid, W, H, stride,
-             cn, cols, rows, sf, minw, minh, maxw, maxh);
+    char key[384];
+    int kl = snprintf(key, sizeof(key), "F|%llu|%d|%d|%d|%d|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)casc->c.uid, W, H, stride,
+                      cn, cols, rows, sf, minw, minh, maxw, maxh);
+    if (yuv) snprintf(key + kl, sizeof(key) - kl, "|Y%d|%zu|%zu|%zu|%d|%d|%d", yuv->format, yuv->offset[0], yuv->offset[1], yuv->offset[2],
+                      yuv->stride[0], yuv->stride[1], yuv->stride[2]);
     if (GeomPlan *gp = find_plan(ctx, key)) { *out = gp; return NVCA_OK; }
     std::unique_ptr<GeomPlan> gp(new GeomPlan());
     make_geom(gp->g, W, H, stride, cn, cols, rows);

@@ -21,7 +21,7 @@ struct Switches {
     int  ingest_chunk = 8;           // NVCA_INGEST_CHUNK=n: chunk size of host-frame batches, 0 = no chunking (default 8)
     int  deep_stage = 0;             // NVCA_DEEP_STAGE=s: first stage of k_deep (default 0: the plan's own choice)
     bool tiles = true;               // NVCA_TILES=0: row-strip kernel instead of the tile kernels (default 1)
-    bool plan_debug = false;         // NVCA_PLAN_DEBUG: per-scale tile sizes on stderr (default off)
+    bool plan_debug = false;         // NVCA_PLAN_DEBUG: per-scale tile sizes, and the gray kernel of each 4:2:0 launch, on stderr (default off)
     bool deep_lds = true;            // NVCA_DEEP_LDS_OFF: k_deep without LDS patches (default: with them)
     bool trk_fold = true;            // NVCA_TRK_FOLD=0: NuboTracker's components through the per-pixel kernels (k_ccl_flatten / _reduce / _collect) instead of the per-tile reduction + fold of tile roots (default 1)
     int  trk_order = -1;             // NVCA_TRK_ORDER: visiting order of k_ccl_reduce (default -1: decided per frame on the device)

@@ -18,6 +18,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 HAAR_DO_CANNY_PRUNING, HAAR_SCALE_IMAGE, HAAR_FIND_BIGGEST_OBJECT, HAAR_DO_ROUGH_SEARCH = 1, 2, 4, 8
 SUM_F32PAIR, SUM_F64 = 0, 1
 K_COUNT = 14
+PIX_BGR, PIX_NV12, PIX_I420 = 0, 1, 2
 
 
 class NvcaError(RuntimeError):
@@ -45,6 +46,19 @@ class Overlay(C.Structure):
 class Frame(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("stride", C.c_int),
                 ("mem", C.c_int), ("pts", C.c_uint64)]
+
+
+class PixelLayout(C.Structure):
+    """nvca_pixel_layout: the planes of a 4:2:0 buffer, byte offsets from the frame's base and bytes per row"""
+    _fields_ = [("format", C.c_int), ("offset", C.c_size_t * 3), ("stride", C.c_int * 3)]
+
+
+def pixel_layout(fmt, offsets, strides):
+    lay = PixelLayout()
+    lay.format = fmt
+    for i, (o, s) in enumerate(zip(offsets, strides)):
+        lay.offset[i], lay.stride[i] = int(o), int(s)
+    return lay
 
 
 class FaceParams(C.Structure):
@@ -82,7 +96,7 @@ SYMBOLS = [
     "nvca_host_register", "nvca_host_unregister", "nvca_face_batch_submit", "nvca_face_batch_collect",
     "nvca_integral_tilted", "nvca_cascade_kind", "nvca_part_batch_process", "nvca_device_count", "nvca_draw_shapes",
     "nvca_cascade_validate_mem", "nvca_abi_selftest", "nvca_ctx_set_option", "nvca_ctx_get_option", "nvca_overlay_blend",
-    "nvca_part_batch_submit", "nvca_part_batch_collect",
+    "nvca_part_batch_submit", "nvca_part_batch_collect", "nvca_face_stream_set_input", "nvca_yuv420_to_bgr",
 ]
 
 _lib = None
@@ -165,6 +179,8 @@ def load():
     L.nvca_face_stream_destroy.restype = None
     L.nvca_face_stream_set_params.argtypes = [vp, C.POINTER(FaceParams)]
     L.nvca_face_stream_motion_event.argtypes = [vp]
+    L.nvca_face_stream_set_input.argtypes = [vp, C.POINTER(PixelLayout)]
+    L.nvca_yuv420_to_bgr.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(PixelLayout), C.c_int, vp, C.c_int]
     L.nvca_face_stream_process.argtypes = [vp, C.POINTER(Frame), C.POINTER(Rect), ip, C.c_int, ip]
     L.nvca_face_batch_process.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Frame), C.POINTER(Rect), ip, C.c_int, ip]
     L.nvca_face_batch_submit.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Frame), ip]
@@ -321,6 +337,16 @@ class Context:
         self.check(self.L.nvca_integral(self.h, img.ctypes.data, w, h, img.strides[0], MEM_HOST,
                                         s.ctypes.data_as(C.POINTER(C.c_int32)), q.ctypes.data_as(C.POINTER(C.c_double))))
         return s, q
+
+    def yuv420_to_bgr(self, buf, w, h, layout, mem=MEM_HOST, dst=None, dst_stride=None):
+        """nvca_yuv420_to_bgr.  Host: buf is a flat uint8 numpy buffer, the BGR image [h, w, 3] is returned.  Device: buf and dst
+        are device pointers (dst: packed BGR rows dst_stride bytes apart), nothing is returned."""
+        if mem == MEM_HOST:
+            buf = np.ascontiguousarray(buf, np.uint8)
+            out = np.empty((h, w, 3), np.uint8)
+            self.check(self.L.nvca_yuv420_to_bgr(self.h, buf.ctypes.data, w, h, C.byref(layout), MEM_HOST, out.ctypes.data, w * 3))
+            return out
+        self.check(self.L.nvca_yuv420_to_bgr(self.h, int(buf), w, h, C.byref(layout), MEM_DEVICE, int(dst), dst_stride))
 
     def draw_shapes(self, frame, channels, shapes):
         """nvca_draw_shapes: shapes = [(kind, x, y, w, h, (b, g, r, a))]; frame: a Frame (device memory) or a writable numpy image (drawn in place)"""
@@ -511,6 +537,17 @@ def make_frame(arr_or_ptr, width=None, height=None, stride=None, mem=MEM_HOST, p
     return Frame(int(arr_or_ptr), width, height, stride, mem, pts)
 
 
+def make_planar_frame(buf, width, height, layout, mem=MEM_HOST, pts=0):
+    """Frame of a 4:2:0 stream (FaceStream.set_input): buf is the flat uint8 numpy buffer the layout's offsets count from (host),
+    or a device pointer; width x height is the luma size, the frame's stride the layout's stride[0]."""
+    if isinstance(buf, np.ndarray):
+        assert buf.dtype == np.uint8 and buf.flags.c_contiguous
+        f = Frame(buf.ctypes.data, width, height, layout.stride[0], MEM_HOST, pts)
+        f._keep = buf
+        return f
+    return Frame(int(buf), width, height, layout.stride[0], mem, pts)
+
+
 class FaceStream:
     """nvca_face_stream: mirrors one `nubofacedetector` element instance
     (properties of FACE/kmsfacedetect.cpp:1043-1102 by their reference names)."""
@@ -536,6 +573,10 @@ class FaceStream:
 
     def motion_event(self):
         self.ctx.check(self.ctx.L.nvca_face_stream_motion_event(self.h))
+
+    def set_input(self, layout=None):
+        """nvca_face_stream_set_input: the stream's frames are 4:2:0 buffers of this PixelLayout from now on (None: packed BGR)"""
+        self.ctx.check(self.ctx.L.nvca_face_stream_set_input(self.h, C.byref(layout) if layout is not None else None))
 
     def process(self, bgr, cap=64):
         """One transform_frame_ip on a host BGR frame -> (boxes[n,4], ids[n])."""

@@ -488,6 +488,35 @@ def gray_to_bgr(g, seed, channels=3):
     return out
 
 
+def make_yuv420(W, H, seed, fmt, kind="natural", faces=(), pad=0, luma_rows=None, gap=0, chroma_pad=None):
+    """A 4:2:0 frame as a decoder lays it out: (flat uint8 buffer, (format, offsets, strides)) with format 1 = NV12, 2 = I420 (the
+    values of NVCA_PIX_*).  Y = 16 + gray * 219 / 255 of make_gray's field (limited range), chroma near 128 with small seeded
+    noise.  pad: bytes added to every plane's row (chroma_pad: to the chroma planes' rows, where that differs); luma_rows: rows the luma plane is allocated with (1080 in 1088; the chroma
+    planes likewise); gap: unused bytes between planes.  What no pixel lies in holds 0xA5."""
+    assert W % 2 == 0 and H % 2 == 0 and fmt in (1, 2)
+    g = make_gray(W, H, seed, kind, faces).astype(np.int32)
+    rng = np.random.default_rng(seed ^ 0xC420)
+    y = (16 + (g * 219 + 127) // 255).astype(np.uint8)
+    u = (128 + rng.integers(-9, 10, size=(H // 2, W // 2))).astype(np.uint8)
+    v = (128 + rng.integers(-9, 10, size=(H // 2, W // 2))).astype(np.uint8)
+    rows = luma_rows or H
+    assert rows >= H and rows % 2 == 0
+    ys, cpad = W + pad, pad if chroma_pad is None else chroma_pad
+    if fmt == 1:
+        planes = [(y, ys, rows), (np.stack([u, v], axis=-1).reshape(H // 2, W), W + cpad, rows // 2)]
+    else:
+        planes = [(y, ys, rows), (u, W // 2 + cpad, rows // 2), (v, W // 2 + cpad, rows // 2)]
+    offsets, strides, off = [], [], 0
+    for (_, st, nr) in planes:
+        offsets.append(off); strides.append(st)
+        off += st * nr + gap
+    buf = np.full(off - gap, 0xA5, np.uint8)
+    for (p, st, nr), o in zip(planes, offsets):
+        view = buf[o:o + st * nr].reshape(nr, st)
+        view[:p.shape[0], :p.shape[1]] = p
+    return buf, (fmt, offsets, strides)
+
+
 def frame_seed(stream_id, frame_idx):
     """seed = 0xC0FFEE + stream_id*1000 + frame_idx."""
     return 0xC0FFEE + stream_id * 1000 + frame_idx
