@@ -42,6 +42,46 @@ template <class T> __device__ __forceinline__ T load_const(const T *p)
     return r;
 }
 
+// What the tile kernels read of a scale's record.  The record is bound BY VALUE, once per workgroup (k_tile) or band (k_band):
+// its fields are wave-uniform and constant for the whole walk, but through a reference into global memory the compiler has
+// to assume that the kernel's own stores alias them and reloads every field at every use, with vector loads that stand in the
+// tile's chain of dependent round trips.  Read through the constant address space they are scalar loads, issued once.
+struct ScaleHot {
+    int plane_off, pitch, eq[4], xpos_off, ypos_off, sq32, task_off, wpr, adaptive;
+    double inv_area;
+    const TStumpRec *trecs; const LStumpRec *lrecs;
+};
+__device__ __forceinline__ ScaleHot load_scale(const ScaleRec *p)
+{
+    typedef const __attribute__((address_space(4))) ScaleRec CScaleRec;
+    CScaleRec *q = (CScaleRec *)p;
+    ScaleHot h;
+    h.plane_off = q->plane_off; h.pitch = q->pitch;
+#pragma unroll
+    for (int i = 0; i < 4; i++) h.eq[i] = q->eq[i];
+    h.xpos_off = q->xpos_off; h.ypos_off = q->ypos_off; h.sq32 = q->sq32; h.task_off = q->task_off; h.wpr = q->wpr; h.adaptive = q->adaptive;
+    h.inv_area = q->inv_area;
+    h.trecs = q->trecs; h.lrecs = q->lrecs;
+    return h;
+}
+// The part of it that tile_coords / tile_commit / tile_stages use, with what derives from the record and the batch slot formed
+// once: plane and table pointers as scalar pairs
+struct TileScale {
+    int pitch, xpos_off, ypos_off, wpr;
+    const char *sum;                 // the slot's sum plane of this scale
+    double *vnf;                     // the slot's variance normalisers of the scale's first scan row (a row of tiles adds iy0 * wpr * 64)
+    const TStumpRec *trecs; const LStumpRec *lrecs;
+};
+__device__ __forceinline__ TileScale tile_scale(const CascadeArgs &a, const ScaleHot &h, int slot)
+{
+    TileScale ts;
+    ts.pitch = h.pitch; ts.xpos_off = h.xpos_off; ts.ypos_off = h.ypos_off; ts.wpr = h.wpr;
+    ts.sum = (const char *)(a.sum + (size_t)slot * a.sum_slot + h.plane_off);
+    ts.vnf = a.vnf + ((size_t)slot * a.ntasks + h.task_off) * 64;
+    ts.trecs = h.trecs; ts.lrecs = h.lrecs;
+    return ts;
+}
+
 // ---- K5b: stages 1 .. deep_stage-1 on LDS lattice tiles -------------------------------------
 // A tile is nx x ny (<= 32 x 16) windows of one scale.  Window origins and scaled rectangle corners of a scale
 // fall on a near-lattice, so the tile's windows touch only ~2.7 (n + 20) distinct columns and rows of the sum
@@ -120,11 +160,7 @@ __device__ __forceinline__ Sum tile_vote_s(unsigned cm, unsigned rm, double vnf,
 template <bool PAIR, class Sum = double>
 __device__ __forceinline__ Sum tile_stage_sum(unsigned cm, unsigned rm, double vnf, const TStumpRec *recs, int j0, int count, int step)
 {
-    // the table pointer is wave-uniform but comes out of a vector load: hand the asm a scalar copy
-    const unsigned long long u = (unsigned long long)recs;
-    const unsigned long long ub = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) |
-                                  (unsigned)__builtin_amdgcn_readfirstlane((int)u);
-    const TStumpRec *base = (const TStumpRec *)ub;
+    const TStumpRec *base = recs;        // wave-uniform, in scalar registers (TileScale::trecs)
     asm("" : "+v"(cm), "+v"(rm));        // keep the two per-window addresses whole: a look-up address is then one shift-add of a scalar
     Sum sum = 0;
     for (int j = j0; j < count; j += step) sum += tile_vote_s<PAIR, Sum>(cm, rm, vnf, load_srec(base + j));
@@ -214,8 +250,11 @@ __device__ __forceinline__ TileLds carve_tile(unsigned char *lds, const TileRec 
 // destination is 64 consecutive words of the row, no registers in between).  A wave takes rows wave, wave + NW, ...; every
 // transfer of the tile is in flight before the first one is waited for (register staging kept two rows per wave in
 // flight: the copy was a chain of dependent round trips).  The caller waits: s_waitcnt vmcnt(0) + barrier before T is read.
-struct TileCoords { int mapc, mapr, wx, wy; unsigned rowb, xcb[4]; };
-__device__ __forceinline__ TileCoords tile_coords(const CascadeArgs &a, const TileRec &t, const ScaleRec &sc)
+// The list entries stay as loaded (rowy: a sample row, xc: sample columns): whatever is computed from them here would be waited
+// for here, and in k_band, where the next tile's coordinates are requested behind this tile's transfers, that wait is a wait
+// for every transfer of the tile (vmcnt counts in order) in front of the remaining requests.  tile_commit scales them.
+struct TileCoords { int mapc, mapr, wx, wy; unsigned rowy, xc[4]; };
+__device__ __forceinline__ TileCoords tile_coords(const CascadeArgs &a, const TileRec &t, const TileScale &sc)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int NW = kTileThreads / 64;
@@ -226,26 +265,27 @@ __device__ __forceinline__ TileCoords tile_coords(const CascadeArgs &a, const Ti
     c.wx = tid < t.nx ? a.pos[sc.xpos_off + t.ix0 + tid] : 0;
     c.wy = (tid >= 64 && tid < 64 + t.ny) ? a.pos[sc.ypos_off + t.iy0 + tid - 64] : 0;
     const int nmine = t.nrow > wave ? (t.nrow - wave + NW - 1) / NW : 0;
-    c.rowb = lane < nmine ? (unsigned)rl[wave + NW * lane] * (unsigned)sc.pitch * 4u : 0u;     // lane j: the wave's j-th sample row
+    c.rowy = 0u;
+    if (lane < nmine) c.rowy = rl[wave + NW * lane];         // lane j: the wave's j-th sample row
 #pragma unroll
-    for (int k = 0; k < 4; k++) { const int q = lane + 64 * k; c.xcb[k] = 4u * (unsigned)cl[q < t.ncol ? q : t.ncol - 1]; }
+    for (int k = 0; k < 4; k++) { const int q = lane + 64 * k; c.xc[k] = cl[q < t.ncol ? q : t.ncol - 1]; }
     return c;
 }
-__device__ __forceinline__ void tile_commit(const CascadeArgs &a, const TileRec &t, const ScaleRec &sc, int slot, const TileLds &L, const TileCoords &c)
+__device__ __forceinline__ void tile_commit(const TileRec &t, const TileScale &sc, const TileLds &L, const TileCoords &c)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int NW = kTileThreads / 64;
-    const char *__restrict__ src = (const char *)(a.sum + (size_t)slot * a.sum_slot + sc.plane_off);
+    const char *__restrict__ src = sc.sum;
     const int nmine = t.nrow > wave ? (t.nrow - wave + NW - 1) / NW : 0;
     const int nk = (t.ncol + 63) >> 6;      // 64-column groups that hold a staged column (wave-uniform)
     for (int j = 0; j < nmine; j++) {
-        const unsigned rb = (unsigned)__builtin_amdgcn_readlane((int)c.rowb, j);
+        const unsigned rb = (unsigned)__builtin_amdgcn_readlane((int)c.rowy, j) * (unsigned)sc.pitch * 4u;      // byte offset of the row: scalar
         const char *rowp = src + rb;
         int *dst = L.T + (wave + NW * j) * L.pitchT;
 #pragma unroll
         for (int k = 0; k < 4; k++)
             if (k < nk && lane + 64 * k < t.ncol)
-                __builtin_amdgcn_global_load_lds((gptr_t)(rowp + c.xcb[k]), (lptr_t)(dst + 64 * k), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(rowp + 4u * c.xc[k]), (lptr_t)(dst + 64 * k), 4, 0, 0);
     }
     if (tid < 3) L.qn[tid] = 0;          // the three rotating queue counters (qn[3]: list base scratch)
     if (tid < t.nx) L.winx[tid] = (unsigned short)(c.wx - t.x0);
@@ -303,7 +343,7 @@ static constexpr int kPairMax = 32;           // windows up to which a round run
 static_assert(7 * kPairMax <= kTileSlots && 64 + kTileRows <= kTileThreads && kTileRows <= kTileWin,
               "a round's seven accumulator rows fit the tile's accumulators; threads 64 .. 64 + kTileRows - 1 fill winy[kTileWin]");
 template <bool VNF_LDS>
-__device__ __forceinline__ void tile_stages(const CascadeArgs &a, const TileRec &t, const ScaleRec &sc, int slot, const TileLds &L, int ti = 0, int par = 0)
+__device__ __forceinline__ void tile_stages(const CascadeArgs &a, const TileRec &t, const TileScale &sc, int slot, const TileLds &L, int ti = 0, int par = 0)
 {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -311,8 +351,7 @@ __device__ __forceinline__ void tile_stages(const CascadeArgs &a, const TileRec 
     int *stat_w = L.qn + 4 + (par ^ 1) * kStatStages;       // what this tile sees
     constexpr int NW = kTileThreads / 64;
     const TStumpRec *urecs = sc.trecs;
-    const size_t vbase = ((size_t)slot * a.ntasks + sc.task_off + (size_t)t.iy0 * sc.wpr) * 64;
-    const double *__restrict__ vnfp = a.vnf + vbase;
+    const double *__restrict__ vnfp = sc.vnf + (size_t)t.iy0 * sc.wpr * 64;
     auto vnf_of = [&](int w) {
         if (VNF_LDS) return L.vnf_s[w];
         const int ix = t.ix0 + (w & 31);
@@ -536,7 +575,7 @@ __device__ __forceinline__ void tile_stages(const CascadeArgs &a, const TileRec 
         const int w = qi[i], ix = t.ix0 + (w & 31);
         const unsigned key = ((unsigned)t.scale << a.key_ss) | ((unsigned)(t.iy0 + (w >> 5)) << a.key_sy) | (unsigned)ix;
         if (gb + i < cap) list[1 + gb + i] = ((unsigned long long)slot << 32) | key;
-        if (VNF_LDS && last != a.nstages) a.vnf[vbase + ((size_t)(w >> 5) * sc.wpr + (ix >> 6)) * 64 + (ix & 63)] = L.vnf_s[w];
+        if (VNF_LDS && last != a.nstages) sc.vnf[((size_t)(t.iy0 + (w >> 5)) * sc.wpr + (ix >> 6)) * 64 + (ix & 63)] = L.vnf_s[w];
     }
     NVCA_STAMP(a, ti, 7);
 }
@@ -559,19 +598,20 @@ __global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_tile(Cascad
     const int tidx = a.tile_order[blockIdx.x - slot * a.tile_blocks_per_frame];
     if (tidx < 0) return;
     const TileRec t = a.tiles[tidx];
-    const ScaleRec &sc = a.scales[t.scale];
+    const ScaleHot sh = load_scale(a.scales + t.scale);
+    const TileScale sc = tile_scale(a, sh, slot);
     const TileLds L = carve_tile(lds, t);
     const TileCoords tc = tile_coords(a, t, sc);
-    tile_commit(a, t, sc, slot, L, tc);
+    tile_commit(t, sc, L, tc);
     tile_prologue(a, L);
-    const unsigned long long *__restrict__ bits = a.failbits + (size_t)slot * a.ntasks + sc.task_off + (size_t)t.iy0 * sc.wpr;
+    const unsigned long long *__restrict__ bits = a.failbits + (size_t)slot * a.ntasks + sh.task_off + (size_t)t.iy0 * sc.wpr;
     // this thread's window (window id = ry * 32 + rx = tid): the pre-pass's verdict on it, under the tile's transfers
     const int w = tid, ry = w >> 5, rx = w & 31;
     bool keep = false;
     if (ry < t.ny && rx < t.nx) {
         const int ix = t.ix0 + rx;
         const unsigned long long *rb = bits + (size_t)ry * sc.wpr;
-        if (!((rb[ix >> 6] >> (ix & 63)) & 1ull)) keep = sc.adaptive ? visited(rb, ix) : true;
+        if (!((rb[ix >> 6] >> (ix & 63)) & 1ull)) keep = sh.adaptive ? visited(rb, ix) : true;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's transfers have landed
     __syncthreads();                 // qn zeroed, maps and samples staged
@@ -600,11 +640,15 @@ __global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_band(Cascad
         bi = r / g; slot = xcd + 8 * (fi * g + (r - bi * g));
     }
     const BandRec b = load_const(a.bands + a.band_order[bi]);
-    const ScaleRec &sc = a.scales[b.scale];
-    const unsigned *__restrict__ sql = (const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + sc.plane_off;
-    const uint8_t *__restrict__ sqh = (const uint8_t *)((const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + a.sum_slot) + sc.plane_off;
-    const bool sq_lo_only = sc.sq32 != 0;
-    const int ex0 = sc.eq[0] % sc.pitch, ey0 = sc.eq[0] / sc.pitch, ex1 = sc.eq[3] % sc.pitch, ey1 = sc.eq[3] / sc.pitch;
+    // the scale's record and what derives from it and the slot: once per band, in scalar registers
+    const ScaleHot sh = load_scale(a.scales + b.scale);
+    const TileScale sc = tile_scale(a, sh, slot);
+    const unsigned *__restrict__ sql = (const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + sh.plane_off;
+    const uint8_t *__restrict__ sqh = (const uint8_t *)((const unsigned *)a.sqsum + (size_t)slot * 2 * a.sum_slot + a.sum_slot) + sh.plane_off;
+    const bool sq_lo_only = sh.sq32 != 0;
+    const int ex0 = sh.eq[0] % sh.pitch, ey0 = sh.eq[0] / sh.pitch, ex1 = sh.eq[3] % sh.pitch, ey1 = sh.eq[3] / sh.pitch;
+    const double inv_area = sh.inv_area;
+    const bool adaptive_x = sh.adaptive != 0;
     const StageRec st0 = load_const(a.stages);
     const bool pair0 = a.pair_policy && (st0.flags & 1);
     static_assert(kTileSlots == kTileThreads, "one window per thread and tile");
@@ -623,19 +667,20 @@ __global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_band(Cascad
         NVCA_STAMP(a, ti, 0);
         const TileLds L = carve_tile(lds, t);
         // this thread's window: the four (eight) squared-integral corners -- uncoalesced global reads -- are requested before the
-        // tile's samples and arrive under their transfer
+        // tile's samples and arrive under their transfer: every address below comes from registers, nothing is waited for
+        // between the barrier above and the last transfer of tile_commit
         const bool active = ry < t.ny && rx < t.nx;
         int xw = oxw, yw = oyw;
         unsigned q0 = 0, q1 = 0, q2 = 0, q3 = 0, h0 = 0, h1 = 0, h2 = 0, h3 = 0;
         if (active) {
             xw -= t.x0; yw -= t.y0;
             const unsigned off = (unsigned)((t.y0 + yw) * sc.pitch + t.x0 + xw);
-            const unsigned e0 = off + sc.eq[0], e1 = off + sc.eq[1], e2 = off + sc.eq[2], e3 = off + sc.eq[3];
+            const unsigned e0 = off + sh.eq[0], e1 = off + sh.eq[1], e2 = off + sh.eq[2], e3 = off + sh.eq[3];
             q0 = sql[e0]; q1 = sql[e1]; q2 = sql[e2]; q3 = sql[e3];
             if (!sq_lo_only) { h0 = sqh[e0]; h1 = sqh[e1]; h2 = sqh[e2]; h3 = sqh[e3]; }
         }
         NVCA_STAMP(a, ti, 1);
-        tile_commit(a, t, sc, slot, L, tc);
+        tile_commit(t, sc, L, tc);
         if (tid < kStatStages) L.qn[4 + ((ti + 1) & 1) * kStatStages + tid] = 0;       // the survivor counts this tile will write
         TileRec tn = t; TileCoords tcn = tc; int nxw = 0, nyw = 0;
         if (ti + 1 < b.ntiles) {                                 // the next tile's coordinates
@@ -647,18 +692,19 @@ __global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_band(Cascad
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's transfers have landed
         __syncthreads();
         NVCA_STAMP(a, ti, 3);
+        asm volatile("" : "+v"(h0), "+v"(h1), "+v"(h2), "+v"(h3));      // the corners' high words are first touched here: arithmetic on them moved up in front of the transfers waits there for the gathers
         // variance + stage 0 for every window of the tile; a wave covers two window rows
         bool pass0 = false;
         if (active) {
             const int c0 = L.cmap[xw + ex0], c1 = L.cmap[xw + ex1], r0 = L.rmap[yw + ey0], r1 = L.rmap[yw + ey1];
             const int ws = lds_sample(r0, c0) - lds_sample(r0, c1) - lds_sample(r1, c0) + lds_sample(r1, c1);
-            const double mean = (double)ws * sc.inv_area;
+            const double mean = (double)ws * inv_area;
             // squared-pixel sum of the variance window: exact integers below 2^53 (see window_sqsum)
             double vnf;
             if (sq_lo_only) vnf = (double)(unsigned)(q0 - q1 - q2 + q3);
             else vnf = (double)(((unsigned long long)h0 << 32) | q0) - (double)(((unsigned long long)h1 << 32) | q1) -
                        (double)(((unsigned long long)h2 << 32) | q2) + (double)(((unsigned long long)h3 << 32) | q3);
-            vnf = vnf * sc.inv_area - mean * mean;
+            vnf = vnf * inv_area - mean * mean;
             vnf = vnf >= 0. ? sqrt(vnf) : 1.;
             L.vnf_s[w] = vnf;
             pass0 = tile_stage_pass(L.cmA + 2 * xw, L.rmA + 2 * yw, vnf, sc.trecs, st0, pair0);
@@ -670,7 +716,7 @@ __global__ __launch_bounds__(kTileThreads, kTileWavesPerSimd) void k_band(Cascad
         const unsigned R = lane < 32 ? (unsigned)fb : (unsigned)(fb >> 32);
         bool keep = false;
         if (active && !((R >> rx) & 1u)) {
-            if (!sc.adaptive) keep = true;
+            if (!adaptive_x) keep = true;
             else {
                 int ones = 0;
                 if (rx > 0) {
