@@ -58,7 +58,7 @@ struct TrkWorkspace {
     void release_all() { slots.release(); labels.release(); acc.release(); out.release(); staging.release(); flags.release(); roots.release(); tiles.release(); h_slots.release(); h_out.release(); tiles_w = tiles_h = tiles_batch = 0; }
 };
 
-// batched part detectors (parts.cpp): working images of a call carved from one arena, the small tables its launches read
+// batched part detectors (part_images.cpp): working images of a call carved from one arena, the small tables its launches read
 struct PartWorkspace {
     DevBuf arena, tables, hist, luts; PinnedBuf h_tables;
     size_t tab_used = 0;
@@ -71,6 +71,9 @@ struct DetectPlan;   // plan.cpp
 struct ScaleTable;   // plan.cpp: one cascade at one scale factor (geometry-independent stump records), cached in the context
 struct FaceTicket;   // face_stream.cpp
 void free_face_ticket(FaceTicket *t);
+struct PartCall;     // part_call.h: a submitted, not yet collected call of the batched part detectors
+// (parts.cpp) the outstanding calls that hold stream s (nullptr: any) are given up: rolled back (newest first), drained, deleted
+void part_calls_abandon(nvca_ctx *ctx, const nvca_part_stream *s);
 struct GeomPlan;     // host_state.h
 struct Workspace;    // host_state.h
 
@@ -112,7 +115,7 @@ struct nvca_ctx {
     uint64_t face_serial = 0;
     int ptr_ring_used = 0;                    // nvca_bgr2gray: entries of the frame-pointer ring handed out since the last drain
     int defer_device_sync = 0;                // > 0: primitives that write device memory return without draining the stream
-                                              // (internal callers chaining primitives on the context's stream, parts.cpp)
+                                              // (internal callers chaining primitives on the context's stream)
     std::string err;
     int hit_cap = 16384;
     int hit_cap_wanted = 0;                   // > hit_cap: a launch set produced more raw candidates than its lists hold; the per-frame size that holds it
@@ -124,11 +127,10 @@ struct nvca_ctx {
     std::unique_ptr<nvca::Workspace> ws;
     nvca::TrkWorkspace trk;           // tracker buffers live and die with the context
     // the working images / tables of a batched part-detector call; two sets: a submitted call (nvca_part_batch_submit) may be in
-    // flight while the one before it is collected -- a call uses the set of its ticket's parity (parts.cpp sets part_set)
+    // flight while the one before it is collected -- a call uses the set of its ticket's parity (part_call.cpp sets part_set)
     nvca::PartWorkspace part_sets[2]; int part_set = 0;
     nvca::PartWorkspace &pw() { return part_sets[part_set]; }
-    void *part_calls[2] = {nullptr, nullptr};  // submitted, not yet collected part-detector calls (parts.cpp: PartCall), by ticket parity
-    void (*part_calls_abandon)(nvca_ctx *) = nullptr;      // gives up whatever is outstanding (newest first: rolled back, drained, deleted)
+    nvca::PartCall *part_calls[2] = {nullptr, nullptr};    // submitted, not yet collected part-detector calls, by ticket parity (parts.cpp)
     int part_seq = 0;                         // the next ticket
     nvca::Switches sw;                // this context's switches: the process defaults (environment), nvca_ctx_set_option overrides
     int lds_grant[2] = {0, 0};        // dynamic LDS already granted to k_tile / k_band through this context (hipFuncSetAttribute)
@@ -187,7 +189,7 @@ int caller_h2d(nvca_ctx *ctx, void *dst, const void *src, size_t bytes, hipStrea
 int caller_h2d_rows(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows, hipStream_t st);
 int caller_d2h_rows(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows, hipStream_t st);   // returns with dst filled (the stream is drained)
 
-// ---- the part detectors' upload ring for small tables (parts.cpp); nvca_draw_shapes queues its shapes through it too
+// ---- the part detectors' upload ring for small tables (part_images.cpp); nvca_draw_shapes queues its shapes through it too
 int part_table(nvca_ctx *ctx, const void *host, size_t bytes, void **dev);   // a small table for the next launch on the current lane (upload ring)
 struct DetectJob;
 int make_detect_job(nvca_ctx *ctx, DetectJob &j, const nvca_cascade *casc, const void *gray, int w, int h, int stride, int mem,

@@ -1,7 +1,7 @@
 // detect_rounds.cpp -- rounds of detectMultiScale jobs that share one wait: every unfinished job of a set queues its next launch
 // set (detect_job.cpp; the small images of a round go into one launch: roi_batch.cpp), the lanes are waited for once, every job is
 // advanced.  The part detectors queue the face passes of every stream of a tick, then every ROI pass, with three synchronisations
-// per tick instead of several per stream (parts.cpp).
+// per tick instead of several per stream (part_call.cpp).
 #include "host_state.h"
 #include <cstdio>
 #include <algorithm>
@@ -12,7 +12,7 @@ using namespace nvca;
 
 namespace nvca {
 
-// One round of a job set in two halves, so that a caller may leave a round queued and come back for it (parts.cpp: a submitted part-detector
+// One round of a job set in two halves, so that a caller may leave a round queued and come back for it (part_call.cpp: a submitted part-detector
 // batch keeps its face passes in flight while the batch before it is collected).  begin: every unfinished job queues its next launch
 // set (small images: all in ONE k_roi launch); end: the lanes are waited for, the candidates handed out, every job advanced.
 struct JobRound { RoiBatch rb; bool used[kLanes] = {false}; int rc = NVCA_OK; double t_queued = 0; int roi_regrown = 0; };

@@ -197,7 +197,7 @@ void draw_shapes_host(uint8_t *data, int w, int h, int stride, int channels, con
 }
 
 // ------------------------------------------------------------ part detectors: merging heuristics
-// (moved here from parts.cpp: pure functions of box lists, O(#faces); std::vector idioms of the reference that rely on
+// (their callers: part_logic.cpp; pure functions of box lists, O(#faces); std::vector idioms of the reference that rely on
 // libstdc++ behaviour -- erase through a reverse iterator, erase(end()-i) inside a counting loop -- are written out as the
 // index operations they perform)
 typedef std::vector<nvca_rect> RectV;

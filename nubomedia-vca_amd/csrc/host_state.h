@@ -1,8 +1,8 @@
 // host_state.h -- host-side state and helpers that the library's host sources share (not part of the ABI): the workspace, the
 // cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect_job.cpp, detect_rounds.cpp,
-// roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, fb_search.cpp, part_stats.cpp, options.cpp,
-// cascade_xml.cpp and work_pool.cpp do not include it: the CPU drivers under tests/ build those without it (fb_search.cpp,
-// part_stats.cpp and options.cpp without any HIP header, the others with host doubles of their own).
+// roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, part_logic.cpp, fb_search.cpp, part_stats.cpp,
+// options.cpp, cascade_xml.cpp and work_pool.cpp do not include it: the CPU drivers under tests/ build those without it (part_logic.cpp,
+// fb_search.cpp, part_stats.cpp and options.cpp without any HIP header, the others with host doubles of their own).
 #pragma once
 #include "context.h"
 #include "plan.h"
@@ -26,7 +26,7 @@ struct ResultBufs {
 };
 // Working memory of the kernels, per LANE.  A lane is a HIP stream with its own planes and cascade scratch: whatever runs on a
 // lane is ordered by its stream, different lanes run side by side.  Everything uses lane 0 (the context's stream) except
-// the batched part detectors, which spread their streams' small, launch-bound jobs over all lanes (parts.cpp): the GPU then
+// the batched part detectors, which spread their streams' small, launch-bound jobs over all lanes (part_call.cpp): the GPU then
 // holds several of those tiny kernels at a time instead of one.  What a job leaves for the host lives in ResultBufs regions
 // of its own, shared by all lanes.
 struct Lane {

@@ -1,5 +1,5 @@
 // part_stats.h -- NVCA_PART_STATS (diagnostic): where the batched part detectors and their job rounds spend the host's time.  One
-// per context (nvca_ctx::stats); parts.cpp and detect_rounds.cpp add to it through scoped timers, report() and report_round() print it.
+// per context (nvca_ctx::stats); part_call.cpp and detect_rounds.cpp add to it through scoped timers, report() and report_round() print it.
 #pragma once
 #include <chrono>
 #include <cstddef>

@@ -4,6 +4,8 @@ bit-exact box lists over multi-frame sequences (the merging heuristics carry sta
 import numpy as np
 import pytest
 
+from part_scenes import scene as _scene
+
 pytestmark = pytest.mark.gpu
 
 PARTS = ("righteye", "lefteye", "nose", "mouth", "leftear", "rightear")
@@ -36,18 +38,6 @@ def _streams(env, kind, **props):
     g = capi.PartStream(ctx, k, dev["face"], dev[a], dev[b] if b else None, **props)
     o = orc.PartStream(k, cpu["face"], cpu[a], cpu[b] if b else None, **{names[n]: v for n, v in props.items()})
     return g, o
-
-
-def _scene(W, H, n, seed, two_faces=False):
-    from nubovca import synth
-    frames = []
-    s = int(H * 0.5)
-    for i in range(n):
-        faces = [] if i % 6 == 4 else [(W // 5 + 5 * i, H // 5, s)]
-        if two_faces and faces:
-            faces.append((W // 2 + 30, H // 3 + 3 * i, int(s * 0.7)))
-        frames.append(synth.make_bgr(W, H, seed + i, "natural", faces))
-    return frames
 
 
 @pytest.mark.parametrize("kind", ["eye", "nose", "mouth", "ear"])
