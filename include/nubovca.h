@@ -64,8 +64,9 @@ typedef struct nvca_rect { int x, y, w, h; } nvca_rect;
 
 typedef struct nvca_frame {
     const void *data;     /* packed rows, BGR (3 B/px) or BGRA (4 B/px); frames of a
-                             4:2:0 face stream (nvca_face_stream_set_input): the
-                             buffer base the stream's plane offsets count from      */
+                             4:2:0 stream (nvca_face_stream_set_input, nvca_part_stream_set_input,
+                             nvca_tracker_set_input): the buffer base the stream's
+                             plane offsets count from                                */
     int width, height;    /* (4:2:0 streams: the luma size)                          */
     int stride;           /* bytes per row; the reference assumes align4(width*bpp),
                              FACE/kmsfacedetect.cpp:300-305 (4:2:0 streams: the
@@ -74,7 +75,7 @@ typedef struct nvca_frame {
     uint64_t pts;
 } nvca_frame;
 
-/* Pixel format of a face stream's frames (a property of the stream, as caps are in GStreamer; the plane table mirrors
+/* Pixel format of a stream's frames (a property of the stream, as caps are in GStreamer; the plane table mirrors
  * GstVideoInfo's offset[] / stride[]).  4:2:0 frames are what decoders emit: a stream that takes them stands for the
  * videoconvert in front of the element plus the element, cv::cvtColor(CV_YUV2BGR_NV12 / CV_YUV2BGR_I420) in front of
  * FACE/kmsfacedetect.cpp:805 (SURVEY.md A.13 states the arithmetic). */
@@ -326,6 +327,16 @@ int  nvca_part_stream_create(nvca_ctx *ctx, const nvca_part_params *params, cons
                              const nvca_cascade *a, const nvca_cascade *b, nvca_part_stream **out);
 void nvca_part_stream_destroy(nvca_part_stream *s);
 int  nvca_part_stream_set_params(nvca_part_stream *s, const nvca_part_params *params);
+/* The pixel format of the stream's frames, as nvca_face_stream_set_input: NV12 / I420 frames are converted where the working-image
+ * kernels read them -- cv::cvtColor(CV_YUV2BGR_NV12 / _I420) in front of the element's own order, cvtColor then resize then
+ * equalizeHist (NOSE/kmsnosedetect.cpp:836-841, MOUTH/kmsmouthdetect.cpp:842-847, EAR/kmseardetect.cpp:787-792; EYE/kmseyedetect.cpp:948-956:
+ * the full-size gray image is equalized first).  Results are those of the same stream fed the converted BGR frame, bit for bit;
+ * boxes and pushed faces stay in original-frame pixels.  layout == NULL or format NVCA_PIX_BGR: back to packed BGR.  The layout holds
+ * from the next nvca_part_stream_process / nvca_part_batch_process / _submit on; a submitted ticket keeps the layout it was submitted
+ * with.  Packed, NV12 and I420 streams mix in one call; streams share a frame's upload and work only when the layout is equal too.
+ * A frame of a 4:2:0 stream is refused with NVCA_ERR_ARG -- the whole call, before any stream's frame gate advances -- when its
+ * width or height is odd, its stride is not the layout's stride[0], a plane's stride is shorter than its row, or planes overlap. */
+int  nvca_part_stream_set_input(nvca_part_stream *s, const nvca_pixel_layout *layout);
 /* one upstream "message" worth of faces, original-frame pixels (EYE/kmseyedetect.cpp:680-764) */
 int  nvca_part_stream_push_faces(nvca_part_stream *s, const nvca_rect *faces, int n);
 /* the face list the last processed frame worked with (working-image pixels of the face pass, or the pushed
@@ -379,6 +390,14 @@ void nvca_tracker_params_default(nvca_tracker_params *p);
 int  nvca_tracker_create(nvca_ctx *ctx, const nvca_tracker_params *params, nvca_tracker **out);
 void nvca_tracker_destroy(nvca_tracker *t);
 int  nvca_tracker_set_params(nvca_tracker *t, const nvca_tracker_params *params);
+/* The pixel format of the tracker's frames, as nvca_face_stream_set_input: NV12 / I420 frames are converted inside the pixel
+ * pass -- cv::cvtColor(CV_YUV2BGR_NV12 / _I420) in front of the cvtColor of TRK/gstnubotracker.cpp:356 -- and the boxes are those of
+ * the same tracker fed the converted frame as BGRA, bit for bit.  layout == NULL or format NVCA_PIX_BGR: back to packed BGRA.
+ * nvca_frame.stride is the luma stride (stride >= width * 4 is asked of packed trackers only).  Previous gray image and motion
+ * history persist across a format change at the same size.  Packed, NV12 and I420 trackers mix in one nvca_tracker_batch_process
+ * (one launch set per size and format).  A bad frame (odd width or height, a stride that is not the layout's stride[0], a plane
+ * stride shorter than its row, overlapping planes) refuses the whole call with NVCA_ERR_ARG before any tracker's state advances. */
+int  nvca_tracker_set_input(nvca_tracker *t, const nvca_pixel_layout *layout);
 /* timestamp_ms: the reference passes 1000*clock()/CLOCKS_PER_SEC (:349) */
 int  nvca_tracker_process(nvca_tracker *t, const nvca_frame *frame_bgra, double timestamp_ms,
                           nvca_rect *out, int cap, int *n_out);

@@ -156,7 +156,7 @@ struct PyrLevelDev {
 
 // ---- tracker (kernels_tracker.hip) ----
 struct TrkSlot {                // per tracker in the batch
-    const uint8_t *src;         // BGRA frame
+    const uint8_t *src;         // BGRA frame; 4:2:0 trackers (nvca_tracker_set_input): the base `yuv`'s plane offsets count from
     uint8_t *prev;              // previous gray  [h][w]
     float *mhi;                 // motion history [h][w]
     float ts, delbound;         // (float)timestamp, (float)(timestamp - duration)
@@ -166,6 +166,7 @@ struct TrkSlot {                // per tracker in the batch
     int sstride;
     int min_area;               // __join_objects drops boxes outside (min_area, max_area) before anything else:
     long long max_area;         // k_ccl_collect does not even report them
+    YuvPlanes yuv;              // planes of a 4:2:0 frame (the luma stride is sstride); unused by the packed kernels
 };
 struct CompAcc { int minx, miny, maxx, maxy, seed, pad; };   // per root, stored at the root's pixel index
 inline size_t tracker_count_offset(int w, int h, int batch) { return ((size_t)((w + 255) / 256) * h * batch + 63) & ~(size_t)63; }

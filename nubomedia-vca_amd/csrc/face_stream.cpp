@@ -33,13 +33,6 @@ struct FrameWork {
     std::vector<nvca_rect> det;
 };
 
-bool same_layout(const nvca_pixel_layout &a, const nvca_pixel_layout &b)
-{
-    if (a.format != b.format) return false;
-    for (int p = 0; p < 3; p++) if (a.offset[p] != b.offset[p] || a.stride[p] != b.stride[p]) return false;
-    return true;
-}
-
 // the frame gating of kms_face_detect_process_frame (:794-803, :829-830); independent of detection results
 bool face_gate(nvca_face_stream *s)
 {
@@ -94,15 +87,7 @@ int nvca_face_stream_set_input(nvca_face_stream *s, const nvca_pixel_layout *lay
 try {
     if (!s) return NVCA_ERR_ARG;
     nvca_pixel_layout in{};
-    if (layout && layout->format != NVCA_PIX_BGR) {
-        if (layout->format != NVCA_PIX_NV12 && layout->format != NVCA_PIX_I420) { s->ctx->set_error("pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420"); return NVCA_ERR_ARG; }
-        const int np = layout->format == NVCA_PIX_NV12 ? 2 : 3;
-        in.format = layout->format;
-        for (int p = 0; p < np; p++) {           // what the format does not use stays zero: layouts compare by value
-            if (layout->stride[p] <= 0) { s->ctx->set_error("pixel layout: plane strides must be positive"); return NVCA_ERR_ARG; }
-            in.offset[p] = layout->offset[p]; in.stride[p] = layout->stride[p];
-        }
-    }
+    if (int rc = parse_pixel_layout(s->ctx, layout, in)) return rc;
     s->input = in;                               // frames of a batch in flight keep the layout they were submitted with (its plan holds it)
     return NVCA_OK;
 }
@@ -167,9 +152,7 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
         const nvca_frame &f = frames[i];
         if (!s || s->ctx != ctx) return NVCA_ERR_ARG;
         if (const nvca_pixel_layout *yuv = s->yuv()) {
-            if (!f.data || (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
-            if (check_yuv_layout(ctx, *yuv, f.width, f.height)) return NVCA_ERR_ARG;
-            if (f.stride != yuv->stride[0]) { ctx->set_error("4:2:0 frame: its stride is not the stride[0] of the stream's layout"); return NVCA_ERR_ARG; }
+            if (check_yuv_frame(ctx, *yuv, f)) return NVCA_ERR_ARG;
         } else if (check_img(ctx, f.data, f.width, f.height, f.stride, 3, f.mem)) return NVCA_ERR_ARG;
         if (s->p.width_to_process <= 0) { ctx->set_error("width-to-process must be > 0"); return NVCA_ERR_ARG; }
     }

@@ -233,6 +233,44 @@ int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h)
         }
     return NVCA_OK;
 }
+// nvca_*_set_input: the caller's layout, validated, as the stream keeps it (null / NVCA_PIX_BGR: packed frames).  What the format
+// does not use stays zero: layouts compare by value.
+int parse_pixel_layout(nvca_ctx *ctx, const nvca_pixel_layout *layout, nvca_pixel_layout &out)
+{
+    nvca_pixel_layout in{};
+    if (layout && layout->format != NVCA_PIX_BGR) {
+        if (layout->format != NVCA_PIX_NV12 && layout->format != NVCA_PIX_I420) { ctx->set_error("pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420"); return NVCA_ERR_ARG; }
+        in.format = layout->format;
+        for (int p = 0; p < yuv_planes_of(*layout); p++) {
+            if (layout->stride[p] <= 0) { ctx->set_error("pixel layout: plane strides must be positive"); return NVCA_ERR_ARG; }
+            in.offset[p] = layout->offset[p]; in.stride[p] = layout->stride[p];
+        }
+    }
+    out = in;
+    return NVCA_OK;
+}
+bool same_layout(const nvca_pixel_layout &a, const nvca_pixel_layout &b)
+{
+    if (a.format != b.format) return false;
+    for (int p = 0; p < 3; p++) if (a.offset[p] != b.offset[p] || a.stride[p] != b.stride[p]) return false;
+    return true;
+}
+// a frame of a 4:2:0 stream against the stream's layout
+int check_yuv_frame(nvca_ctx *ctx, const nvca_pixel_layout &l, const nvca_frame &f)
+{
+    if (!f.data || (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+    if (check_yuv_layout(ctx, l, f.width, f.height)) return NVCA_ERR_ARG;
+    if (f.stride != l.stride[0]) { ctx->set_error("4:2:0 frame: its stride is not the stride[0] of the stream's layout"); return NVCA_ERR_ARG; }
+    return NVCA_OK;
+}
+// a host 4:2:0 frame to device memory, plane by plane, each at the caller's offset (gaps between planes are not copied); `dst` holds
+// yuv_extent() bytes
+int caller_h2d_planes(nvca_ctx *ctx, void *dst, const void *src, const nvca_pixel_layout &l, int w, int h, hipStream_t st)
+{
+    for (int p = 0; p < yuv_planes_of(l); p++)
+        if (int rc = caller_h2d(ctx, (uint8_t *)dst + l.offset[p], (const uint8_t *)src + l.offset[p], yuv_plane_bytes(l, p, w, h), st)) return rc;
+    return NVCA_OK;
+}
 YuvPlanes yuv_planes(const nvca_pixel_layout *l)
 {
     YuvPlanes p{};
@@ -313,13 +351,14 @@ int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n,
             uint8_t *d = ws.res[ws.cur_res].staging.as<uint8_t>() + off;
             int rc;
             if (yuv) {
-                // plane by plane, each at the caller's offset: the luma rows the resize reads and exactly the chroma rows those use
-                for (int p = 0; p < yuv_planes_of(*yuv); p++) {
+                // plane by plane, each at the caller's offset: whole planes (the staging every 4:2:0 element shares), or the luma rows
+                // the resize reads and exactly the chroma rows those use
+                if (!rows) { if ((rc = caller_h2d_planes(ctx, d, f.data, *yuv, f.width, f.height, st))) return rc; }
+                else for (int p = 0; p < yuv_planes_of(*yuv); p++) {
                     uint8_t *dp = d + yuv->offset[p];
                     const uint8_t *sp = (const uint8_t *)f.data + yuv->offset[p];
                     const size_t stride = (size_t)yuv->stride[p], rb = yuv_plane_row_bytes(*yuv, p, f.width), pr = yuv_plane_rows(p, f.height);
-                    if (!rows) rc = caller_h2d(ctx, dp, sp, yuv_plane_bytes(*yuv, p, f.width, f.height), st);
-                    else if (p == 0) rc = copy_row_runs(ctx, dp, sp, stride, rb, pr, (size_t)rows->first, (size_t)rows->period, (size_t)rows->run, (size_t)rows->count, st);
+                    if (p == 0) rc = copy_row_runs(ctx, dp, sp, stride, rb, pr, (size_t)rows->first, (size_t)rows->period, (size_t)rows->run, (size_t)rows->count, st);
                     else rc = copy_chroma_runs(ctx, dp, sp, stride, rb, pr, *rows, st);
                     if (rc) return rc;
                 }
@@ -352,12 +391,17 @@ bool frames_aligned4(const nvca_frame *frames, const int *idx, int n)
 }
 
 // 4:2:0 frames of one layout: every plane and stride takes k_gray_yuv16's loads (staged host frames start on 256 bytes)
-bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l)
+bool yuv_layout_aligned16(const nvca_pixel_layout &l)
 {
     const bool nv12 = l.format == NVCA_PIX_NV12;
     const size_t cmask = nv12 ? 15 : 7;
     if ((l.offset[0] & 15) || (l.stride[0] & 15) || (l.offset[1] & cmask) || ((size_t)l.stride[1] & cmask)) return false;
     if (!nv12 && ((l.offset[2] & 7) || (l.stride[2] & 7))) return false;
+    return true;
+}
+bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l)
+{
+    if (!yuv_layout_aligned16(l)) return false;
     for (int i = 0; i < n; i++) {
         const nvca_frame &f = frames[idx ? idx[i] : i];
         if (f.mem == NVCA_MEM_DEVICE && ((uintptr_t)f.data & 15)) return false;

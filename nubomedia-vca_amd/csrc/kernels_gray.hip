@@ -4,13 +4,9 @@
 // HBM-bound streaming work.
 #include "launch.h"
 #include "pre_device.h"
+#include "yuv_device.h"
 
 namespace nvca {
-
-__device__ __forceinline__ int gray_of(int b, int g, int r)
-{   // RGB2Gray<uchar>: B2Y 1868, G2Y 9617, R2Y 4899, shift 14, rounding 1<<13
-    return (b * 1868 + g * 9617 + r * 4899 + 8192) >> 14;
-}
 
 // ---- K1 generic: one output pixel per thread, any resize mode, any alignment.
 // mode 0 identity, 1 bilinear (fixed point, 11-bit coefficients), 2 area 2x2.
@@ -147,34 +143,7 @@ void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, 
 // ---- 4:2:0 sources (NV12 / I420 face streams, nvca_yuv420_to_bgr): cv::cvtColor(CV_YUV2BGR_NV12 / _I420) in front of
 // FACE/kmsfacedetect.cpp:805, computed where the frame is read.  OpenCV 2.4 color.cpp, BT.601 limited range, shift 20:
 // pixel (x, y) takes the chroma sample (x >> 1, y >> 1); all int32, the shift arithmetic.
-struct ChromaTerm { int r, g, b; };                      // what a chroma sample adds to every pixel of its 2 x 2 block, rounding included
-__device__ __forceinline__ ChromaTerm chroma_term(int U, int V)
-{
-    const int u = U - 128, v = V - 128;
-    ChromaTerm c;
-    c.r = (1 << 19) + 1673527 * v;
-    c.g = (1 << 19) - 852492 * v - 409993 * u;
-    c.b = (1 << 19) + 2116026 * u;
-    return c;
-}
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-__device__ __forceinline__ void yuv_bgr(int Y, const ChromaTerm &c, int &B, int &G, int &R)
-{
-    const int y = (Y > 16 ? Y - 16 : 0) * 1220542;
-    B = sat8((y + c.b) >> 20); G = sat8((y + c.g) >> 20); R = sat8((y + c.r) >> 20);
-}
-__device__ __forceinline__ int yuv_gray(int Y, const ChromaTerm &c)
-{
-    int B, G, R;
-    yuv_bgr(Y, c, B, G, R);
-    return gray_of(B, G, R);
-}
-template <int FMT>
-__device__ __forceinline__ ChromaTerm chroma_at(const uint8_t *__restrict__ src, const YuvPlanes &p, int cx, int cy)
-{
-    if (FMT == 1) { const uint8_t *c = src + p.off_u + (size_t)cy * p.cstride + 2 * cx; return chroma_term(c[0], c[1]); }
-    return chroma_term(src[p.off_u + (size_t)cy * p.cstride + cx], src[p.off_v + (size_t)cy * p.vstride + cx]);
-}
+// (the arithmetic: yuv_device.h)
 
 // ---- K1 for 4:2:0 frames at full resolution, beside k_gray_fast4: a thread owns 16 pixels of two rows -- the block one row of
 // chroma samples serves -- and reads them with one 16-byte load per luma row and 16 bytes of chroma (NV12: 8 U,V pairs; I420: 8
@@ -465,12 +434,14 @@ void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstr
 }
 
 // ---- working images of the part detectors, all frames of a batched call in one launch: image z of the launch is
-// resize(gray(frame z)) (BGR = true: the gray value of a source pixel is computed where the resize reads it -- cvtColor then
-// resize, EYE/kmseyedetect.cpp:948-956, NOSE/kmsnosedetect.cpp:836-841 -- without writing the full-size gray image) or
-// resize(lut[gray z]) (the eye detector equalizes the full-size gray image first, EYE :950), plus its histogram.
-template <bool BGR>
+// resize(gray(frame z)) (SRC = kWorkBgr: the gray value of a source pixel is computed where the resize reads it -- cvtColor then
+// resize, EYE/kmseyedetect.cpp:948-956, NOSE/kmsnosedetect.cpp:836-841 -- without writing the full-size gray image; kWorkNv12 /
+// kWorkI420: the same with cv::cvtColor(CV_YUV2BGR_NV12 / _I420) in front, tap (r, c) = yuv_gray(Y[r][c], chroma(c >> 1, r >> 1))) or
+// resize(lut[gray z]) (kWorkGray: the eye detector equalizes the full-size gray image first, EYE :950), plus its histogram.
+enum { kWorkGray = 0, kWorkBgr = 1, kWorkNv12 = 2, kWorkI420 = 3 };
+template <int SRC>
 __global__ __launch_bounds__(256) void k_work_resize(
-    const uint8_t *const *__restrict__ srcs, const int *__restrict__ lut_idx, const uint8_t *__restrict__ luts,
+    const uint8_t *const *__restrict__ srcs, const int *__restrict__ lut_idx, const uint8_t *__restrict__ luts, YuvPlanes yp,
     int sh, int sstride, int mode, const int *__restrict__ xofs, const short *__restrict__ ialpha,
     const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
     uint8_t *__restrict__ dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *__restrict__ hist)
@@ -480,7 +451,7 @@ __global__ __launch_bounds__(256) void k_work_resize(
     const int tid = threadIdx.x, wave = tid >> 6, z = blockIdx.z;
     for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
     const uint8_t *__restrict__ src = srcs[z];
-    const bool use_lut = !BGR && lut_idx != nullptr;
+    const bool use_lut = SRC == kWorkGray && lut_idx != nullptr;
     if (use_lut) sl[tid] = luts[(size_t)lut_idx[z] * 256 + tid];
     __syncthreads();
     dst += (size_t)z * dst_slot;
@@ -490,8 +461,11 @@ __global__ __launch_bounds__(256) void k_work_resize(
         if (y >= dh) break;
         if (x < dw) {
             int v;
-            if (BGR) v = resize1_sample([&](int r, int c) { const uint8_t *p = src + (size_t)r * sstride + (size_t)c * 3; return gray_of(p[0], p[1], p[2]); },
-                                        sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            if (SRC == kWorkBgr) v = resize1_sample([&](int r, int c) { const uint8_t *p = src + (size_t)r * sstride + (size_t)c * 3; return gray_of(p[0], p[1], p[2]); },
+                                                    sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            else if (SRC == kWorkNv12 || SRC == kWorkI420)
+                v = resize1_sample([&](int r, int c) { return yuv_gray(src[yp.off_y + (size_t)r * sstride + c], chroma_at<SRC == kWorkNv12 ? 1 : 2>(src, yp, c >> 1, r >> 1)); },
+                                   sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
             else if (use_lut) v = resize1_sample([&](int r, int c) { return (int)sl[src[(size_t)r * sstride + c]]; }, sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
             else v = resize1_value(src, sh, sstride, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
             dst[(size_t)y * dstride + x] = (uint8_t)v;
@@ -500,15 +474,20 @@ __global__ __launch_bounds__(256) void k_work_resize(
     }
     if (hist) hist_flush(lh, hist + (size_t)z * 256, tid);
 }
+// yuv: planes of the frames' 4:2:0 layout (fmt 0 / null: `bgr` says whether the sources are packed BGR frames or gray images)
 void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, const int *d_lut_idx, const uint8_t *d_luts, int sh, int sstride,
                         int mode, const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
-                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch)
+                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch, const YuvPlanes *yuv)
 {
     dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, batch);
-    if (bgr) NVCA_LAUNCH(k_work_resize<true>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax,
-                         dst, dw, dh, dstride, dst_slot, hist);
-    else NVCA_LAUNCH(k_work_resize<false>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax,
-                     dst, dw, dh, dstride, dst_slot, hist);
+    const YuvPlanes yp = yuv ? *yuv : YuvPlanes{};
+#define NVCA_WORK_RESIZE(SRC) NVCA_LAUNCH(k_work_resize<SRC>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, yp, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax, \
+                                          dst, dw, dh, dstride, dst_slot, hist)
+    if (yp.fmt == 1) NVCA_WORK_RESIZE(kWorkNv12);
+    else if (yp.fmt == 2) NVCA_WORK_RESIZE(kWorkI420);
+    else if (bgr) NVCA_WORK_RESIZE(kWorkBgr);
+    else NVCA_WORK_RESIZE(kWorkGray);
+#undef NVCA_WORK_RESIZE
 }
 
 // ---- CV_HAAR_SCALE_IMAGE pyramids: every level of every image in one launch (k_pyr_integral, kernels_integral.hip, takes them from here)

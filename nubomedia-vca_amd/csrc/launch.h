@@ -54,7 +54,7 @@ void launch_apply_lut(hipStream_t st, const uint8_t *src, int w, int h, int spit
                       uint8_t *dst, int dpitch, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0);
 void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, const int *d_lut_idx, const uint8_t *d_luts, int sh, int sstride,
                         int mode, const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
-                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch);
+                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch, const YuvPlanes *yuv = nullptr);
 void launch_colsum(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g,
                    unsigned *bandsum, unsigned *bandsq, int batch);
 void launch_bandscan(hipStream_t st, const PreGeom &g, unsigned *bandsum, unsigned *bandsq, int batch);
@@ -73,7 +73,9 @@ void launch_small_integral(hipStream_t st, const uint8_t *gray, const uint8_t *l
 // component kernels leave the other segments alone (a static scene with a few moving objects is mostly such segments)
 // roots: [0] = tile roots listed, [1] = the list overflowed, then one entry (slot * w * h + pixel) per tile root; mode: 0 folded component
 // path, 1 per-pixel component kernels, 2 the latter without the pixel pass (fallback behind an overflow of mode 0's list)
-void launch_tracker(hipStream_t st, const void *d_slots, int batch, int w, int h, bool vec4, int *labels, void *acc,
+// fmt: 0 BGRA frames (vec4: every frame takes k_trk_pixel4's 16-byte loads), 1 / 2: NV12 / I420 frames, planes per slot (vec4: every plane
+// and stride takes the wide kernel's loads and w % 4 == 0)
+void launch_tracker(hipStream_t st, const void *d_slots, int batch, int w, int h, int fmt, bool vec4, int *labels, void *acc,
                     int *out, int cap, bool run_ccl, uint8_t *flags, int order /* Switches::trk_order */, int *roots, int roots_cap, int mode, int *tiles, int tick);
 
 // One launch per kernel; each is a no-op when the plan has no work for its kernel (no tasks, no tiles / bands / strips, no late stage).

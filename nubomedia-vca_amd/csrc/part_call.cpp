@@ -30,16 +30,16 @@ static constexpr int kCallLanes = 3;                      // lanes of one call: 
 // lanes 1 .. 3 / 4 .. 6; calls with several streams stay off lane 0, where a face detector's batch may be in flight
 int lane_base(const PartCall &c) { return c.parity ? 1 + kCallLanes : 1; }
 
-// the frame group of frame f
-int frame_group(PartCall &c, const nvca_frame &f)
+// the frame group of frame f, handed to a stream of this layout
+int frame_group(PartCall &c, const nvca_frame &f, const nvca_pixel_layout &layout)
 {
     for (size_t gi = 0; gi < c.groups.size(); gi++) {
         const FrameGroup &fg = c.groups[gi];
-        if (fg.data == f.data && fg.w == f.width && fg.h == f.height && fg.stride == f.stride && fg.mem == f.mem) return (int)gi;
+        if (fg.data == f.data && fg.w == f.width && fg.h == f.height && fg.stride == f.stride && fg.mem == f.mem && same_layout(fg.layout, layout)) return (int)gi;
     }
     c.groups.emplace_back();
     FrameGroup &fg = c.groups.back();
-    fg.data = f.data; fg.w = f.width; fg.h = f.height; fg.stride = f.stride; fg.mem = f.mem;
+    fg.data = f.data; fg.w = f.width; fg.h = f.height; fg.stride = f.stride; fg.mem = f.mem; fg.layout = layout;
     return (int)c.groups.size() - 1;
 }
 // image k of the batch of (frame geometry, size, chain): asked for by frame group gi
@@ -50,12 +50,15 @@ ImageRef request_image(PartCall &c, int gi, int dw, int dh, bool eye, bool post_
     ImageRef r;
     for (size_t bi = 0; bi < batches.size() && r.batch < 0; bi++) {
         const ImageBatch &b = batches[bi];
-        if (b.W == fg.w && b.H == fg.h && b.stride == fg.stride && b.dw == dw && b.dh == dh && b.eye == eye && b.post_eq == post_eq) r.batch = (int)bi;
+        // the eye chain's images are read from the full-size gray images (pitch W), not from the frames: packed, NV12 and I420 frames
+        // of one size share a batch whatever their strides and layouts
+        const bool same_source = eye || (b.stride == fg.stride && same_layout(b.layout, fg.layout));
+        if (b.W == fg.w && b.H == fg.h && same_source && b.dw == dw && b.dh == dh && b.eye == eye && b.post_eq == post_eq) r.batch = (int)bi;
     }
     if (r.batch < 0) {
         batches.emplace_back();
         ImageBatch &b = batches.back();
-        b.W = fg.w; b.H = fg.h; b.stride = fg.stride; b.dw = dw; b.dh = dh; b.eye = eye; b.post_eq = post_eq;
+        b.W = fg.w; b.H = fg.h; b.stride = fg.stride; b.layout = fg.layout; b.dw = dw; b.dh = dh; b.eye = eye; b.post_eq = post_eq;
         r.batch = (int)batches.size() - 1;
     }
     ImageBatch &b = batches[r.batch];
@@ -91,8 +94,9 @@ int part_front(nvca_ctx *ctx, PartCall &c, int n, nvca_part_stream *const *strea
     if (n < 0 || (n > 0 && (!streams || !frames))) return NVCA_ERR_ARG;
     for (int i = 0; i < n; i++) {
         const nvca_part_stream *s = streams[i]; const nvca_frame *f = &frames[i];
-        if (!s || s->ctx != ctx || !f->data || f->width <= 0 || f->height <= 0 || f->stride < f->width * 3 || s->p.width_to_process <= 0 ||
-            (f->mem != NVCA_MEM_HOST && f->mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+        if (!s || s->ctx != ctx || s->p.width_to_process <= 0) return NVCA_ERR_ARG;
+        if (const nvca_pixel_layout *yuv = s->yuv()) { if (check_yuv_frame(ctx, *yuv, *f)) return NVCA_ERR_ARG; }
+        else if (!f->data || f->width <= 0 || f->height <= 0 || f->stride < f->width * 3 || (f->mem != NVCA_MEM_HOST && f->mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
         for (int j = 0; j < i; j++) if (streams[j] == s) { ctx->set_error("a part stream may appear once per batch"); return NVCA_ERR_ARG; }
         // every frame is validated before any stream's gate advances: a refused call leaves all streams as they were
         PartScales sc;
@@ -117,7 +121,7 @@ int part_front(nvca_ctx *ctx, PartCall &c, int n, nvca_part_stream *const *strea
         const PartFrame &g = w.gate = part_gate(s->st, s->p);
         if (g.popped) c.snaps[i].note_popped(s->st);
         if (!g.run) continue;
-        w.group = frame_group(c, *f);
+        w.group = frame_group(c, *f, s->input);
         w.lane = n > 1 ? base + w.group % kCallLanes : 0;          // the part searches of one frame's streams share a lane
         // the images this stream works on: requested here, computed below for all streams at once
         if (g.eye_chain && c.groups[w.group].eye_index < 0) c.groups[w.group].eye_index = c.n_eye++;

@@ -11,6 +11,8 @@ struct nvca_part_stream {
     nvca_part_params p;
     const nvca_cascade *face, *a, *b;
     nvca::PartState st;
+    nvca_pixel_layout input{};        // format NVCA_PIX_BGR: packed BGR frames; else the planes of its 4:2:0 frames (nvca_part_stream_set_input)
+    const nvca_pixel_layout *yuv() const { return input.format != NVCA_PIX_BGR ? &input : nullptr; }
 };
 
 namespace nvca {
@@ -21,13 +23,16 @@ namespace nvca {
 // face pass of one kind over those images is one job.  Same arithmetic on the same bytes: the results are those of per-stream calls.
 struct FrameGroup {
     const void *data = nullptr; int w = 0, h = 0, stride = 0, mem = 0;
-    const void *bgr = nullptr;               // device BGR (the caller's, or the one upload of a host frame)
+    nvca_pixel_layout layout{};              // of the streams that were handed the frame (format NVCA_PIX_BGR: a packed frame); a call keeps the layouts it was submitted with
+    const nvca_pixel_layout *yuv() const { return layout.format != NVCA_PIX_BGR ? &layout : nullptr; }
+    const void *bgr = nullptr;               // the frame on the device (the caller's, or the one upload of a host frame): packed BGR, or the base of its planes
     int eye_index = -1;                      // an eye detector looks at it: index of its full-size gray image / LUT
     size_t upload_at = 0, gray_at = 0;       // arena offsets
 };
 struct ImageRef { int batch = -1, k = 0; };
 struct ImageBatch {                          // the working images [equalizeHist](resize(gray or equalized gray)) of one size
     int W = 0, H = 0, stride = 0, dw = 0, dh = 0; bool eye = false, post_eq = true, flips = false;
+    nvca_pixel_layout layout{};              // of the source frames (one launch set reads planes of one layout)
     std::vector<int> members;                // frame groups, image k belongs to members[k]
     size_t at = 0, slot = 0; uint8_t *base = nullptr;        // image k at base + k * slot (pitch dw), its mirror image at base + (count + k) * slot
     const uint8_t *image(int k, bool mirrored = false) const { return base + slot * ((mirrored ? members.size() : 0) + k); }

@@ -27,6 +27,7 @@ namespace {
 // computed on the fly (cvtColor then resize); gray sources go through LUT lut_idx[k] of `luts` first when lut_idx is given
 struct PartImageBatch {
     bool bgr = true, post_eq = true;
+    YuvPlanes yuv{};                             // fmt 1 / 2: the sources are 4:2:0 frames of these planes (cvtColor(YUV2BGR), cvtColor, resize)
     int sw = 0, sh = 0, sstride = 0, dw = 0, dh = 0;
     std::vector<const void *> src; std::vector<int> lut_idx;
     uint8_t *dst = nullptr; size_t slot = 0;
@@ -48,17 +49,26 @@ int part_luts(nvca_ctx *ctx, int n_keep, int n_scratch, uint8_t **keep)
     *keep = pw.luts.as<uint8_t>();
     return NVCA_OK;
 }
-int part_gray_eq(nvca_ctx *ctx, const void *const *bgr, int n, int w, int h, int stride, uint8_t *gray, size_t slot, uint8_t *luts)
+int part_gray_eq(nvca_ctx *ctx, const void *const *bgr, int n, int w, int h, int stride, const nvca_pixel_layout *yuv, uint8_t *gray, size_t slot, uint8_t *luts)
 {
     int rc;
     void *d_ptrs = nullptr;
     if ((rc = part_table(ctx, bgr, (size_t)n * sizeof(void *), &d_ptrs))) return rc;
-    PreGeom g; make_geom(g, w, h, stride, 3, w, h);
+    PreGeom g; make_geom(g, w, h, stride, yuv ? 1 : 3, w, h);
     g.gpitch = w; g.gray_slot = slot;
-    bool aligned = stride % 4 == 0 && w % 4 == 0 && slot % 4 == 0 && ((uintptr_t)gray & 3) == 0;
-    for (int k = 0; k < n; k++) aligned = aligned && ((uintptr_t)bgr[k] & 3) == 0;
     unsigned *hist = ctx->pw().hist.as<unsigned>();
-    { TimedLaunch t(ctx, NVCA_K_GRAY);
+    if (yuv) {
+        // k_gray_yuv16 stores 16 bytes at gray + row * gpitch + x: the image's pitch is its width here, so the width, the slot and the
+        // base must take the stores as the planes take the loads
+        bool wide = yuv_layout_aligned16(*yuv) && w % 16 == 0 && slot % 16 == 0 && ((uintptr_t)gray & 15) == 0;
+        for (int k = 0; k < n; k++) wide = wide && ((uintptr_t)bgr[k] & 15) == 0;
+        TimedLaunch t(ctx, NVCA_K_GRAY);
+        wide = launch_gray_yuv(ctx->cs(), (const uint8_t *const *)d_ptrs, g, yuv_planes(yuv), 0, nullptr, nullptr, nullptr, nullptr, w, gray, hist, n, wide);
+        if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 eye gray of %d frame(s) %d x %d: %s\n", n, w, h, wide ? "k_gray_yuv16" : "k_gray_yuv_generic");
+    } else {
+      bool aligned = stride % 4 == 0 && w % 4 == 0 && slot % 4 == 0 && ((uintptr_t)gray & 3) == 0;
+      for (int k = 0; k < n; k++) aligned = aligned && ((uintptr_t)bgr[k] & 3) == 0;
+      TimedLaunch t(ctx, NVCA_K_GRAY);
       launch_gray(ctx->cs(), (const uint8_t *const *)d_ptrs, g, 0, nullptr, nullptr, nullptr, nullptr, w, gray, hist, n, aligned); }
     { TimedLaunch t(ctx, NVCA_K_LUT); launch_lut(ctx->cs(), hist, w * h, luts, n, 1); }
     NVCA_LAUNCH_CHECK(ctx);
@@ -84,7 +94,7 @@ int part_image_batch(nvca_ctx *ctx, const PartImageBatch &b, const uint8_t *luts
     { TimedLaunch t(ctx, NVCA_K_RESIZE1);
       launch_work_resize(ctx->cs(), b.bgr, (const uint8_t *const *)d_tab, with_lut ? (const int *)((uint8_t *)d_tab + (size_t)n * sizeof(void *)) : nullptr, luts,
                          b.sh, b.sstride, gp->tab.mode, gp->d_xofs.as<int>(), gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(),
-                         gp->tab.xmax, b.dst, b.dw, b.dh, b.dw, b.slot, hist, n); }
+                         gp->tab.xmax, b.dst, b.dw, b.dh, b.dw, b.slot, hist, n, b.yuv.fmt ? &b.yuv : nullptr); }
     if (b.post_eq) {
         { TimedLaunch t(ctx, NVCA_K_LUT); launch_lut(ctx->cs(), hist, b.dw * b.dh, scratch, n, 1); }
         launch_apply_lut(ctx->cs(), b.dst, b.dw, b.dh, b.dw, scratch, b.dst, b.dw, n, b.slot, b.slot);
@@ -108,7 +118,7 @@ int part_images(nvca_ctx *ctx, std::vector<FrameGroup> &groups, std::vector<Imag
     int rc;
     size_t need = 0;
     auto carve = [&](size_t bytes) { const size_t at = need; need += (bytes + 255) & ~(size_t)255; return at; };
-    for (FrameGroup &fg : groups) if (fg.mem == NVCA_MEM_HOST) fg.upload_at = carve((size_t)fg.stride * fg.h);
+    for (FrameGroup &fg : groups) if (fg.mem == NVCA_MEM_HOST) fg.upload_at = carve(fg.yuv() ? yuv_extent(fg.layout, fg.w, fg.h) : (size_t)fg.stride * fg.h);
     for (int e = 0; e < n_eye; e++)              // in LUT order: frames of one geometry then sit at equal distances
         for (FrameGroup &fg : groups) if (fg.eye_index == e) fg.gray_at = carve((size_t)fg.w * fg.h);
     for (ImageBatch &b : batches) { b.slot = ((size_t)b.dw * b.dh + 255) & ~(size_t)255; b.at = carve(b.slot * b.members.size() * (b.flips ? 2 : 1)); }
@@ -120,7 +130,9 @@ int part_images(nvca_ctx *ctx, std::vector<FrameGroup> &groups, std::vector<Imag
     for (FrameGroup &fg : groups) {
         fg.bgr = fg.data;
         if (fg.mem == NVCA_MEM_HOST) {
-            if ((rc = caller_h2d(ctx, arena + fg.upload_at, fg.data, (size_t)fg.stride * (fg.h - 1) + (size_t)fg.w * 3, ctx->cs()))) return rc;
+            if (fg.yuv()) rc = caller_h2d_planes(ctx, arena + fg.upload_at, fg.data, fg.layout, fg.w, fg.h, ctx->cs());      // plane by plane, at the caller's offsets
+            else rc = caller_h2d(ctx, arena + fg.upload_at, fg.data, (size_t)fg.stride * (fg.h - 1) + (size_t)fg.w * 3, ctx->cs());
+            if (rc) return rc;
             fg.bgr = arena + fg.upload_at;
         }
     }
@@ -134,16 +146,17 @@ int part_images(nvca_ctx *ctx, std::vector<FrameGroup> &groups, std::vector<Imag
             const size_t slot = ((size_t)g0.w * g0.h + 255) & ~(size_t)255;
             for (size_t gj = gi; gj < groups.size(); gj++) {
                 const FrameGroup &fg = groups[gj];
-                if (fg.eye_index < 0 || done[gj] || fg.w != g0.w || fg.h != g0.h || fg.stride != g0.stride) continue;
+                if (fg.eye_index < 0 || done[gj] || fg.w != g0.w || fg.h != g0.h || fg.stride != g0.stride || !same_layout(fg.layout, g0.layout)) continue;
                 if (fg.eye_index != g0.eye_index + (int)srcs.size() || fg.gray_at != g0.gray_at + slot * srcs.size()) continue;
                 srcs.push_back(fg.bgr); done[gj] = 1;
             }
-            if ((rc = part_gray_eq(ctx, srcs.data(), (int)srcs.size(), g0.w, g0.h, g0.stride, arena + g0.gray_at, slot, eye_luts + (size_t)g0.eye_index * 256))) return rc;
+            if ((rc = part_gray_eq(ctx, srcs.data(), (int)srcs.size(), g0.w, g0.h, g0.stride, g0.yuv(), arena + g0.gray_at, slot, eye_luts + (size_t)g0.eye_index * 256))) return rc;
         }
     }
     for (ImageBatch &b : batches) {
         PartImageBatch ib;
-        ib.bgr = !b.eye; ib.post_eq = b.post_eq; ib.sw = b.W; ib.sh = b.H; ib.sstride = b.eye ? b.W : b.stride; ib.dw = b.dw; ib.dh = b.dh;
+        ib.bgr = !b.eye; if (!b.eye) ib.yuv = yuv_planes(&b.layout);
+        ib.post_eq = b.post_eq; ib.sw = b.W; ib.sh = b.H; ib.sstride = b.eye ? b.W : b.stride; ib.dw = b.dw; ib.dh = b.dh;
         ib.dst = b.base = arena + b.at; ib.slot = b.slot;
         for (int gi : b.members) {
             const FrameGroup &fg = groups[gi];

@@ -74,6 +74,15 @@ try {
     return NVCA_OK;
 }
 NVCA_API_CATCH((s ? s->ctx : nullptr))
+int nvca_part_stream_set_input(nvca_part_stream *s, const nvca_pixel_layout *layout)
+try {
+    if (!s) return NVCA_ERR_ARG;
+    nvca_pixel_layout in{};
+    if (int rc = parse_pixel_layout(s->ctx, layout, in)) return rc;
+    s->input = in;                    // a submitted call keeps the layout it was submitted with (its frame groups hold it)
+    return NVCA_OK;
+}
+NVCA_API_CATCH((s ? s->ctx : nullptr))
 int nvca_part_stream_push_faces(nvca_part_stream *s, const nvca_rect *faces, int n)
 try {
     if (!s || n < 0 || (n > 0 && !faces)) return NVCA_ERR_ARG;

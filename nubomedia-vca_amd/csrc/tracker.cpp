@@ -2,7 +2,7 @@
 // gst_nubo_tracker_process (TRK/gstnubotracker.cpp:202-237, 339-421).  Per stream the
 // device keeps the previous gray frame and the motion-history image; every frame runs
 // k_trk_pixel + the connected-component kernels, then __join_objects on the host.
-#include "context.h"
+#include "host_state.h"
 #include "host_logic.h"
 #include <chrono>
 #include <algorithm>
@@ -15,6 +15,8 @@ struct nvca_tracker {
     nvca_tracker_params p;
     int w = 0, h = 0, num_frames = 0;
     DevBuf prev, mhi;
+    nvca_pixel_layout input{};        // format NVCA_PIX_BGR: packed BGRA frames; else the planes of its 4:2:0 frames (nvca_tracker_set_input)
+    const nvca_pixel_layout *yuv() const { return input.format != NVCA_PIX_BGR ? &input : nullptr; }
 };
 
 namespace {
@@ -60,6 +62,16 @@ try {
 }
 NVCA_API_CATCH((t ? t->ctx : nullptr))
 
+int nvca_tracker_set_input(nvca_tracker *t, const nvca_pixel_layout *layout)
+try {
+    if (!t) return NVCA_ERR_ARG;
+    nvca_pixel_layout in{};
+    if (int rc = parse_pixel_layout(t->ctx, layout, in)) return rc;
+    t->input = in;                    // previous gray and motion history stay: gray values whatever the source
+    return NVCA_OK;
+}
+NVCA_API_CATCH((t ? t->ctx : nullptr))
+
 int nvca_tracker_batch_process(nvca_ctx *ctx, int n, nvca_tracker *const *trackers, const nvca_frame *frames,
                                const double *ts, nvca_rect *out, int cap, int *n_out)
 try {
@@ -72,8 +84,10 @@ try {
     for (int i = 0; i < n; i++) {
         n_out[i] = 0;
         const nvca_frame &f = frames[i];
-        if (!trackers[i] || trackers[i]->ctx != ctx || !f.data || f.width <= 0 || f.height <= 0 || f.stride < f.width * 4 ||
-            (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+        if (!trackers[i] || trackers[i]->ctx != ctx) return NVCA_ERR_ARG;
+        // every frame is validated before any tracker's state advances: a refused call leaves all of them as they were
+        if (const nvca_pixel_layout *yuv = trackers[i]->yuv()) { if (check_yuv_frame(ctx, *yuv, f)) return NVCA_ERR_ARG; }
+        else if (!f.data || f.width <= 0 || f.height <= 0 || f.stride < f.width * 4 || (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
         for (int j = 0; j < i; j++) if (trackers[j] == trackers[i]) { ctx->set_error("a tracker may appear once per batch"); return NVCA_ERR_ARG; }
     }
     TrkWorkspace &ws = ctx->trk;
@@ -83,9 +97,10 @@ try {
     std::vector<char> done(n, 0);
     for (int i0 = 0; i0 < n; i0++) {
         if (done[i0]) continue;
-        const int W = frames[i0].width, H = frames[i0].height;
+        // one launch set per (size, format): the pixel kernels are instances per format, the planes travel per slot
+        const int W = frames[i0].width, H = frames[i0].height, fmt = trackers[i0]->input.format;
         std::vector<int> idx;
-        for (int j = i0; j < n; j++) if (!done[j] && frames[j].width == W && frames[j].height == H) { idx.push_back(j); done[j] = 1; }
+        for (int j = i0; j < n; j++) if (!done[j] && frames[j].width == W && frames[j].height == H && trackers[j]->input.format == fmt) { idx.push_back(j); done[j] = 1; }
         const int batch = (int)idx.size();
         const size_t N = (size_t)W * H;
         // per-stream state (gst_nubo_tracker_img_conf: MHI re-created zeroed on a size change)
@@ -100,8 +115,18 @@ try {
                 t->w = W; t->h = H;
             }
             const nvca_frame &f = frames[idx[b]];
-            if (f.mem == NVCA_MEM_HOST) stage_bytes += ((size_t)f.stride * H + 255) / 256 * 256;
-            if ((f.stride & 15) || (f.mem == NVCA_MEM_DEVICE && ((uintptr_t)f.data & 15))) vec4 = false;
+            if (const nvca_pixel_layout *yuv = t->yuv()) {
+                if (f.mem == NVCA_MEM_HOST) stage_bytes += round_up(yuv_extent(*yuv, W, H), 256);
+                // k_trk_pixel_yuv8's loads: 8 bytes of luma and of NV12 chroma, 4 bytes of an I420 chroma plane.  A staged host frame
+                // counts as base 0: ws.staging is 256-byte aligned and every staged frame starts on a multiple of 256 bytes in it
+                const uintptr_t base = f.mem == NVCA_MEM_DEVICE ? (uintptr_t)f.data : 0;
+                const size_t cmask = fmt == NVCA_PIX_NV12 ? 7 : 3;
+                if (((base + yuv->offset[0]) & 7) || (yuv->stride[0] & 7) || ((base + yuv->offset[1]) & cmask) || ((size_t)yuv->stride[1] & cmask) ||
+                    (fmt == NVCA_PIX_I420 && (((base + yuv->offset[2]) & 3) || (yuv->stride[2] & 3)))) vec4 = false;
+            } else {
+                if (f.mem == NVCA_MEM_HOST) stage_bytes += ((size_t)f.stride * H + 255) / 256 * 256;
+                if ((f.stride & 15) || (f.mem == NVCA_MEM_DEVICE && ((uintptr_t)f.data & 15))) vec4 = false;
+            }
             if (t->num_frames > 0) any_ccl = true;
         }
         static const int roots_div = [] { const char *e = getenv("NVCA_TRK_ROOTS_DIV"); const int v = e ? atoi(e) : 8; return v >= 1 ? v : 8; }();      // diagnostic: the share of the pixels the root list holds (1 / n)
@@ -127,9 +152,16 @@ try {
             memset(&s, 0, sizeof(s));
             if (f.mem == NVCA_MEM_HOST) {
                 uint8_t *d = ws.staging.as<uint8_t>() + off;
-                if (int rc = caller_h2d(ctx, d, f.data, (size_t)f.stride * (H - 1) + (size_t)W * 4, ctx->cs())) return rc;
-                s.src = d; off += ((size_t)f.stride * H + 255) / 256 * 256;
+                if (const nvca_pixel_layout *yuv = t->yuv()) {
+                    if (int rc = caller_h2d_planes(ctx, d, f.data, *yuv, W, H, ctx->cs())) return rc;
+                    off += round_up(yuv_extent(*yuv, W, H), 256);
+                } else {
+                    if (int rc = caller_h2d(ctx, d, f.data, (size_t)f.stride * (H - 1) + (size_t)W * 4, ctx->cs())) return rc;
+                    off += ((size_t)f.stride * H + 255) / 256 * 256;
+                }
+                s.src = d;
             } else s.src = (const uint8_t *)f.data;
+            s.yuv = yuv_planes(t->yuv());
             s.prev = t->prev.as<uint8_t>(); s.mhi = t->mhi.as<float>();
             const double timestamp = ts[idx[b]];
             s.ts = (float)timestamp; s.delbound = (float)(timestamp - t->p.mhi_duration);    // cvUpdateMotionHistory
@@ -142,8 +174,9 @@ try {
         // kernels' visiting order)
         if (!ctx->sw.trk_fold) NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.flags.as<uint8_t>() + tracker_count_offset(W, H, batch), 0, sizeof(int) * (size_t)batch, ctx->cs()));
         const bool fold = ctx->sw.trk_fold;
+        if (fmt != NVCA_PIX_BGR && ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 tracker pass of %d frame(s) %d x %d: %s\n", batch, W, H, vec4 ? "k_trk_pixel_yuv8" : "k_trk_pixel_yuv");
         { TimedLaunch tl(ctx, NVCA_K_TRACKER);
-          launch_tracker(ctx->cs(), ws.slots.p, batch, W, H, vec4, ws.labels.as<int>(), ws.acc.p, ws.out.as<int>(), kCompCap, any_ccl, ws.flags.as<uint8_t>(), ctx->sw.trk_order,
+          launch_tracker(ctx->cs(), ws.slots.p, batch, W, H, fmt, vec4, ws.labels.as<int>(), ws.acc.p, ws.out.as<int>(), kCompCap, any_ccl, ws.flags.as<uint8_t>(), ctx->sw.trk_order,
                          ws.roots.as<int>(), roots_cap, fold ? 0 : 1, ws.tiles.as<int>(), tick); }
         NVCA_LAUNCH_CHECK(ctx);
         tp1 = std::chrono::steady_clock::now();
@@ -165,7 +198,7 @@ try {
                 NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.out.p, 0, 2 * sizeof(int), ctx->cs()));
                 NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.flags.as<uint8_t>() + tracker_count_offset(W, H, batch), 0, sizeof(int) * (size_t)batch, ctx->cs()));
                 { TimedLaunch tl(ctx, NVCA_K_TRACKER);
-                  launch_tracker(ctx->cs(), ws.slots.p, batch, W, H, vec4, ws.labels.as<int>(), ws.acc.p, ws.out.as<int>(), kCompCap, true, ws.flags.as<uint8_t>(), ctx->sw.trk_order,
+                  launch_tracker(ctx->cs(), ws.slots.p, batch, W, H, fmt, vec4, ws.labels.as<int>(), ws.acc.p, ws.out.as<int>(), kCompCap, true, ws.flags.as<uint8_t>(), ctx->sw.trk_order,
                                  ws.roots.as<int>(), roots_cap, 2, ws.tiles.as<int>(), tick); }
                 NVCA_LAUNCH_CHECK(ctx);
                 NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ho, ws.out.p, sizeof(int) * (2 + 6 * (size_t)first), hipMemcpyDeviceToHost, ctx->cs()));

@@ -1,0 +1,46 @@
+// yuv_device.h -- device-only arithmetic of the 4:2:0 sources, shared by every kernel that reads NV12 / I420 planes
+// (kernels_gray.hip: face streams, the part detectors' working images, nvca_yuv420_to_bgr; kernels_tracker.hip: the pixel pass):
+// cv::cvtColor(CV_YUV2BGR_NV12 / _I420) as OpenCV 2.4 color.cpp computes it, BT.601 limited range, shift 20 -- pixel
+// (x, y) takes the chroma sample (x >> 1, y >> 1); all int32, the shift arithmetic -- and the BGR2GRAY / BGRA2GRAY that follows it.
+#pragma once
+#include "launch.h"
+
+#if defined(__HIPCC__)
+namespace nvca {
+
+__device__ __forceinline__ int gray_of(int b, int g, int r)
+{   // RGB2Gray<uchar>: B2Y 1868, G2Y 9617, R2Y 4899, shift 14, rounding 1<<13
+    return (b * 1868 + g * 9617 + r * 4899 + 8192) >> 14;
+}
+
+struct ChromaTerm { int r, g, b; };                      // what a chroma sample adds to every pixel of its 2 x 2 block, rounding included
+__device__ __forceinline__ ChromaTerm chroma_term(int U, int V)
+{
+    const int u = U - 128, v = V - 128;
+    ChromaTerm c;
+    c.r = (1 << 19) + 1673527 * v;
+    c.g = (1 << 19) - 852492 * v - 409993 * u;
+    c.b = (1 << 19) + 2116026 * u;
+    return c;
+}
+__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+__device__ __forceinline__ void yuv_bgr(int Y, const ChromaTerm &c, int &B, int &G, int &R)
+{
+    const int y = (Y > 16 ? Y - 16 : 0) * 1220542;
+    B = sat8((y + c.b) >> 20); G = sat8((y + c.g) >> 20); R = sat8((y + c.r) >> 20);
+}
+__device__ __forceinline__ int yuv_gray(int Y, const ChromaTerm &c)
+{
+    int B, G, R;
+    yuv_bgr(Y, c, B, G, R);
+    return gray_of(B, G, R);
+}
+template <int FMT>
+__device__ __forceinline__ ChromaTerm chroma_at(const uint8_t *__restrict__ src, const YuvPlanes &p, int cx, int cy)
+{
+    if (FMT == 1) { const uint8_t *c = src + p.off_u + (size_t)cy * p.cstride + 2 * cx; return chroma_term(c[0], c[1]); }
+    return chroma_term(src[p.off_u + (size_t)cy * p.cstride + cx], src[p.off_v + (size_t)cy * p.vstride + cx]);
+}
+
+} // namespace nvca
+#endif

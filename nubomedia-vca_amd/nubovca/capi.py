@@ -97,6 +97,7 @@ SYMBOLS = [
     "nvca_integral_tilted", "nvca_cascade_kind", "nvca_part_batch_process", "nvca_device_count", "nvca_draw_shapes",
     "nvca_cascade_validate_mem", "nvca_abi_selftest", "nvca_ctx_set_option", "nvca_ctx_get_option", "nvca_overlay_blend",
     "nvca_part_batch_submit", "nvca_part_batch_collect", "nvca_face_stream_set_input", "nvca_yuv420_to_bgr",
+    "nvca_part_stream_set_input", "nvca_tracker_set_input",
 ]
 
 _lib = None
@@ -191,6 +192,7 @@ def load():
     L.nvca_tracker_destroy.argtypes = [vp]
     L.nvca_tracker_destroy.restype = None
     L.nvca_tracker_set_params.argtypes = [vp, C.POINTER(TrackerParams)]
+    L.nvca_tracker_set_input.argtypes = [vp, C.POINTER(PixelLayout)]
     L.nvca_tracker_process.argtypes = [vp, C.POINTER(Frame), C.c_double, C.POINTER(Rect), C.c_int, ip]
     L.nvca_tracker_batch_process.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Frame), C.POINTER(C.c_double),
                                              C.POINTER(Rect), C.c_int, ip]
@@ -202,6 +204,7 @@ def load():
     L.nvca_part_stream_destroy.argtypes = [vp]
     L.nvca_part_stream_destroy.restype = None
     L.nvca_part_stream_set_params.argtypes = [vp, C.POINTER(PartParams)]
+    L.nvca_part_stream_set_input.argtypes = [vp, C.POINTER(PixelLayout)]
     L.nvca_part_stream_push_faces.argtypes = [vp, C.POINTER(Rect), C.c_int]
     L.nvca_part_stream_faces.argtypes = [vp, C.POINTER(Rect), C.c_int, ip]
     L.nvca_part_batch_process.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Frame), C.POINTER(Rect), C.c_int, ip, C.POINTER(Rect), C.c_int, ip]
@@ -538,7 +541,7 @@ def make_frame(arr_or_ptr, width=None, height=None, stride=None, mem=MEM_HOST, p
 
 
 def make_planar_frame(buf, width, height, layout, mem=MEM_HOST, pts=0):
-    """Frame of a 4:2:0 stream (FaceStream.set_input): buf is the flat uint8 numpy buffer the layout's offsets count from (host),
+    """Frame of a 4:2:0 stream (FaceStream / PartStream / Tracker .set_input): buf is the flat uint8 numpy buffer the layout's offsets count from (host),
     or a device pointer; width x height is the luma size, the frame's stride the layout's stride[0]."""
     if isinstance(buf, np.ndarray):
         assert buf.dtype == np.uint8 and buf.flags.c_contiguous
@@ -615,6 +618,10 @@ class Tracker:
     def set_property(self, name, value):
         setattr(self.p, self.PROPS[name], value)
         self.ctx.check(self.ctx.L.nvca_tracker_set_params(self.h, C.byref(self.p)))
+
+    def set_input(self, layout=None):
+        """nvca_tracker_set_input: the tracker's frames are 4:2:0 buffers of this PixelLayout from now on (None: packed BGRA)"""
+        self.ctx.check(self.ctx.L.nvca_tracker_set_input(self.h, C.byref(layout) if layout is not None else None))
 
     def process(self, bgra, timestamp_ms, cap=4096):
         return tracker_batch_process(self.ctx, [self], [make_frame(np.ascontiguousarray(bgra, np.uint8))],
@@ -751,6 +758,10 @@ class PartStream:
         for i, r in enumerate(faces):
             buf[i] = Rect(*[int(v) for v in r])
         self.ctx.check(self.ctx.L.nvca_part_stream_push_faces(self.h, buf, len(faces)))
+
+    def set_input(self, layout=None):
+        """nvca_part_stream_set_input: the stream's frames are 4:2:0 buffers of this PixelLayout from now on (None: packed BGR)"""
+        self.ctx.check(self.ctx.L.nvca_part_stream_set_input(self.h, C.byref(layout) if layout is not None else None))
 
     def process(self, bgr, cap=64):
         f = bgr if isinstance(bgr, Frame) else make_frame(np.ascontiguousarray(bgr, np.uint8))
