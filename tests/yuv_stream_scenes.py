@@ -103,10 +103,9 @@ def _trk_planes(W, H):
     return frames
 
 
-@functools.lru_cache(maxsize=None)
-def trk_frame(W, H, i, fmt, pad=0, chroma_pad=None, gap=0):
-    """(buffer, layout tuple) of frame i in make_yuv420's plane arrangement; what no pixel lies in holds 0xA5; read-only"""
-    y, u, v = _trk_planes(W, H)[i]
+def pack_planes(y, u, v, fmt, pad=0, chroma_pad=None, gap=0):
+    """(buffer, layout tuple) of the planes in make_yuv420's arrangement; what no pixel lies in holds 0xA5; read-only"""
+    H, W = y.shape
     cpad = pad if chroma_pad is None else chroma_pad
     if fmt == R.NV12:
         planes = [(y, W + pad), (np.stack([u, v], axis=-1).reshape(H // 2, W), W + cpad)]
@@ -121,6 +120,12 @@ def trk_frame(W, H, i, fmt, pad=0, chroma_pad=None, gap=0):
         buf[o:o + st * p.shape[0]].reshape(p.shape[0], st)[:, :p.shape[1]] = p
     buf.setflags(write=False)
     return buf, (fmt, tuple(offsets), tuple(strides))
+
+
+@functools.lru_cache(maxsize=None)
+def trk_frame(W, H, i, fmt, pad=0, chroma_pad=None, gap=0):
+    """(buffer, layout tuple) of frame i in make_yuv420's plane arrangement; what no pixel lies in holds 0xA5; read-only"""
+    return pack_planes(*_trk_planes(W, H)[i], fmt, pad=pad, chroma_pad=chroma_pad, gap=gap)
 
 
 @functools.lru_cache(maxsize=None)
