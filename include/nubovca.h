@@ -190,6 +190,17 @@ int nvca_resize_linear(nvca_ctx *ctx, const void *src, int sw, int sh, int sstri
  * dst_bgr: packed BGR rows dst_stride bytes apart. */
 int nvca_yuv420_to_bgr(nvca_ctx *ctx, const void *base, int w, int h, const nvca_pixel_layout *layout, int mem,
                        void *dst_bgr, int dst_stride);
+/* cv::cvtColor(CV_BGR2YUV_I420), the inverse of nvca_yuv420_to_bgr: what the pipeline's videoconvert behind the element does
+ * (FACE/run_plugin.sh:3) when a viewed frame goes on to an encoder.  OpenCV 2.4 color.cpp (RGB888toYUV420pInvoker), BT.601 limited
+ * range, integer, SURVEY.md A.14: Y of every pixel; the chroma sample of a 2 x 2 block is (U, V) of the block's top-left pixel alone
+ * (nothing is averaged).  OpenCV 2.4 writes I420 only; NVCA_PIX_NV12 holds the same samples with U and V interleaved.  src: packed
+ * BGR (channels 3) or BGRA (channels 4, alpha ignored -- the tracker's frames, TRK/gstnubotracker.cpp:356) rows `stride` bytes apart;
+ * w x h: both even; base: the buffer the layout's offsets count from; src and base are both host or both device memory (mem).  The
+ * layout rules are those of the 4:2:0 streams (nvca_face_stream_set_input): plane strides at least a row, no overlapping planes,
+ * gaps allowed.  Only the rows' own bytes are written: row padding, gaps between planes and whatever lies behind the last plane
+ * keep their value.  Device buffers are converted in place in the order of the context's stream. */
+int nvca_bgr_to_yuv420(nvca_ctx *ctx, const void *src_bgr, int w, int h, int stride, int channels, int mem,
+                       void *base, const nvca_pixel_layout *layout);
 /* cv::equalizeHist FACE/kmsfacedetect.cpp:807 */
 int nvca_equalize_hist(nvca_ctx *ctx, const void *src_gray, int w, int h, int stride, int mem,
                        void *dst_gray, int dst_stride);
@@ -208,6 +219,17 @@ int nvca_flip_horizontal(nvca_ctx *ctx, const void *src_gray, int w, int h, int 
 #define NVCA_SHAPE_RING4 1
 typedef struct { int kind; int x, y, w, h; uint8_t bgra[4]; } nvca_shape;
 int nvca_draw_shapes(nvca_ctx *ctx, const nvca_frame *frame, int channels, const nvca_shape *shapes, int n);
+/* The same outlines on a 4:2:0 frame (frame->data: the buffer base, frame->stride: the layout's stride[0]; layout rules and
+ * refusals as nvca_face_stream_set_input states them), so that a viewed NV12 / I420 stream -- decoder, detector, outlines, encoder --
+ * never holds a BGR frame: FACE/kmsfacedetect.cpp:832-850 with the face colour of FACE/BaseFace.cpp:76-80, TRK/gstnubotracker.cpp:388-395,
+ * EYE/kmseyedetect.cpp:1075-1092, and the videoconvert behind the element (FACE/run_plugin.sh:3) in one call.  Coverage as
+ * nvca_draw_shapes (shapes in order, the last one that covers a pixel colours it).  A covered pixel's Y byte becomes Y(colour); the
+ * chroma sample of a 2 x 2 block becomes (U, V)(colour of the last shape covering the block's top-left pixel) if that pixel is
+ * covered; every other byte keeps its value.  That is SURVEY.md A.14 applied to the drawn BGR image, restricted to the samples whose
+ * defining pixel was drawn: an untouched region stays bit-identical (it is not converted there and back).  Host frames need no
+ * device: ctx may be NULL for them. */
+int nvca_draw_shapes_yuv420(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout,
+                            const nvca_shape *shapes, int n);
 /* image-to-overlay: kms_face_detect_display_detections_overlay_img, FACE/kmsfacedetect.cpp:427-502 -- for every
  * box, in order, the overlay image is scaled (cvResize, CV_INTER_LINEAR) to (box.w * width_percent) x (box.h * height_percent),
  * placed at box.x + box.w * offset_x_percent, box.y + box.h * offset_y_percent (truncated as the reference's int arithmetic does)
@@ -222,6 +244,15 @@ typedef struct nvca_overlay {
     double offset_x_percent, offset_y_percent, width_percent, height_percent;   /* the image-to-overlay structure's fields, :351-367 */
 } nvca_overlay;
 int nvca_overlay_blend(nvca_ctx *ctx, const nvca_frame *frame_bgr, const nvca_rect *boxes, int n, const nvca_overlay *overlay);
+/* image-to-overlay on a 4:2:0 frame (frame and layout as nvca_draw_shapes_yuv420): placement, scaling and the per-pixel blend are
+ * nvca_overlay_blend's (FACE/kmsfacedetect.cpp:427-502), boxes in order, each on the frame the previous one left.  For one box, a pixel
+ * inside the placed image and the frame is touched unless the image has 4 channels and its scaled alpha there is 0 (the reference
+ * leaves such a pixel's BGR value as it is; here its bytes stay).  A touched pixel's BGR value before the box is SURVEY.md A.13 of
+ * its Y and its block's chroma; the reference's write (:467-490) goes onto that value; Y becomes A.14's Y of the result, and the
+ * chroma sample of a block becomes A.14's (U, V) of the blended top-left pixel of the block if that pixel is touched.  Every other
+ * byte keeps its value.  Host frames: plain loops, ctx may be NULL; device frames: one kernel per box. */
+int nvca_overlay_blend_yuv420(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout,
+                              const nvca_rect *boxes, int n, const nvca_overlay *overlay);
 /* cv::integral as used inside detectMultiScale: sum int32 and sqsum float64,
  * both dense (h+1)*(w+1) */
 int nvca_integral(nvca_ctx *ctx, const void *src_gray, int w, int h, int stride, int mem,

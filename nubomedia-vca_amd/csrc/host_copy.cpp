@@ -216,22 +216,31 @@ size_t yuv_extent(const nvca_pixel_layout &l, int w, int h)
     for (int p = 0; p < yuv_planes_of(l); p++) e = std::max(e, l.offset[p] + yuv_plane_bytes(l, p, w, h));
     return e;
 }
-int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h)
+// what is wrong with a w x h frame in this layout (null: nothing) -- the one set of layout rules, for the streams and for the
+// calls that take a host frame without a context
+const char *yuv_layout_fault(const nvca_pixel_layout &l, int w, int h)
 {
-    if (l.format != NVCA_PIX_NV12 && l.format != NVCA_PIX_I420) { ctx->set_error("pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420"); return NVCA_ERR_ARG; }
-    if (w <= 0 || h <= 0) { ctx->set_error("4:2:0 frame: width and height must be positive"); return NVCA_ERR_ARG; }
-    if ((w | h) & 1) { ctx->set_error("4:2:0 frame: width and height must be even (OpenCV's 4:2:0 conversions assert it)"); return NVCA_ERR_ARG; }
+    if (l.format != NVCA_PIX_NV12 && l.format != NVCA_PIX_I420) return "pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420";
+    if (w <= 0 || h <= 0) return "4:2:0 frame: width and height must be positive";
+    if ((w | h) & 1) return "4:2:0 frame: width and height must be even (OpenCV's 4:2:0 conversions assert it)";
     const int np = yuv_planes_of(l);
     for (int p = 0; p < np; p++) {
-        if (l.stride[p] <= 0 || (size_t)l.stride[p] < yuv_plane_row_bytes(l, p, w)) { ctx->set_error("4:2:0 frame: a plane's stride is shorter than its row"); return NVCA_ERR_ARG; }
-        if (l.offset[p] > ((size_t)1 << 40)) { ctx->set_error("4:2:0 frame: plane offset out of range"); return NVCA_ERR_ARG; }
+        if (l.stride[p] <= 0 || (size_t)l.stride[p] < yuv_plane_row_bytes(l, p, w)) return "4:2:0 frame: a plane's stride is shorter than its row";
+        if (l.offset[p] > ((size_t)1 << 40)) return "4:2:0 frame: plane offset out of range";
     }
     for (int p = 0; p < np; p++)
         for (int q = p + 1; q < np; q++) {
             const size_t a0 = l.offset[p], a1 = a0 + yuv_plane_bytes(l, p, w, h), b0 = l.offset[q], b1 = b0 + yuv_plane_bytes(l, q, w, h);
-            if (a0 < b1 && b0 < a1) { ctx->set_error("4:2:0 frame: planes overlap"); return NVCA_ERR_ARG; }
+            if (a0 < b1 && b0 < a1) return "4:2:0 frame: planes overlap";
         }
-    return NVCA_OK;
+    return nullptr;
+}
+int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h)
+{
+    const char *fault = yuv_layout_fault(l, w, h);
+    if (!fault) return NVCA_OK;
+    if (ctx) ctx->set_error(fault);
+    return NVCA_ERR_ARG;
 }
 // nvca_*_set_input: the caller's layout, validated, as the stream keeps it (null / NVCA_PIX_BGR: packed frames).  What the format
 // does not use stays zero: layouts compare by value.
@@ -260,7 +269,7 @@ int check_yuv_frame(nvca_ctx *ctx, const nvca_pixel_layout &l, const nvca_frame 
 {
     if (!f.data || (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
     if (check_yuv_layout(ctx, l, f.width, f.height)) return NVCA_ERR_ARG;
-    if (f.stride != l.stride[0]) { ctx->set_error("4:2:0 frame: its stride is not the stride[0] of the stream's layout"); return NVCA_ERR_ARG; }
+    if (f.stride != l.stride[0]) { if (ctx) ctx->set_error("4:2:0 frame: its stride is not the stride[0] of the stream's layout"); return NVCA_ERR_ARG; }
     return NVCA_OK;
 }
 // a host 4:2:0 frame to device memory, plane by plane, each at the caller's offset (gaps between planes are not copied); `dst` holds

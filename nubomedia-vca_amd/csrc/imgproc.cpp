@@ -3,6 +3,7 @@
 #include "host_state.h"
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 
@@ -66,6 +67,44 @@ try {
     { TimedLaunch t(ctx, NVCA_K_GRAY);
       launch_yuv420_to_bgr(ctx->cs(), ws.res[ws.cur_res].staging.as<uint8_t>(), w, h, layout->stride[0], planes, ws.ln().aux.as<uint8_t>(), (int)dp); }
     return unstage_2d(ctx, dst, dst_stride, ws.ln().aux.p, dp, (size_t)w * 3, h, mem);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_bgr_to_yuv420(nvca_ctx *ctx, const void *src, int w, int h, int stride, int channels, int mem, void *base, const nvca_pixel_layout *layout)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    if (channels != 3 && channels != 4) return NVCA_ERR_ARG;
+    int rc = check_img(ctx, src, w, h, stride, channels, mem);
+    if (rc || !base || !layout) return NVCA_ERR_ARG;
+    if ((rc = check_yuv_layout(ctx, *layout, w, h))) return rc;
+    (void)hipSetDevice(ctx->device);
+    const YuvPlanes planes = yuv_planes(layout);
+    const char *const names[2] = {"k_bgr_yuv_generic", "k_bgr_yuv16"};
+    if (mem == NVCA_MEM_DEVICE) {          // read and written where they are (ordered on the context's stream)
+        const bool aligned = yuv_layout_aligned16(*layout) && !(((uintptr_t)src | (uintptr_t)base | (uintptr_t)stride) & 15);
+        bool wide;
+        { TimedLaunch t(ctx, NVCA_K_GRAY);
+          wide = launch_bgr_to_yuv420(ctx->cs(), (const uint8_t *)src, w, h, stride, channels, (uint8_t *)base, layout->stride[0], planes, aligned); }
+        if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] BGR to 4:2:0 of a device frame %d x %d: %s\n", w, h, names[wide]);
+        return finish_device_op(ctx);
+    }
+    // host memory: the packed frame in through the staging ring, the planes computed at the caller's offsets of a device buffer of the
+    // layout's extent, and back plane by plane, row by row: what lies between the written rows of the caller's buffer is never touched
+    Workspace &ws = *ctx->ws;
+    const size_t sp = round_up((size_t)w * channels, 64), extent = yuv_extent(*layout, w, h);
+    if (ws.ln().staging.ensure(sp * h) || ws.ln().aux.ensure(extent)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+    if ((rc = stage_2d(ctx, ws.ln().staging.p, sp, src, stride, (size_t)w * channels, h, mem))) return rc;
+    bool wide;
+    { TimedLaunch t(ctx, NVCA_K_GRAY);
+      wide = launch_bgr_to_yuv420(ctx->cs(), ws.ln().staging.as<uint8_t>(), w, h, (int)sp, channels, ws.ln().aux.as<uint8_t>(), layout->stride[0], planes,
+                                  yuv_layout_aligned16(*layout) && !(((uintptr_t)ws.ln().staging.p | (uintptr_t)ws.ln().aux.p) & 15)); }
+    if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] BGR to 4:2:0 of a host frame %d x %d: %s\n", w, h, names[wide]);
+    const int np = layout->format == NVCA_PIX_NV12 ? 2 : 3;
+    for (int p = 0; p < np; p++) {
+        const size_t row = (p == 0 || np == 2) ? (size_t)w : (size_t)w / 2, rows = p == 0 ? (size_t)h : (size_t)h / 2;
+        if ((rc = unstage_2d(ctx, (uint8_t *)base + layout->offset[p], (size_t)layout->stride[p], ws.ln().aux.as<uint8_t>() + layout->offset[p], (size_t)layout->stride[p], row, rows, mem))) return rc;
+    }
+    return NVCA_OK;
 }
 NVCA_API_CATCH(ctx)
 
@@ -197,6 +236,83 @@ try {
         if ((rc = get_resize_plan(ctx, ov->width, ov->height, p.w, p.h, &gp))) return rc;
         launch_overlay(ctx->cs(), (uint8_t *)frame->data, frame->width, frame->height, frame->stride, p, ctx->overlay_img.as<uint8_t>(), ov->height, ov->stride, ov->channels,
                        gp->tab.mode, gp->d_xofs.as<int>(), gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax);
+    }
+    // the image is the caller's: the upload must have left it before the call returns
+    NVCA_LAUNCH_CHECK(ctx);
+    NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
+    return NVCA_OK;
+}
+NVCA_API_CATCH(ctx)
+
+// the argument checks nvca_draw_shapes_yuv420 and nvca_overlay_blend_yuv420 share: a 4:2:0 frame against its layout (the rules of the
+// 4:2:0 streams, check_yuv_frame); a host frame needs no context
+static int check_yuv_target(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout)
+{
+    if (!frame || !layout) return NVCA_ERR_ARG;
+    if (!ctx && frame->mem != NVCA_MEM_HOST) return NVCA_ERR_ARG;
+    return check_yuv_frame(ctx, *layout, *frame);
+}
+
+int nvca_draw_shapes_yuv420(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout, const nvca_shape *shapes, int n)
+try {
+    if (check_yuv_target(ctx, frame, layout) || n < 0 || (n > 0 && !shapes) || n > 1024) return NVCA_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if ((shapes[i].kind != NVCA_SHAPE_RECT3 && shapes[i].kind != NVCA_SHAPE_RING4) || std::abs((long long)shapes[i].x) > (1 << 24) || std::abs((long long)shapes[i].y) > (1 << 24) ||
+            std::abs((long long)shapes[i].w) > (1 << 24) || std::abs((long long)shapes[i].h) > (1 << 24)) return NVCA_ERR_ARG;
+    if (!n) return NVCA_OK;
+    const YuvPlanes planes = yuv_planes(layout);
+    if (frame->mem == NVCA_MEM_HOST) { draw_shapes_yuv420_host((uint8_t *)frame->data, frame->width, frame->height, frame->stride, planes, shapes, n); return NVCA_OK; }
+    NVCA_LOCK_OR_FAIL(ctx);
+    int rc;
+    (void)hipSetDevice(ctx->device);
+    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = INT_MIN, by1 = INT_MIN;          // common bounding box, clipped to the frame
+    for (int i = 0; i < n; i++) {
+        const nvca_shape &sh = shapes[i];
+        int x0, y0, x1, y1;
+        if (sh.kind == NVCA_SHAPE_RING4) { const int r = (sh.w > 0 ? sh.w : 0) + 2; x0 = sh.x - r; x1 = sh.x + r; y0 = sh.y - r; y1 = sh.y + r; }
+        else { x0 = std::min(sh.x, sh.x + sh.w) - 1; x1 = std::max(sh.x, sh.x + sh.w) + 1; y0 = std::min(sh.y, sh.y + sh.h) - 1; y1 = std::max(sh.y, sh.y + sh.h) + 1; }
+        bx0 = std::min(bx0, x0); by0 = std::min(by0, y0); bx1 = std::max(bx1, x1); by1 = std::max(by1, y1);
+    }
+    bx0 = std::max(bx0, 0); by0 = std::max(by0, 0); bx1 = std::min(bx1, frame->width - 1); by1 = std::min(by1, frame->height - 1);
+    if (bx0 > bx1 || by0 > by1) return NVCA_OK;
+    void *d_shapes = nullptr;
+    if ((rc = part_table(ctx, shapes, (size_t)n * sizeof(nvca_shape), &d_shapes))) return rc;
+    // grown to even coordinates: the chroma blocks [bx0 >> 1, bx1 >> 1] x [by0 >> 1, by1 >> 1] (the frame's size is even)
+    const bool uv2 = layout->format == NVCA_PIX_NV12 && !((((uintptr_t)frame->data + layout->offset[1]) | (uintptr_t)layout->stride[1]) & 1);
+    launch_draw_shapes_yuv(ctx->cs(), (uint8_t *)frame->data, frame->stride, planes, (const nvca_shape *)d_shapes, n, bx0 >> 1, by0 >> 1, bx1 >> 1, by1 >> 1, uv2);
+    return finish_device_op(ctx);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_overlay_blend_yuv420(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout, const nvca_rect *boxes, int n, const nvca_overlay *ov)
+try {
+    if (check_yuv_target(ctx, frame, layout) || !ov || n < 0 || (n > 0 && !boxes) || n > 1024) return NVCA_ERR_ARG;
+    if (!ov->data || ov->width <= 0 || ov->height <= 0 || (ov->channels != 1 && ov->channels != 3 && ov->channels != 4) || ov->stride < ov->width * ov->channels ||
+        ov->width > 8192 || ov->height > 8192) return NVCA_ERR_ARG;
+    if (!(std::fabs(ov->offset_x_percent) <= 64 && std::fabs(ov->offset_y_percent) <= 64 && ov->width_percent >= 0 && ov->width_percent <= 64 && ov->height_percent >= 0 && ov->height_percent <= 64)) return NVCA_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if (std::abs((long long)boxes[i].x) > (1 << 20) || std::abs((long long)boxes[i].y) > (1 << 20) || boxes[i].w < 0 || boxes[i].h < 0 || boxes[i].w > (1 << 14) || boxes[i].h > (1 << 14)) return NVCA_ERR_ARG;
+    if (!n || ov->height_percent == 0 || ov->width_percent == 0) return NVCA_OK;           // FACE/kmsfacedetect.cpp:436-439
+    const YuvPlanes planes = yuv_planes(layout);
+    const int W = frame->width, H = frame->height;
+    if (frame->mem == NVCA_MEM_HOST) { overlay_blend_yuv420_host((uint8_t *)frame->data, W, H, frame->stride, planes, boxes, n, *ov); return NVCA_OK; }
+    NVCA_LOCK_OR_FAIL(ctx);
+    (void)hipSetDevice(ctx->device);
+    int rc;
+    const size_t bytes = (size_t)ov->stride * (ov->height - 1) + (size_t)ov->width * ov->channels;
+    if (ctx->overlay_img.ensure(bytes + 64)) { ctx->set_error("allocation failed (overlay image)"); return NVCA_ERR_NOMEM; }
+    if ((rc = caller_h2d(ctx, ctx->overlay_img.p, ov->data, bytes, ctx->cs()))) return rc;
+    for (int b = 0; b < n; b++) {            // in order, one launch a box: each box works on the frame the previous one left
+        const OverlayPlace p = overlay_place(boxes[b], *ov);
+        if (p.w <= 0 || p.h <= 0) continue;
+        const long long x0 = std::max<long long>(p.x, 0), y0 = std::max<long long>(p.y, 0);
+        const long long x1 = std::min<long long>((long long)p.x + p.w, W) - 1, y1 = std::min<long long>((long long)p.y + p.h, H) - 1;
+        if (x0 > x1 || y0 > y1) continue;
+        GeomPlan *gp = nullptr;
+        if ((rc = get_resize_plan(ctx, ov->width, ov->height, p.w, p.h, &gp))) return rc;
+        const OverlayImage o{ctx->overlay_img.as<uint8_t>(), ov->height, ov->stride, ov->channels, gp->tab.mode, gp->tab.xmax,
+                             gp->d_xofs.as<int>(), gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>()};
+        launch_overlay_yuv(ctx->cs(), (uint8_t *)frame->data, W, H, frame->stride, planes, p, o, (int)(x0 >> 1), (int)(y0 >> 1), (int)(x1 >> 1), (int)(y1 >> 1));
     }
     // the image is the caller's: the upload must have left it before the call returns
     NVCA_LAUNCH_CHECK(ctx);

@@ -97,6 +97,15 @@ void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, co
                     int mode, const int *xofs, const short *ialpha, const int *yofs, const short *ibeta, int xmax);
 void launch_draw_shapes(hipStream_t st, uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *d_shapes, int n,
                         int bx0, int by0, int bx1, int by1);
+// ---- the way out in 4:2:0 (kernels_yuv_out.hip): cv::cvtColor(CV_BGR2YUV_I420) into the planes of a layout, and the two drawing kernels
+// on a 4:2:0 device frame.  aligned16: the source, its stride and every plane and stride of the layout take the wide kernel's accesses;
+// returns whether k_bgr_yuv16 took the launch (that, 3 channels and w % 16 == 0) and not k_bgr_yuv_generic.
+bool launch_bgr_to_yuv420(hipStream_t st, const uint8_t *src, int w, int h, int sstride, int cn, uint8_t *base, int ystride, const YuvPlanes &p, bool aligned16);
+// chroma blocks [cx0, cx1] x [cy0, cy1] of the frame; uv2: an NV12 pair may be written with one 2-byte store
+void launch_draw_shapes_yuv(hipStream_t st, uint8_t *base, int ystride, const YuvPlanes &p, const nvca_shape *d_shapes, int n,
+                            int cx0, int cy0, int cx1, int cy1, bool uv2);
+void launch_overlay_yuv(hipStream_t st, uint8_t *base, int W, int H, int ystride, const YuvPlanes &yp, const OverlayPlace &p, const OverlayImage &o,
+                        int cx0, int cy0, int cx1, int cy1);
 // tilted integral (cv::integral's third plane) of `batch` images / of every pyramid level: one workgroup per image
 void launch_tilted(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g, int *tilted, int batch);
 void launch_pyr_tilted(hipStream_t st, const uint8_t *aux, size_t aux_slot, const PyrLevelDev *levels, int nlev, int nimg,

@@ -3,7 +3,13 @@
 #pragma once
 #include <vector>
 #include "../../include/nubovca.h"
-#include "device_records.h"     // NVCA_HD
+#include "device_records.h"     // NVCA_HD, YuvPlanes
+
+#if defined(__HIPCC__)
+#define NVCA_HD_INLINE __host__ __device__ inline __attribute__((always_inline))
+#else
+#define NVCA_HD_INLINE inline
+#endif
 
 namespace nvca {
 
@@ -36,6 +42,47 @@ NVCA_HD inline bool shape_covers(const nvca_shape &sh, int px, int py)
     return mx + my == 1;
 }
 void draw_shapes_host(uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *shapes, int n);
+
+// ---- 4:2:0 frames, both directions.  A.13: cv::cvtColor(CV_YUV2BGR_NV12 / _I420) as OpenCV 2.4 color.cpp computes it, BT.601 limited
+// range, shift 20 -- pixel (x, y) takes the chroma sample (x >> 1, y >> 1); all int32, the shift arithmetic.  (The kernels that read
+// 4:2:0 frames: yuv_device.h.)
+struct ChromaTerm { int r, g, b; };                      // what a chroma sample adds to every pixel of its 2 x 2 block, rounding included
+NVCA_HD_INLINE ChromaTerm chroma_term(int U, int V)
+{
+    const int u = U - 128, v = V - 128;
+    ChromaTerm c;
+    c.r = (1 << 19) + 1673527 * v;
+    c.g = (1 << 19) - 852492 * v - 409993 * u;
+    c.b = (1 << 19) + 2116026 * u;
+    return c;
+}
+NVCA_HD_INLINE int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+NVCA_HD_INLINE void yuv_bgr(int Y, const ChromaTerm &c, int &B, int &G, int &R)
+{
+    const int y = (Y > 16 ? Y - 16 : 0) * 1220542;
+    B = sat8((y + c.b) >> 20); G = sat8((y + c.g) >> 20); R = sat8((y + c.r) >> 20);
+}
+// A.14: cv::cvtColor(CV_BGR2YUV_I420), OpenCV 2.4 color.cpp (RGB888toYUV420pInvoker), BT.601 limited range, shift 20, all int32.  Y of
+// every pixel; the chroma sample of a 2 x 2 block is (U, V) of the block's top-left pixel alone, nothing is averaged.  Over all 2^24
+// colours Y stays in 16 .. 235 and U, V in 16 .. 240: nothing saturates.
+NVCA_HD_INLINE void bgr_yuv(int B, int G, int R, int &Y, int &U, int &V)
+{
+    Y = (269484 * R + 528482 * G + 102760 * B + (1 << 19) + (16 << 20)) >> 20;
+    U = (-155188 * R - 305135 * G + 460324 * B + (1 << 19) + (128 << 20)) >> 20;
+    V = (460324 * R - 385875 * G - 74448 * B + (1 << 19) + (128 << 20)) >> 20;
+}
+// where the samples of a 4:2:0 buffer lie (`p`: the layout as the kernels read it, `ystride`: its luma stride): NV12 keeps V behind U
+NVCA_HD_INLINE uint8_t *yuv_luma_at(uint8_t *base, const YuvPlanes &p, int ystride, int x, int y) { return base + p.off_y + (size_t)y * ystride + x; }
+NVCA_HD_INLINE uint8_t *yuv_u_at(uint8_t *base, const YuvPlanes &p, int cx, int cy) { return base + p.off_u + (size_t)cy * p.cstride + (p.fmt == 1 ? 2 * cx : cx); }
+NVCA_HD_INLINE uint8_t *yuv_v_at(uint8_t *base, const YuvPlanes &p, int cx, int cy) { return p.fmt == 1 ? yuv_u_at(base, p, cx, cy) + 1 : base + p.off_v + (size_t)cy * p.vstride + cx; }
+// nvca_bgr_to_yuv420 on host memory is the device path through the staging ring; these two are what its kernels compute (the host
+// statement a CPU driver checks the rule with): every pixel's Y, the chroma of every block from its top-left pixel
+void bgr_to_yuv420_host(const uint8_t *src, int w, int h, int stride, int channels, uint8_t *base, int ystride, const YuvPlanes &p);
+
+// ---- view-* outlines on a 4:2:0 frame (nvca_draw_shapes_yuv420): a covered pixel's Y byte becomes Y(colour); the chroma sample of a
+// block becomes (U, V)(colour of the last shape covering the block's top-left pixel) if that pixel is covered; every other byte stays.
+// = A.14 of the drawn BGR image, restricted to the samples whose defining pixel was drawn.
+void draw_shapes_yuv420_host(uint8_t *base, int w, int h, int ystride, const YuvPlanes &p, const nvca_shape *shapes, int n);
 
 // ---- image-to-overlay (nvca_overlay_blend): kms_face_detect_display_detections_overlay_img, FACE/kmsfacedetect.cpp:427-502.
 // One arithmetic for the host loop and the kernel (as for the outlines above).
@@ -80,5 +127,39 @@ inline OverlayPlace overlay_place(const nvca_rect &b, const nvca_overlay &ov)
     return p;
 }
 void overlay_blend_host(uint8_t *frame, int W, int H, int stride, const nvca_rect *boxes, int n, const nvca_overlay &ov);
+
+// ---- image-to-overlay on a 4:2:0 frame (nvca_overlay_blend_yuv420), one box: the 2 x 2 block (cx, cy) of the frame.  A pixel inside the
+// placed image and the frame is touched unless the image has 4 channels and its scaled alpha there is 0 (the reference leaves such a
+// pixel's BGR value as it is: its bytes stay).  A touched pixel's BGR value before the box is A.13 of its Y and the block's chroma;
+// overlay_pixel blends onto it; Y becomes A.14's Y of the result, and the block's chroma A.14's (U, V) of the blended top-left pixel if
+// that one is touched.  Everything is read before anything is written, and nothing outside the block is read: blocks are independent.
+struct OverlayImage { const uint8_t *img; int ih, istride, cn, mode, xmax; const int *xofs; const short *ialpha; const int *yofs; const short *ibeta; };
+NVCA_HD_INLINE void overlay_block_yuv(uint8_t *base, int W, int H, int ystride, const YuvPlanes &yp, const OverlayPlace &p, const OverlayImage &o, int cx, int cy)
+{
+    uint8_t *pu = yuv_u_at(base, yp, cx, cy), *pv = yuv_v_at(base, yp, cx, cy);
+    const ChromaTerm c = chroma_term(*pu, *pv);
+    int ny[4], nu = -1, nv = -1;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int x = 2 * cx + (j & 1), y = 2 * cy + (j >> 1), w = x - p.x, h = y - p.y;
+        ny[j] = -1;
+        if (x >= W || y >= H || w < 0 || h < 0 || w >= p.w || h >= p.h) continue;
+        int v[4] = {0, 0, 0, 0};
+        for (int k = 0; k < o.cn; k++) v[k] = resize_sample_cn(o.img, o.ih, o.istride, o.cn, o.mode, o.xofs, o.ialpha, o.yofs, o.ibeta, o.xmax, w, h, k);
+        if (o.cn == 4 && v[3] == 0) continue;
+        int B, G, R, Y, U, V;
+        yuv_bgr(*yuv_luma_at(base, yp, ystride, x, y), c, B, G, R);
+        uint8_t px[3] = {(uint8_t)B, (uint8_t)G, (uint8_t)R};
+        overlay_pixel(px, v, o.cn);
+        bgr_yuv(px[0], px[1], px[2], Y, U, V);
+        ny[j] = Y;
+        if (j == 0) { nu = U; nv = V; }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (ny[j] >= 0) *yuv_luma_at(base, yp, ystride, 2 * cx + (j & 1), 2 * cy + (j >> 1)) = (uint8_t)ny[j];
+    if (nu >= 0) { *pu = (uint8_t)nu; *pv = (uint8_t)nv; }
+}
+void overlay_blend_yuv420_host(uint8_t *base, int W, int H, int ystride, const YuvPlanes &p, const nvca_rect *boxes, int n, const nvca_overlay &ov);
 
 } // namespace nvca

@@ -13,22 +13,7 @@ __device__ __forceinline__ int gray_of(int b, int g, int r)
     return (b * 1868 + g * 9617 + r * 4899 + 8192) >> 14;
 }
 
-struct ChromaTerm { int r, g, b; };                      // what a chroma sample adds to every pixel of its 2 x 2 block, rounding included
-__device__ __forceinline__ ChromaTerm chroma_term(int U, int V)
-{
-    const int u = U - 128, v = V - 128;
-    ChromaTerm c;
-    c.r = (1 << 19) + 1673527 * v;
-    c.g = (1 << 19) - 852492 * v - 409993 * u;
-    c.b = (1 << 19) + 2116026 * u;
-    return c;
-}
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-__device__ __forceinline__ void yuv_bgr(int Y, const ChromaTerm &c, int &B, int &G, int &R)
-{
-    const int y = (Y > 16 ? Y - 16 : 0) * 1220542;
-    B = sat8((y + c.b) >> 20); G = sat8((y + c.g) >> 20); R = sat8((y + c.r) >> 20);
-}
+// (ChromaTerm, chroma_term, sat8, yuv_bgr: pixel_rules.h -- the host loops of the 4:2:0 overlay share them)
 __device__ __forceinline__ int yuv_gray(int Y, const ChromaTerm &c)
 {
     int B, G, R;

@@ -97,7 +97,8 @@ SYMBOLS = [
     "nvca_integral_tilted", "nvca_cascade_kind", "nvca_part_batch_process", "nvca_device_count", "nvca_draw_shapes",
     "nvca_cascade_validate_mem", "nvca_abi_selftest", "nvca_ctx_set_option", "nvca_ctx_get_option", "nvca_overlay_blend",
     "nvca_part_batch_submit", "nvca_part_batch_collect", "nvca_face_stream_set_input", "nvca_yuv420_to_bgr",
-    "nvca_part_stream_set_input", "nvca_tracker_set_input",
+    "nvca_part_stream_set_input", "nvca_tracker_set_input", "nvca_bgr_to_yuv420", "nvca_draw_shapes_yuv420",
+    "nvca_overlay_blend_yuv420",
 ]
 
 _lib = None
@@ -182,6 +183,9 @@ def load():
     L.nvca_face_stream_motion_event.argtypes = [vp]
     L.nvca_face_stream_set_input.argtypes = [vp, C.POINTER(PixelLayout)]
     L.nvca_yuv420_to_bgr.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(PixelLayout), C.c_int, vp, C.c_int]
+    L.nvca_bgr_to_yuv420.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(PixelLayout)]
+    L.nvca_draw_shapes_yuv420.argtypes = [vp, C.POINTER(Frame), C.POINTER(PixelLayout), C.POINTER(Shape), C.c_int]
+    L.nvca_overlay_blend_yuv420.argtypes = [vp, C.POINTER(Frame), C.POINTER(PixelLayout), C.POINTER(Rect), C.c_int, C.POINTER(Overlay)]
     L.nvca_face_stream_process.argtypes = [vp, C.POINTER(Frame), C.POINTER(Rect), ip, C.c_int, ip]
     L.nvca_face_batch_process.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Frame), C.POINTER(Rect), ip, C.c_int, ip]
     L.nvca_face_batch_submit.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Frame), ip]
@@ -351,6 +355,21 @@ class Context:
             return out
         self.check(self.L.nvca_yuv420_to_bgr(self.h, int(buf), w, h, C.byref(layout), MEM_DEVICE, int(dst), dst_stride))
 
+    def bgr_to_yuv420(self, src, w, h, layout, base, mem=MEM_HOST, stride=None, channels=3):
+        """nvca_bgr_to_yuv420 into the planes of `layout`.  Host: src is a numpy image [h, w, 3 or 4], base a writable flat uint8 numpy
+        buffer (written in place: only the rows' own bytes change).  Device: src and base are device pointers, stride / channels describe src."""
+        if mem == MEM_HOST:
+            src = np.ascontiguousarray(src, np.uint8)
+            assert base.dtype == np.uint8 and base.flags.c_contiguous and base.flags.writeable
+            self.check(self.L.nvca_bgr_to_yuv420(self.h, src.ctypes.data, w, h, src.strides[0], src.shape[2], MEM_HOST, base.ctypes.data, C.byref(layout)))
+            return base
+        self.check(self.L.nvca_bgr_to_yuv420(self.h, int(src), w, h, w * channels if stride is None else stride, channels, MEM_DEVICE, int(base), C.byref(layout)))
+
+    def draw_shapes_yuv420(self, frame, layout, shapes):
+        """nvca_draw_shapes_yuv420: frame: a Frame of a 4:2:0 buffer (make_planar_frame; host or device memory), drawn in place"""
+        arr = _shape_array(shapes)
+        self.check(self.L.nvca_draw_shapes_yuv420(self.h, C.byref(frame), C.byref(layout), arr, len(shapes)))
+
     def draw_shapes(self, frame, channels, shapes):
         """nvca_draw_shapes: shapes = [(kind, x, y, w, h, (b, g, r, a))]; frame: a Frame (device memory) or a writable numpy image (drawn in place)"""
         fr = frame if isinstance(frame, Frame) else make_frame(frame)
@@ -513,6 +532,39 @@ def overlay_blend(ctx, frame, boxes, image, offset_x=0.0, offset_y=0.0, width=1.
     rc = L.nvca_overlay_blend(ctx.h if ctx is not None else None, C.byref(fr), buf, len(boxes), C.byref(ov))
     if rc != 0:
         raise NvcaError(rc, L.nvca_last_error(ctx.h).decode() if ctx is not None else "nvca_overlay_blend")
+
+
+def _shape_array(shapes):
+    arr = (Shape * max(len(shapes), 1))()
+    for i, (kind, x, y, w, h, col) in enumerate(shapes):
+        arr[i].kind, arr[i].x, arr[i].y, arr[i].w, arr[i].h = kind, x, y, w, h
+        for k in range(4):
+            arr[i].bgra[k] = col[k]
+    return arr
+
+
+def overlay_blend_yuv420(ctx, frame, layout, boxes, image, offset_x=0.0, offset_y=0.0, width=1.0, height=1.0):
+    """nvca_overlay_blend_yuv420: as overlay_blend, on a Frame of a 4:2:0 buffer (make_planar_frame; a host frame needs no context:
+    ctx may be None), in place"""
+    L = load()
+    image = np.ascontiguousarray(image, np.uint8)
+    cn = 1 if image.ndim == 2 else image.shape[2]
+    ov = Overlay(image.ctypes.data, image.shape[1], image.shape[0], image.strides[0], cn, offset_x, offset_y, width, height)
+    boxes = np.asarray(boxes, np.int32).reshape(-1, 4)
+    buf = (Rect * max(len(boxes), 1))()
+    for i, r in enumerate(boxes):
+        buf[i] = Rect(*[int(v) for v in r])
+    rc = L.nvca_overlay_blend_yuv420(ctx.h if ctx is not None else None, C.byref(frame), C.byref(layout), buf, len(boxes), C.byref(ov))
+    if rc != 0:
+        raise NvcaError(rc, L.nvca_last_error(ctx.h).decode() if ctx is not None else "nvca_overlay_blend_yuv420")
+
+
+def draw_shapes_yuv420_host(frame, layout, shapes):
+    """nvca_draw_shapes_yuv420 on a host 4:2:0 frame (make_planar_frame) without a context (no device needed): drawn in place"""
+    L = load()
+    rc = L.nvca_draw_shapes_yuv420(None, C.byref(frame), C.byref(layout), _shape_array(shapes), len(shapes))
+    if rc != 0:
+        raise NvcaError(rc, "nvca_draw_shapes_yuv420")
 
 
 def draw_shapes_host(img, channels, shapes):
