@@ -89,9 +89,9 @@ static int si_plan(nvca_ctx *ctx, const DetectJob &j, GeomPlan **out)
             for (size_t li = 0; li < np->lv.size(); li++) {
                 const PyrLevel &L = np->lv[li]; GeomPlan *t = np->level_tabs[li].get();
                 PyrLevelDev &d = dl[li]; memset(&d, 0, sizeof(d));
-                d.szw = L.szw; d.szh = L.szh; d.gpitch = L.gpitch; d.mode = t->tab.mode; d.xmax = t->tab.xmax; d.plane_off = L.plane_off;
+                d.szw = L.szw; d.szh = L.szh; d.gpitch = L.gpitch; d.plane_off = L.plane_off;
                 d.gray_off = (long long)L.gray_off;
-                d.xofs = t->d_xofs.as<int>(); d.ialpha = t->d_ialpha.as<short>(); d.yofs = t->d_yofs.as<int>(); d.ibeta = t->d_ibeta.as<short>();
+                d.tab = t->view();
                 np->pyr_maxw = std::max(np->pyr_maxw, L.szw); np->pyr_maxh = std::max(np->pyr_maxh, L.szh);
                 if (L.szw > 1023) np->pyr_ok = false;            // one column per thread, plus the zero column
             }
@@ -163,9 +163,7 @@ static int si_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
         GeomPlan *gp = pp->level_tabs[li].get();
         uint8_t *lg = ws.ln().aux.as<uint8_t>() + L.gray_off;
         { TimedLaunch t(ctx, NVCA_K_RESIZE1);               // cvResize(img, &img1, CV_INTER_LINEAR)
-          launch_resize1(ctx->cs(), src0, cols, rows, spitch0, gp->tab.mode, gp->d_xofs.as<int>(),
-                         gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax, lg, L.szw,
-                         L.szh, L.gpitch, nullptr, nimg, sslot0, gray_total); }
+          launch_resize1(ctx->cs(), src0, cols, rows, spitch0, gp->view(), lg, L.szw, L.szh, L.gpitch, nullptr, nimg, sslot0, gray_total); }
         PreGeom g; make_geom(g, L.szw, L.szh, L.gpitch, 1, L.szw, L.szh);
         g.gpitch = L.gpitch; g.spitch = P; g.sum_slot = plane_total; g.gray_slot = gray_total;
         run_integral(ctx, g, nullptr, nimg, lg, ws.ln().sum.as<int>() + L.plane_off,

@@ -147,11 +147,18 @@ struct YuvPlanes {
     int fmt, cstride, vstride, pad;      // chroma stride (NV12: of the interleaved plane; I420: of U), I420's V stride
     long long off_y, off_u, off_v;
 };
+// the six values of one cv::resize(INTER_LINEAR) geometry on 8-bit images, wherever its tables lie (host vectors: ResizeTab::view,
+// device buffers: GeomPlan::view, a launch's table blob: k_roi).  mode 0 identity (no table is read), 1 bilinear, 2 area 2x2 (no
+// table is read).  What resize_sample (pixel_rules.h) and every kernel that resizes take.
+struct ResizeView {
+    int mode, xmax;               // xmax: first destination column whose right-hand source column does not exist
+    const int *xofs; const short *ialpha; const int *yofs; const short *ibeta;      // [dw], [2 dw], [dh], [2 dh]
+};
 // one pyramid level of a CV_HAAR_SCALE_IMAGE scan (device copy): all levels are resized / integrated by one launch each
 struct PyrLevelDev {
-    int szw, szh, gpitch, mode, xmax, plane_off, pad0, pad1;
+    int szw, szh, gpitch, plane_off;
     long long gray_off;
-    const int *xofs; const short *ialpha; const int *yofs; const short *ibeta;
+    ResizeView tab;
 };
 
 // ---- tracker (kernels_tracker.hip) ----

@@ -252,14 +252,12 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
             if ((rc = cascade_counters(ctx, gp->det, job, &z_hits, &z_deep))) return rc;
             if (yuv) {
               TimedLaunch t(ctx, NVCA_K_GRAY);                             // cvtColor(YUV2BGR) + cv::resize + cvtColor :805-806 (+ histogram)
-              const bool wide = launch_gray_yuv(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, yuv_planes(yuv), gp->tab.mode, gp->d_xofs.as<int>(),
-                              gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,
+              const bool wide = launch_gray_yuv(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, yuv_planes(yuv), gp->view(),
                               ws.ln().gray.as<uint8_t>(), ws.ln().hist.as<unsigned>(), nc, frames_yuv_aligned16(frames, idx.data() + s0, nc, *yuv));
               if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 gray of %d frame(s) %d x %d -> %d x %d: %s\n", nc, f0.width, f0.height, cols, rows, wide ? "k_gray_yuv16" : "k_gray_yuv_generic");
             } else
             { TimedLaunch t(ctx, NVCA_K_GRAY);                             // cv::resize + cvtColor :805-806 (+ histogram)
-              launch_gray(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, gp->tab.mode, gp->d_xofs.as<int>(),
-                          gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,
+              launch_gray(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, gp->view(),
                           ws.ln().gray.as<uint8_t>(), ws.ln().hist.as<unsigned>(), nc, frames_aligned4(frames, idx.data() + s0, nc)); }
             { TimedLaunch t(ctx, NVCA_K_LUT);                              // equalizeHist :807 (applied inside the integral pass)
               launch_lut(ctx->cs(), ws.ln().hist.as<unsigned>(), cols * rows, ws.ln().lut.as<uint8_t>(), nc, 1, z_hits, z_deep); }

@@ -178,15 +178,22 @@ void join_objects(std::vector<nvca_rect> &sb, int min_area, long max_area, int d
     }
 }
 
+int check_shape_list(const nvca_shape *shapes, int n)
+{
+    if (n < 0 || (n > 0 && !shapes) || n > 1024) return NVCA_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if ((shapes[i].kind != NVCA_SHAPE_RECT3 && shapes[i].kind != NVCA_SHAPE_RING4) || std::abs((long long)shapes[i].x) > (1 << 24) || std::abs((long long)shapes[i].y) > (1 << 24) ||
+            std::abs((long long)shapes[i].w) > (1 << 24) || std::abs((long long)shapes[i].h) > (1 << 24)) return NVCA_ERR_ARG;
+    return NVCA_OK;
+}
+
 // view-* outlines on a host frame: the bounding box of every shape is walked, the last shape that covers a pixel colours it
 void draw_shapes_host(uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *shapes, int n)
 {
     for (int i = 0; i < n; i++) {
         const nvca_shape &sh = shapes[i];
-        int x0, y0, x1, y1;
-        if (sh.kind == NVCA_SHAPE_RING4) { const int r = (sh.w > 0 ? sh.w : 0) + 2; x0 = sh.x - r; x1 = sh.x + r; y0 = sh.y - r; y1 = sh.y + r; }
-        else { x0 = std::min(sh.x, sh.x + sh.w) - 1; x1 = std::max(sh.x, sh.x + sh.w) + 1; y0 = std::min(sh.y, sh.y + sh.h) - 1; y1 = std::max(sh.y, sh.y + sh.h) + 1; }
-        x0 = std::max(x0, 0); y0 = std::max(y0, 0); x1 = std::min(x1, w - 1); y1 = std::min(y1, h - 1);
+        const ShapeBox b = shape_bounds(sh);
+        const int x0 = std::max(b.x0, 0), y0 = std::max(b.y0, 0), x1 = std::min(b.x1, w - 1), y1 = std::min(b.y1, h - 1);
         for (int y = y0; y <= y1; y++)
             for (int x = x0; x <= x1; x++)
                 if (shape_covers(sh, x, y)) {
@@ -277,10 +284,20 @@ void to_global(RectV &v, const nvca_rect &face, int scale)
     for (nvca_rect &r : v) { r.x = (face.x + r.x) * scale; r.y = (face.y + r.y) * scale; r.w = (r.w - 1) * scale; r.h = (r.h - 1) * scale; }
 }
 
+int check_overlay_args(const nvca_rect *boxes, int n, const nvca_overlay *ov)
+{
+    if (!ov || n < 0 || (n > 0 && !boxes) || n > 1024) return NVCA_ERR_ARG;
+    if (!ov->data || ov->width <= 0 || ov->height <= 0 || (ov->channels != 1 && ov->channels != 3 && ov->channels != 4) || ov->stride < ov->width * ov->channels ||
+        ov->width > 8192 || ov->height > 8192) return NVCA_ERR_ARG;
+    if (!(std::fabs(ov->offset_x_percent) <= 64 && std::fabs(ov->offset_y_percent) <= 64 && ov->width_percent >= 0 && ov->width_percent <= 64 && ov->height_percent >= 0 && ov->height_percent <= 64)) return NVCA_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if (std::abs((long long)boxes[i].x) > (1 << 20) || std::abs((long long)boxes[i].y) > (1 << 20) || boxes[i].w < 0 || boxes[i].h < 0 || boxes[i].w > (1 << 14) || boxes[i].h > (1 << 14)) return NVCA_ERR_ARG;
+    return NVCA_OK;
+}
 
 // ------------------------------------------------------------ image-to-overlay on a host frame
 // kms_face_detect_display_detections_overlay_img (FACE/kmsfacedetect.cpp:427-502) for every box in order; the arithmetic
-// is pixel_rules.h's resize_sample_cn / overlay_pixel, shared with the kernel
+// is pixel_rules.h's resize_sample / overlay_pixel, shared with the kernel
 void overlay_blend_host(uint8_t *frame, int W, int H, int stride, const nvca_rect *boxes, int n, const nvca_overlay &ov)
 {
     if (ov.height_percent == 0 || ov.width_percent == 0) return;           // :436-439
@@ -290,13 +307,13 @@ void overlay_blend_host(uint8_t *frame, int W, int H, int stride, const nvca_rec
         if (p.w <= 0 || p.h <= 0) continue;
         ResizeTab tab;
         build_resize_tab(ov.width, ov.height, p.w, p.h, tab);
+        const ResizeView t = tab.view();
         for (int h = 0; h < p.h; h++) {
             if (h + p.y < 0 || h + p.y >= H) continue;
             for (int w = 0; w < p.w; w++) {
                 if (w + p.x < 0 || w + p.x >= W) continue;
                 int v[4] = {0, 0, 0, 0};
-                for (int k = 0; k < ov.channels; k++)
-                    v[k] = resize_sample_cn(img, ov.height, ov.stride, ov.channels, tab.mode, tab.xofs.data(), tab.ialpha.data(), tab.yofs.data(), tab.ibeta.data(), tab.xmax, w, h, k);
+                for (int k = 0; k < ov.channels; k++) v[k] = resize_sample_cn(img, ov.height, ov.stride, ov.channels, t, w, h, k);
                 overlay_pixel(frame + (size_t)(h + p.y) * stride + (size_t)(w + p.x) * 3, v, ov.channels);
             }
         }

@@ -19,6 +19,11 @@ struct Faces {                 // FACE/Faces.hpp: the per-stream list with ids
 
 void join_objects(std::vector<nvca_rect> &seg_bounds, int min_area, long max_area, int distance);
 
+// argument checks the drawing entry points share (NVCA_OK / NVCA_ERR_ARG).  nvca_draw_shapes / nvca_draw_shapes_yuv420: 0 .. 1024 shapes,
+// known kinds, coordinates and sizes within 2^24; nvca_overlay_blend / nvca_overlay_blend_yuv420: the image, its placement and the boxes
+int check_shape_list(const nvca_shape *shapes, int n);
+int check_overlay_args(const nvca_rect *boxes, int n, const nvca_overlay *ov);
+
 // part detectors' merging heuristics (EYE/kmseyedetect.cpp:778-913, NOSE/kmsnosedetect.cpp:745-790, MOUTH/kmsmouthdetect.cpp:750-796)
 void merge_consecutive_nm(std::vector<nvca_rect> &cn, const std::vector<nvca_rect> &old, const nvca_rect &face, int scale, int dis, std::vector<nvca_rect> &res);
 bool contain_bb(int px, int py, const nvca_rect &r);

@@ -66,6 +66,7 @@ struct GeomPlan {
     ResizeTab tab;
     RowCopy rowcopy;
     DevBuf d_xofs, d_yofs, d_ialpha, d_ibeta;
+    ResizeView view() const { return ResizeView{tab.mode, tab.xmax, d_xofs.as<int>(), d_ialpha.as<short>(), d_yofs.as<int>(), d_ibeta.as<short>()}; }      // the tables on the device
     DetectPlan det;
     PreGeom g;
     bool has_det = false;

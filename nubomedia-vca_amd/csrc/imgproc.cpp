@@ -1,6 +1,7 @@
 // imgproc.cpp -- the image primitives of the C ABI: cvtColor, resize, equalizeHist, the view-* outlines, the overlay, flip and
 // the integral images.
 #include "host_state.h"
+#include "host_logic.h"
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -39,7 +40,7 @@ try {
     const int slot = ctx->defer_device_sync > 0 ? ctx->ptr_ring_used : 0;
     if ((rc = stage_frames(ctx, &f, nullptr, 1, channels, slot))) return rc;
     { TimedLaunch t(ctx, NVCA_K_GRAY);
-      launch_gray(ctx->cs(), rb.srcptrs.as<const uint8_t *>() + slot, g, 0, nullptr, nullptr, nullptr, nullptr, w,
+      launch_gray(ctx->cs(), rb.srcptrs.as<const uint8_t *>() + slot, g, ResizeView{},
                   ctx->ws->ln().gray.as<uint8_t>(), nullptr, 1, frames_aligned4(&f, nullptr, 1)); }
     return unstage_2d(ctx, dst, dst_stride, ctx->ws->ln().gray.p, g.gpitch, w, h, mem);
 }
@@ -123,8 +124,7 @@ try {
         GeomPlan *gp3 = nullptr;
         if ((rc3 = get_resize_plan(ctx, sw, sh, dw, dh, &gp3))) return rc3;
         { TimedLaunch t(ctx, NVCA_K_RESIZE1);
-          launch_resize3(ctx->cs(), w3.ln().staging.as<uint8_t>(), sw, sh, (int)sp, gp3->tab.mode, gp3->d_xofs.as<int>(), gp3->d_ialpha.as<short>(),
-                         gp3->d_yofs.as<int>(), gp3->d_ibeta.as<short>(), gp3->tab.xmax, w3.ln().aux.as<uint8_t>(), dw, dh, (int)dp3); }
+          launch_resize3(ctx->cs(), w3.ln().staging.as<uint8_t>(), sw, sh, (int)sp, gp3->view(), w3.ln().aux.as<uint8_t>(), dw, dh, (int)dp3); }
         return unstage_2d(ctx, dst, dstride, w3.ln().aux.p, dp3, (size_t)dw * 3, dh, mem);
     }
     if (channels != 1) return NVCA_ERR_ARG;
@@ -138,17 +138,14 @@ try {
     if ((rc = get_resize_plan(ctx, sw, sh, dw, dh, &gp))) return rc;
     if (mem == NVCA_MEM_DEVICE) {          // device images are read and written in place (ordered on the context's stream)
         { TimedLaunch t(ctx, NVCA_K_RESIZE1);
-          launch_resize1(ctx->cs(), (const uint8_t *)src, sw, sh, sstride, gp->tab.mode, gp->d_xofs.as<int>(),
-                         gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,
-                         (uint8_t *)dst, dw, dh, dstride, nullptr); }
+          launch_resize1(ctx->cs(), (const uint8_t *)src, sw, sh, sstride, gp->view(), (uint8_t *)dst, dw, dh, dstride, nullptr); }
         return finish_device_op(ctx);
     }
     if ((rc = ensure_ws(ctx, gs, 1)) || (rc = ensure_ws(ctx, gd, 1))) return rc;
     if (ws.ln().aux.ensure(gd.gray_slot + 64)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
     if ((rc = stage_2d(ctx, ws.ln().gray.p, gs.gpitch, src, sstride, sw, sh, mem))) return rc;
     { TimedLaunch t(ctx, NVCA_K_RESIZE1);
-      launch_resize1(ctx->cs(), ws.ln().gray.as<uint8_t>(), sw, sh, gs.gpitch, gp->tab.mode, gp->d_xofs.as<int>(),
-                     gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax,
+      launch_resize1(ctx->cs(), ws.ln().gray.as<uint8_t>(), sw, sh, gs.gpitch, gp->view(),
                      ws.ln().aux.as<uint8_t>(), dw, dh, gd.gpitch, nullptr); }
     return unstage_2d(ctx, dst, dstride, ws.ln().aux.p, gd.gpitch, dw, dh, mem);
 }
@@ -180,30 +177,32 @@ try {
 }
 NVCA_API_CATCH(ctx)
 
+// the common bounding box of a shape list, clipped to a w x h frame; false: nothing of it lies inside
+static bool shapes_box(const nvca_shape *shapes, int n, int w, int h, int &bx0, int &by0, int &bx1, int &by1)
+{
+    bx0 = by0 = INT_MAX; bx1 = by1 = INT_MIN;
+    for (int i = 0; i < n; i++) {
+        const ShapeBox b = shape_bounds(shapes[i]);
+        bx0 = std::min(bx0, b.x0); by0 = std::min(by0, b.y0); bx1 = std::max(bx1, b.x1); by1 = std::max(by1, b.y1);
+    }
+    bx0 = std::max(bx0, 0); by0 = std::max(by0, 0); bx1 = std::min(bx1, w - 1); by1 = std::min(by1, h - 1);
+    return bx0 <= bx1 && by0 <= by1;
+}
+
 int nvca_draw_shapes(nvca_ctx *ctx, const nvca_frame *frame, int channels, const nvca_shape *shapes, int n)
 try {
     // host frames need no device (and no context): plain loops over the mapped buffer
     const bool host = frame && frame->mem == NVCA_MEM_HOST;
-    if (!frame || (!ctx && !host) || (channels != 3 && channels != 4) || n < 0 || (n > 0 && !shapes) || n > 1024) return NVCA_ERR_ARG;
+    if (!frame || (!ctx && !host) || (channels != 3 && channels != 4)) return NVCA_ERR_ARG;
     if (!frame->data || frame->width <= 0 || frame->height <= 0 || frame->stride < frame->width * channels || (frame->mem != NVCA_MEM_HOST && frame->mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
-    for (int i = 0; i < n; i++)
-        if ((shapes[i].kind != NVCA_SHAPE_RECT3 && shapes[i].kind != NVCA_SHAPE_RING4) || std::abs((long long)shapes[i].x) > (1 << 24) || std::abs((long long)shapes[i].y) > (1 << 24) ||
-            std::abs((long long)shapes[i].w) > (1 << 24) || std::abs((long long)shapes[i].h) > (1 << 24)) return NVCA_ERR_ARG;
+    if (check_shape_list(shapes, n)) return NVCA_ERR_ARG;
     if (!n) return NVCA_OK;
     if (host) { draw_shapes_host((uint8_t *)frame->data, frame->width, frame->height, frame->stride, channels, shapes, n); return NVCA_OK; }
     NVCA_LOCK_OR_FAIL(ctx);
     int rc;
     (void)hipSetDevice(ctx->device);
-    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = INT_MIN, by1 = INT_MIN;          // common bounding box, clipped to the frame
-    for (int i = 0; i < n; i++) {
-        const nvca_shape &sh = shapes[i];
-        int x0, y0, x1, y1;
-        if (sh.kind == NVCA_SHAPE_RING4) { const int r = (sh.w > 0 ? sh.w : 0) + 2; x0 = sh.x - r; x1 = sh.x + r; y0 = sh.y - r; y1 = sh.y + r; }
-        else { x0 = std::min(sh.x, sh.x + sh.w) - 1; x1 = std::max(sh.x, sh.x + sh.w) + 1; y0 = std::min(sh.y, sh.y + sh.h) - 1; y1 = std::max(sh.y, sh.y + sh.h) + 1; }
-        bx0 = std::min(bx0, x0); by0 = std::min(by0, y0); bx1 = std::max(bx1, x1); by1 = std::max(by1, y1);
-    }
-    bx0 = std::max(bx0, 0); by0 = std::max(by0, 0); bx1 = std::min(bx1, frame->width - 1); by1 = std::min(by1, frame->height - 1);
-    if (bx0 > bx1 || by0 > by1) return NVCA_OK;
+    int bx0, by0, bx1, by1;
+    if (!shapes_box(shapes, n, frame->width, frame->height, bx0, by0, bx1, by1)) return NVCA_OK;
     void *d_shapes = nullptr;
     if ((rc = part_table(ctx, shapes, (size_t)n * sizeof(nvca_shape), &d_shapes))) return rc;
     launch_draw_shapes(ctx->cs(), (uint8_t *)frame->data, frame->width, frame->height, frame->stride, channels, (const nvca_shape *)d_shapes, n, bx0, by0, bx1, by1);
@@ -214,13 +213,9 @@ NVCA_API_CATCH(ctx)
 int nvca_overlay_blend(nvca_ctx *ctx, const nvca_frame *frame, const nvca_rect *boxes, int n, const nvca_overlay *ov)
 try {
     const bool host = frame && frame->mem == NVCA_MEM_HOST;
-    if (!frame || !ov || (!ctx && !host) || n < 0 || (n > 0 && !boxes) || n > 1024) return NVCA_ERR_ARG;
+    if (!frame || (!ctx && !host)) return NVCA_ERR_ARG;
     if (!frame->data || frame->width <= 0 || frame->height <= 0 || frame->stride < frame->width * 3 || (frame->mem != NVCA_MEM_HOST && frame->mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
-    if (!ov->data || ov->width <= 0 || ov->height <= 0 || (ov->channels != 1 && ov->channels != 3 && ov->channels != 4) || ov->stride < ov->width * ov->channels ||
-        ov->width > 8192 || ov->height > 8192) return NVCA_ERR_ARG;
-    if (!(std::fabs(ov->offset_x_percent) <= 64 && std::fabs(ov->offset_y_percent) <= 64 && ov->width_percent >= 0 && ov->width_percent <= 64 && ov->height_percent >= 0 && ov->height_percent <= 64)) return NVCA_ERR_ARG;
-    for (int i = 0; i < n; i++)
-        if (std::abs((long long)boxes[i].x) > (1 << 20) || std::abs((long long)boxes[i].y) > (1 << 20) || boxes[i].w < 0 || boxes[i].h < 0 || boxes[i].w > (1 << 14) || boxes[i].h > (1 << 14)) return NVCA_ERR_ARG;
+    if (check_overlay_args(boxes, n, ov)) return NVCA_ERR_ARG;
     if (!n || ov->height_percent == 0 || ov->width_percent == 0) return NVCA_OK;           // FACE/kmsfacedetect.cpp:436-439
     if (host) { overlay_blend_host((uint8_t *)frame->data, frame->width, frame->height, frame->stride, boxes, n, *ov); return NVCA_OK; }
     NVCA_LOCK_OR_FAIL(ctx);
@@ -234,8 +229,8 @@ try {
         if (p.w <= 0 || p.h <= 0) continue;
         GeomPlan *gp = nullptr;
         if ((rc = get_resize_plan(ctx, ov->width, ov->height, p.w, p.h, &gp))) return rc;
-        launch_overlay(ctx->cs(), (uint8_t *)frame->data, frame->width, frame->height, frame->stride, p, ctx->overlay_img.as<uint8_t>(), ov->height, ov->stride, ov->channels,
-                       gp->tab.mode, gp->d_xofs.as<int>(), gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(), gp->tab.xmax);
+        launch_overlay(ctx->cs(), (uint8_t *)frame->data, frame->width, frame->height, frame->stride, p,
+                       OverlayImage{ctx->overlay_img.as<uint8_t>(), ov->height, ov->stride, ov->channels, gp->view()});
     }
     // the image is the caller's: the upload must have left it before the call returns
     NVCA_LAUNCH_CHECK(ctx);
@@ -255,26 +250,15 @@ static int check_yuv_target(nvca_ctx *ctx, const nvca_frame *frame, const nvca_p
 
 int nvca_draw_shapes_yuv420(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout, const nvca_shape *shapes, int n)
 try {
-    if (check_yuv_target(ctx, frame, layout) || n < 0 || (n > 0 && !shapes) || n > 1024) return NVCA_ERR_ARG;
-    for (int i = 0; i < n; i++)
-        if ((shapes[i].kind != NVCA_SHAPE_RECT3 && shapes[i].kind != NVCA_SHAPE_RING4) || std::abs((long long)shapes[i].x) > (1 << 24) || std::abs((long long)shapes[i].y) > (1 << 24) ||
-            std::abs((long long)shapes[i].w) > (1 << 24) || std::abs((long long)shapes[i].h) > (1 << 24)) return NVCA_ERR_ARG;
+    if (check_yuv_target(ctx, frame, layout) || check_shape_list(shapes, n)) return NVCA_ERR_ARG;
     if (!n) return NVCA_OK;
     const YuvPlanes planes = yuv_planes(layout);
     if (frame->mem == NVCA_MEM_HOST) { draw_shapes_yuv420_host((uint8_t *)frame->data, frame->width, frame->height, frame->stride, planes, shapes, n); return NVCA_OK; }
     NVCA_LOCK_OR_FAIL(ctx);
     int rc;
     (void)hipSetDevice(ctx->device);
-    int bx0 = INT_MAX, by0 = INT_MAX, bx1 = INT_MIN, by1 = INT_MIN;          // common bounding box, clipped to the frame
-    for (int i = 0; i < n; i++) {
-        const nvca_shape &sh = shapes[i];
-        int x0, y0, x1, y1;
-        if (sh.kind == NVCA_SHAPE_RING4) { const int r = (sh.w > 0 ? sh.w : 0) + 2; x0 = sh.x - r; x1 = sh.x + r; y0 = sh.y - r; y1 = sh.y + r; }
-        else { x0 = std::min(sh.x, sh.x + sh.w) - 1; x1 = std::max(sh.x, sh.x + sh.w) + 1; y0 = std::min(sh.y, sh.y + sh.h) - 1; y1 = std::max(sh.y, sh.y + sh.h) + 1; }
-        bx0 = std::min(bx0, x0); by0 = std::min(by0, y0); bx1 = std::max(bx1, x1); by1 = std::max(by1, y1);
-    }
-    bx0 = std::max(bx0, 0); by0 = std::max(by0, 0); bx1 = std::min(bx1, frame->width - 1); by1 = std::min(by1, frame->height - 1);
-    if (bx0 > bx1 || by0 > by1) return NVCA_OK;
+    int bx0, by0, bx1, by1;
+    if (!shapes_box(shapes, n, frame->width, frame->height, bx0, by0, bx1, by1)) return NVCA_OK;
     void *d_shapes = nullptr;
     if ((rc = part_table(ctx, shapes, (size_t)n * sizeof(nvca_shape), &d_shapes))) return rc;
     // grown to even coordinates: the chroma blocks [bx0 >> 1, bx1 >> 1] x [by0 >> 1, by1 >> 1] (the frame's size is even)
@@ -286,12 +270,7 @@ NVCA_API_CATCH(ctx)
 
 int nvca_overlay_blend_yuv420(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout, const nvca_rect *boxes, int n, const nvca_overlay *ov)
 try {
-    if (check_yuv_target(ctx, frame, layout) || !ov || n < 0 || (n > 0 && !boxes) || n > 1024) return NVCA_ERR_ARG;
-    if (!ov->data || ov->width <= 0 || ov->height <= 0 || (ov->channels != 1 && ov->channels != 3 && ov->channels != 4) || ov->stride < ov->width * ov->channels ||
-        ov->width > 8192 || ov->height > 8192) return NVCA_ERR_ARG;
-    if (!(std::fabs(ov->offset_x_percent) <= 64 && std::fabs(ov->offset_y_percent) <= 64 && ov->width_percent >= 0 && ov->width_percent <= 64 && ov->height_percent >= 0 && ov->height_percent <= 64)) return NVCA_ERR_ARG;
-    for (int i = 0; i < n; i++)
-        if (std::abs((long long)boxes[i].x) > (1 << 20) || std::abs((long long)boxes[i].y) > (1 << 20) || boxes[i].w < 0 || boxes[i].h < 0 || boxes[i].w > (1 << 14) || boxes[i].h > (1 << 14)) return NVCA_ERR_ARG;
+    if (check_yuv_target(ctx, frame, layout) || check_overlay_args(boxes, n, ov)) return NVCA_ERR_ARG;
     if (!n || ov->height_percent == 0 || ov->width_percent == 0) return NVCA_OK;           // FACE/kmsfacedetect.cpp:436-439
     const YuvPlanes planes = yuv_planes(layout);
     const int W = frame->width, H = frame->height;
@@ -310,8 +289,7 @@ try {
         if (x0 > x1 || y0 > y1) continue;
         GeomPlan *gp = nullptr;
         if ((rc = get_resize_plan(ctx, ov->width, ov->height, p.w, p.h, &gp))) return rc;
-        const OverlayImage o{ctx->overlay_img.as<uint8_t>(), ov->height, ov->stride, ov->channels, gp->tab.mode, gp->tab.xmax,
-                             gp->d_xofs.as<int>(), gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>()};
+        const OverlayImage o{ctx->overlay_img.as<uint8_t>(), ov->height, ov->stride, ov->channels, gp->view()};
         launch_overlay_yuv(ctx->cs(), (uint8_t *)frame->data, W, H, frame->stride, planes, p, o, (int)(x0 >> 1), (int)(y0 >> 1), (int)(x1 >> 1), (int)(y1 >> 1));
     }
     // the image is the caller's: the upload must have left it before the call returns

@@ -6,20 +6,17 @@
 namespace nvca {
 
 // ---- image-to-overlay on a device frame: one thread per pixel of the scaled overlay image of one box
-__global__ __launch_bounds__(256) void k_overlay(uint8_t *__restrict__ frame, int W, int H, int stride, OverlayPlace p, const uint8_t *__restrict__ img,
-                                                 int ih, int istride, int cn, int mode, const int *__restrict__ xofs, const short *__restrict__ ialpha,
-                                                 const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax)
+__global__ __launch_bounds__(256) void k_overlay(uint8_t *__restrict__ frame, int W, int H, int stride, OverlayPlace p, OverlayImage o)
 {
     const int w = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
     if (w >= p.w || h >= p.h || w + p.x < 0 || w + p.x >= W || h + p.y < 0 || h + p.y >= H) return;
     int v[4] = {0, 0, 0, 0};
-    for (int k = 0; k < cn; k++) v[k] = resize_sample_cn(img, ih, istride, cn, mode, xofs, ialpha, yofs, ibeta, xmax, w, h, k);
-    overlay_pixel(frame + (size_t)(h + p.y) * stride + (size_t)(w + p.x) * 3, v, cn);
+    for (int k = 0; k < o.cn; k++) v[k] = resize_sample_cn(o.img, o.ih, o.istride, o.cn, o.tab, w, h, k);
+    overlay_pixel(frame + (size_t)(h + p.y) * stride + (size_t)(w + p.x) * 3, v, o.cn);
 }
-void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const uint8_t *img, int ih, int istride, int cn,
-                    int mode, const int *xofs, const short *ialpha, const int *yofs, const short *ibeta, int xmax)
+void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const OverlayImage &o)
 {
-    NVCA_LAUNCH(k_overlay, dim3((p.w + 255) / 256, p.h), dim3(256), 0, st, frame, W, H, stride, p, img, ih, istride, cn, mode, xofs, ialpha, yofs, ibeta, xmax);
+    NVCA_LAUNCH(k_overlay, dim3((p.w + 255) / 256, p.h), dim3(256), 0, st, frame, W, H, stride, p, o);
 }
 
 // ---- view-* outlines on a device frame: a thread per pixel of the shapes' common bounding box; the last shape of the list

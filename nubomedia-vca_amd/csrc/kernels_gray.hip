@@ -1,19 +1,19 @@
 // kernels_gray.hip -- gfx950 kernels for the colour conversion and the resizes in front of the cascade: cv::resize +
 // cv::cvtColor as the reference calls them (FACE/kmsfacedetect.cpp:805-811), with the histogram of the cv::equalizeHist that
 // follows; the working images of the part detectors and the levels of a CV_HAAR_SCALE_IMAGE pyramid.  All integer;
-// HBM-bound streaming work.
+// HBM-bound streaming work.  Every kernel that resizes takes its geometry as a ResizeView and calls the one statement of
+// cv::resize's 8-bit rule, resize_sample (pixel_rules.h), with a tap of its own: a packed pixel, a gray byte (plain or through the
+// LDS LUT), gray_of of a BGR pixel, yuv_gray / yuv_bgr of a 4:2:0 pixel.  k_gray_fast4 and k_gray_yuv16, the full-resolution
+// paths, do not resize.
 #include "launch.h"
 #include "pre_device.h"
 #include "yuv_device.h"
 
 namespace nvca {
 
-// ---- K1 generic: one output pixel per thread, any resize mode, any alignment.
-// mode 0 identity, 1 bilinear (fixed point, 11-bit coefficients), 2 area 2x2.
+// ---- K1 generic: one output pixel per thread, any resize mode, any alignment: cv::resize on the packed frame, then BGR2GRAY
 __global__ __launch_bounds__(256) void k_gray_generic(
-    const uint8_t *const *__restrict__ srcs, PreGeom g, int mode,
-    const int *__restrict__ xofs, const short *__restrict__ ialpha,
-    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    const uint8_t *const *__restrict__ srcs, PreGeom g, ResizeView t,
     uint8_t *__restrict__ gray, unsigned *__restrict__ hist)
 {
     __shared__ unsigned lh[4][256];
@@ -24,47 +24,17 @@ __global__ __launch_bounds__(256) void k_gray_generic(
     const int cn = g.cn;
     const int x = blockIdx.x * 256 + tid;
     uint8_t *grow = gray + (size_t)slot * g.gray_slot;
+    auto tap = [&](int r, int c, int *p) {
+        const uint8_t *s = src + (size_t)r * g.sstride + (size_t)c * cn;
+        p[0] = s[0]; p[1] = s[1]; p[2] = s[2];
+    };
     for (int ry = 0; ry < kGrayRows; ry++) {
         const int y = blockIdx.y * kGrayRows + ry;
         if (y >= g.h) break;
         if (x < g.w) {
-            int B, G, R;
-            if (mode == 0) {
-                const uint8_t *s = src + (size_t)y * g.sstride + (size_t)x * cn;
-                B = s[0]; G = s[1]; R = s[2];
-            } else if (mode == 2) {
-                const uint8_t *s0 = src + (size_t)(2 * y) * g.sstride + (size_t)(2 * x) * cn;
-                const uint8_t *s1 = s0 + g.sstride;
-                B = (s0[0] + s0[cn] + s1[0] + s1[cn] + 2) >> 2;
-                G = (s0[1] + s0[cn + 1] + s1[1] + s1[cn + 1] + 2) >> 2;
-                R = (s0[2] + s0[cn + 2] + s1[2] + s1[cn + 2] + 2) >> 2;
-            } else {
-                int sy0 = yofs[y], sy1 = sy0 + 1;
-                sy0 = sy0 >= 0 ? (sy0 < g.sh ? sy0 : g.sh - 1) : 0;
-                sy1 = sy1 >= 0 ? (sy1 < g.sh ? sy1 : g.sh - 1) : 0;
-                const int sx = xofs[x] * cn;
-                const uint8_t *s0 = src + (size_t)sy0 * g.sstride + sx;
-                const uint8_t *s1 = src + (size_t)sy1 * g.sstride + sx;
-                const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
-                int c[3];
-                if (x < xmax) {
-                    const int a0 = ialpha[2 * x], a1 = ialpha[2 * x + 1];
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        int h0 = s0[k] * a0 + s0[cn + k] * a1;
-                        int h1 = s1[k] * a0 + s1[cn + k] * a1;
-                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        int h0 = s0[k] * 2048, h1 = s1[k] * 2048;
-                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                    }
-                }
-                B = c[0] & 255; G = c[1] & 255; R = c[2] & 255;
-            }
-            const int v = gray_of(B, G, R);
+            int c[3];
+            resize_sample<3>(tap, g.sh, t, x, y, c);
+            const int v = gray_of(c[0] & 255, c[1] & 255, c[2] & 255);
             grow[(size_t)y * g.gpitch + x] = (uint8_t)v;
             if (hist) atomicAdd(&lh[wave][v], 1u);
         }
@@ -124,19 +94,17 @@ __global__ __launch_bounds__(256) void k_gray_fast4(
     if (hist) hist_flush(lh, hist + slot * 256, tid);
 }
 
-void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, int mode,
-                 const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const ResizeView &t,
                  uint8_t *gray, unsigned *hist, int batch, bool aligned4)
 {
     const int gy = (g.h + kGrayRows - 1) / kGrayRows;
-    if (mode == 0 && aligned4 && (g.cn == 3 || g.cn == 4)) {
+    if (t.mode == 0 && aligned4 && (g.cn == 3 || g.cn == 4)) {
         dim3 grid((g.w + 1023) / 1024, gy, batch);
         if (g.cn == 3) NVCA_LAUNCH(k_gray_fast4<3>, grid, dim3(256), 0, st, d_src, g, gray, hist);
         else           NVCA_LAUNCH(k_gray_fast4<4>, grid, dim3(256), 0, st, d_src, g, gray, hist);
     } else {
         dim3 grid((g.w + 255) / 256, gy, batch);
-        NVCA_LAUNCH(k_gray_generic, grid, dim3(256), 0, st, d_src, g, mode, d_xofs, d_ialpha, d_yofs,
-                           d_ibeta, xmax, gray, hist);
+        NVCA_LAUNCH(k_gray_generic, grid, dim3(256), 0, st, d_src, g, t, gray, hist);
     }
 }
 
@@ -210,13 +178,10 @@ __global__ __launch_bounds__(256) void k_gray_yuv16(
 }
 
 // ---- K1 generic for 4:2:0 frames: one output pixel per thread, any resize mode, any alignment.  The reference's order
-// (convert, cv::resize on BGR, BGR2GRAY): every tap of the resize is a converted pixel, the resize runs per channel with
-// k_gray_generic's arithmetic.
+// (convert, cv::resize on BGR, BGR2GRAY): every tap of the resize is a converted pixel.
 template <int FMT>
 __global__ __launch_bounds__(256) void k_gray_yuv_generic(
-    const uint8_t *const *__restrict__ srcs, PreGeom g, YuvPlanes p, int mode,
-    const int *__restrict__ xofs, const short *__restrict__ ialpha,
-    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    const uint8_t *const *__restrict__ srcs, PreGeom g, YuvPlanes p, ResizeView t,
     uint8_t *__restrict__ gray, unsigned *__restrict__ hist)
 {
     __shared__ unsigned lh[4][256];
@@ -226,47 +191,16 @@ __global__ __launch_bounds__(256) void k_gray_yuv_generic(
     const uint8_t *__restrict__ src = srcs[slot];
     const int x = blockIdx.x * 256 + tid;
     uint8_t *grow = gray + (size_t)slot * g.gray_slot;
-    auto tap = [&](int r, int c, int &B, int &G, int &R) {
-        yuv_bgr(src[p.off_y + (size_t)r * g.sstride + c], chroma_at<FMT>(src, p, c >> 1, r >> 1), B, G, R);
+    auto tap = [&](int r, int c, int *v) {
+        yuv_bgr(src[p.off_y + (size_t)r * g.sstride + c], chroma_at<FMT>(src, p, c >> 1, r >> 1), v[0], v[1], v[2]);
     };
     for (int ry = 0; ry < kGrayRows; ry++) {
         const int y = blockIdx.y * kGrayRows + ry;
         if (y >= g.h) break;
         if (x < g.w) {
-            int B, G, R;
-            if (mode == 0) tap(y, x, B, G, R);
-            else if (mode == 2) {
-                int b[4], gg[4], r[4];
-                tap(2 * y, 2 * x, b[0], gg[0], r[0]); tap(2 * y, 2 * x + 1, b[1], gg[1], r[1]);
-                tap(2 * y + 1, 2 * x, b[2], gg[2], r[2]); tap(2 * y + 1, 2 * x + 1, b[3], gg[3], r[3]);
-                B = (b[0] + b[1] + b[2] + b[3] + 2) >> 2; G = (gg[0] + gg[1] + gg[2] + gg[3] + 2) >> 2; R = (r[0] + r[1] + r[2] + r[3] + 2) >> 2;
-            } else {
-                int sy0 = yofs[y], sy1 = sy0 + 1;
-                sy0 = sy0 >= 0 ? (sy0 < g.sh ? sy0 : g.sh - 1) : 0;
-                sy1 = sy1 >= 0 ? (sy1 < g.sh ? sy1 : g.sh - 1) : 0;
-                const int sx = xofs[x];
-                const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
-                int t0[3], t1[3], c[3];
-                tap(sy0, sx, t0[0], t0[1], t0[2]); tap(sy1, sx, t1[0], t1[1], t1[2]);
-                if (x < xmax) {
-                    const int a0 = ialpha[2 * x], a1 = ialpha[2 * x + 1];
-                    int n0[3], n1[3];
-                    tap(sy0, sx + 1, n0[0], n0[1], n0[2]); tap(sy1, sx + 1, n1[0], n1[1], n1[2]);
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        const int h0 = t0[k] * a0 + n0[k] * a1, h1 = t1[k] * a0 + n1[k] * a1;
-                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        const int h0 = t0[k] * 2048, h1 = t1[k] * 2048;
-                        c[k] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                    }
-                }
-                B = c[0] & 255; G = c[1] & 255; R = c[2] & 255;
-            }
-            const int v = gray_of(B, G, R);
+            int c[3];
+            resize_sample<3>(tap, g.sh, t, x, y, c);
+            const int v = gray_of(c[0] & 255, c[1] & 255, c[2] & 255);
             grow[(size_t)y * g.gpitch + x] = (uint8_t)v;
             if (hist) atomicAdd(&lh[wave][v], 1u);
         }
@@ -274,11 +208,10 @@ __global__ __launch_bounds__(256) void k_gray_yuv_generic(
     if (hist) hist_flush(lh, hist + slot * 256, tid);
 }
 
-bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, int mode,
-                     const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, const ResizeView &t,
                      uint8_t *gray, unsigned *hist, int batch, bool aligned16)
 {
-    if (mode == 0 && aligned16) {
+    if (t.mode == 0 && aligned16) {
         const int units = ((g.w + 15) >> 4) * (g.h >> 1);
         dim3 grid((units + 255) / 256, 1, batch);
         if (p.fmt == 1) NVCA_LAUNCH(k_gray_yuv16<1>, grid, dim3(256), 0, st, d_src, g, p, gray, hist);
@@ -286,8 +219,8 @@ bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom 
         return true;
     } else {
         dim3 grid((g.w + 255) / 256, (g.h + kGrayRows - 1) / kGrayRows, batch);
-        if (p.fmt == 1) NVCA_LAUNCH(k_gray_yuv_generic<1>, grid, dim3(256), 0, st, d_src, g, p, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax, gray, hist);
-        else            NVCA_LAUNCH(k_gray_yuv_generic<2>, grid, dim3(256), 0, st, d_src, g, p, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax, gray, hist);
+        if (p.fmt == 1) NVCA_LAUNCH(k_gray_yuv_generic<1>, grid, dim3(256), 0, st, d_src, g, p, t, gray, hist);
+        else            NVCA_LAUNCH(k_gray_yuv_generic<2>, grid, dim3(256), 0, st, d_src, g, p, t, gray, hist);
         return false;
     }
 }
@@ -324,39 +257,22 @@ void launch_yuv420_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int 
     else            NVCA_LAUNCH(k_yuv420_to_bgr<2>, grid, dim3(256), 0, st, src, w, h, ystride, p, dst, dstride);
 }
 
-// ---- 8UC1 resize (gray-then-resize order of the part detectors, pyramid levels)
-// one destination sample of cv::resize(INTER_LINEAR) 8UC1 (mode 0: copy, 2: exact 2x area-fast, 1: fixed-point bilinear)
-// `px(row, col)`: the source sample (a gray byte, a gray byte through a LUT, or the gray value of a BGR pixel)
+// ---- 8UC1 resize (gray-then-resize order of the part detectors, pyramid levels): resize_sample on one channel, the value as a
+// byte.  `px(row, col)`: the source sample (a gray byte, a gray byte through a LUT, or the gray value of a converted pixel)
 template <class Px>
-__device__ __forceinline__ int resize1_sample(Px px, int sh, int mode,
-                                              const int *__restrict__ xofs, const short *__restrict__ ialpha,
-                                              const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax, int x, int y)
+__device__ __forceinline__ int resize1_sample(Px px, int sh, const ResizeView &t, int x, int y)
 {
-    if (mode == 0) return px(y, x);
-    if (mode == 2) return (px(2 * y, 2 * x) + px(2 * y, 2 * x + 1) + px(2 * y + 1, 2 * x) + px(2 * y + 1, 2 * x + 1) + 2) >> 2;
-    int sy0 = yofs[y], sy1 = sy0 + 1;
-    sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
-    sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
-    const int sx = xofs[x];
-    const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
-    int h0, h1;
-    if (x < xmax) {
-        const int a0 = ialpha[2 * x], a1 = ialpha[2 * x + 1];
-        h0 = px(sy0, sx) * a0 + px(sy0, sx + 1) * a1; h1 = px(sy1, sx) * a0 + px(sy1, sx + 1) * a1;
-    } else { h0 = px(sy0, sx) * 2048; h1 = px(sy1, sx) * 2048; }
-    return ((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 255;
+    int v;
+    resize_sample<1>([&](int r, int c, int *p) { p[0] = px(r, c); }, sh, t, x, y, &v);
+    return v & 255;
 }
-__device__ __forceinline__ int resize1_value(const uint8_t *__restrict__ src, int sh, int sstride, int mode,
-                                             const int *__restrict__ xofs, const short *__restrict__ ialpha,
-                                             const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax, int x, int y)
+__device__ __forceinline__ int resize1_value(const uint8_t *__restrict__ src, int sh, int sstride, const ResizeView &t, int x, int y)
 {
-    return resize1_sample([&](int r, int c) { return (int)src[(size_t)r * sstride + c]; }, sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+    return resize1_sample([&](int r, int c) { return (int)src[(size_t)r * sstride + c]; }, sh, t, x, y);
 }
 
 __global__ __launch_bounds__(256) void k_resize1(
-    const uint8_t *__restrict__ src, int sw, int sh, int sstride, int mode,
-    const int *__restrict__ xofs, const short *__restrict__ ialpha,
-    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    const uint8_t *__restrict__ src, int sw, int sh, int sstride, ResizeView t,
     uint8_t *__restrict__ dst, int dw, int dh, int dstride, unsigned *__restrict__ hist, size_t src_slot, size_t dst_slot)
 {
     __shared__ unsigned lh[4][256];
@@ -370,7 +286,7 @@ __global__ __launch_bounds__(256) void k_resize1(
         const int y = blockIdx.y * kGrayRows + ry;
         if (y >= dh) break;
         if (x < dw) {
-            const int v = resize1_value(src, sh, sstride, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            const int v = resize1_value(src, sh, sstride, t, x, y);
             dst[(size_t)y * dstride + x] = (uint8_t)v;
             if (hist) atomicAdd(&lh[wave][v], 1u);
         }
@@ -381,56 +297,35 @@ __global__ __launch_bounds__(256) void k_resize1(
 // ---- 8UC3 resize (cv::resize on the BGR frame, FACE/kmsfacedetect.cpp:805, as a stand-alone primitive;
 // the face stream fuses it with BGR2GRAY in k_gray_generic)
 __global__ __launch_bounds__(256) void k_resize3(
-    const uint8_t *__restrict__ src, int sw, int sh, int sstride, int mode,
-    const int *__restrict__ xofs, const short *__restrict__ ialpha,
-    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
+    const uint8_t *__restrict__ src, int sw, int sh, int sstride, ResizeView t,
     uint8_t *__restrict__ dst, int dw, int dh, int dstride)
 {
     const int x = blockIdx.x * 256 + threadIdx.x;
+    auto tap = [&](int r, int c, int *p) {
+        const uint8_t *s = src + (size_t)r * sstride + (size_t)c * 3;
+        p[0] = s[0]; p[1] = s[1]; p[2] = s[2];
+    };
     for (int ry = 0; ry < kGrayRows; ry++) {
         const int y = blockIdx.y * kGrayRows + ry;
         if (y >= dh || x >= dw) continue;
+        int c[3];
+        resize_sample<3>(tap, sh, t, x, y, c);
         uint8_t *d = dst + (size_t)y * dstride + (size_t)x * 3;
-        if (mode == 0) {
-            const uint8_t *s = src + (size_t)y * sstride + (size_t)x * 3;
-            d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
-        } else if (mode == 2) {
-            const uint8_t *s0 = src + (size_t)(2 * y) * sstride + (size_t)(2 * x) * 3, *s1 = s0 + sstride;
-#pragma unroll
-            for (int k = 0; k < 3; k++) d[k] = (uint8_t)((s0[k] + s0[3 + k] + s1[k] + s1[3 + k] + 2) >> 2);
-        } else {
-            int sy0 = yofs[y], sy1 = sy0 + 1;
-            sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
-            sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
-            const int sx = xofs[x] * 3;
-            const uint8_t *s0 = src + (size_t)sy0 * sstride + sx, *s1 = src + (size_t)sy1 * sstride + sx;
-            const int b0 = ibeta[2 * y], b1 = ibeta[2 * y + 1];
-            const bool inner = x < xmax;
-            const int a0 = inner ? ialpha[2 * x] : 2048, a1 = inner ? ialpha[2 * x + 1] : 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const int h0 = s0[k] * a0 + (inner ? s0[3 + k] * a1 : 0), h1 = s1[k] * a0 + (inner ? s1[3 + k] * a1 : 0);
-                d[k] = (uint8_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
-            }
-        }
+        d[0] = (uint8_t)c[0]; d[1] = (uint8_t)c[1]; d[2] = (uint8_t)c[2];
     }
 }
-void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
-                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
-                    int xmax, uint8_t *dst, int dw, int dh, int dstride)
+void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, const ResizeView &t,
+                    uint8_t *dst, int dw, int dh, int dstride)
 {
     dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, 1);
-    NVCA_LAUNCH(k_resize3, grid, dim3(256), 0, st, src, sw, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax,
-                       dst, dw, dh, dstride);
+    NVCA_LAUNCH(k_resize3, grid, dim3(256), 0, st, src, sw, sh, sstride, t, dst, dw, dh, dstride);
 }
 
-void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
-                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
-                    int xmax, uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch, size_t src_slot, size_t dst_slot)
+void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, const ResizeView &t,
+                    uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch, size_t src_slot, size_t dst_slot)
 {
     dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, batch);
-    NVCA_LAUNCH(k_resize1, grid, dim3(256), 0, st, src, sw, sh, sstride, mode, d_xofs, d_ialpha, d_yofs,
-                       d_ibeta, xmax, dst, dw, dh, dstride, hist, src_slot, dst_slot);
+    NVCA_LAUNCH(k_resize1, grid, dim3(256), 0, st, src, sw, sh, sstride, t, dst, dw, dh, dstride, hist, src_slot, dst_slot);
 }
 
 // ---- working images of the part detectors, all frames of a batched call in one launch: image z of the launch is
@@ -442,9 +337,7 @@ enum { kWorkGray = 0, kWorkBgr = 1, kWorkNv12 = 2, kWorkI420 = 3 };
 template <int SRC>
 __global__ __launch_bounds__(256) void k_work_resize(
     const uint8_t *const *__restrict__ srcs, const int *__restrict__ lut_idx, const uint8_t *__restrict__ luts, YuvPlanes yp,
-    int sh, int sstride, int mode, const int *__restrict__ xofs, const short *__restrict__ ialpha,
-    const int *__restrict__ yofs, const short *__restrict__ ibeta, int xmax,
-    uint8_t *__restrict__ dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *__restrict__ hist)
+    int sh, int sstride, ResizeView t, uint8_t *__restrict__ dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *__restrict__ hist)
 {
     __shared__ unsigned lh[4][256];
     __shared__ uint8_t sl[256];
@@ -461,13 +354,11 @@ __global__ __launch_bounds__(256) void k_work_resize(
         if (y >= dh) break;
         if (x < dw) {
             int v;
-            if (SRC == kWorkBgr) v = resize1_sample([&](int r, int c) { const uint8_t *p = src + (size_t)r * sstride + (size_t)c * 3; return gray_of(p[0], p[1], p[2]); },
-                                                    sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+            if (SRC == kWorkBgr) v = resize1_sample([&](int r, int c) { const uint8_t *p = src + (size_t)r * sstride + (size_t)c * 3; return gray_of(p[0], p[1], p[2]); }, sh, t, x, y);
             else if (SRC == kWorkNv12 || SRC == kWorkI420)
-                v = resize1_sample([&](int r, int c) { return yuv_gray(src[yp.off_y + (size_t)r * sstride + c], chroma_at<SRC == kWorkNv12 ? 1 : 2>(src, yp, c >> 1, r >> 1)); },
-                                   sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
-            else if (use_lut) v = resize1_sample([&](int r, int c) { return (int)sl[src[(size_t)r * sstride + c]]; }, sh, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
-            else v = resize1_value(src, sh, sstride, mode, xofs, ialpha, yofs, ibeta, xmax, x, y);
+                v = resize1_sample([&](int r, int c) { return yuv_gray(src[yp.off_y + (size_t)r * sstride + c], chroma_at<SRC == kWorkNv12 ? 1 : 2>(src, yp, c >> 1, r >> 1)); }, sh, t, x, y);
+            else if (use_lut) v = resize1_sample([&](int r, int c) { return (int)sl[src[(size_t)r * sstride + c]]; }, sh, t, x, y);
+            else v = resize1_value(src, sh, sstride, t, x, y);
             dst[(size_t)y * dstride + x] = (uint8_t)v;
             if (hist) atomicAdd(&lh[wave][v], 1u);
         }
@@ -476,13 +367,11 @@ __global__ __launch_bounds__(256) void k_work_resize(
 }
 // yuv: planes of the frames' 4:2:0 layout (fmt 0 / null: `bgr` says whether the sources are packed BGR frames or gray images)
 void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, const int *d_lut_idx, const uint8_t *d_luts, int sh, int sstride,
-                        int mode, const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
-                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch, const YuvPlanes *yuv)
+                        const ResizeView &t, uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch, const YuvPlanes *yuv)
 {
     dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, batch);
     const YuvPlanes yp = yuv ? *yuv : YuvPlanes{};
-#define NVCA_WORK_RESIZE(SRC) NVCA_LAUNCH(k_work_resize<SRC>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, yp, sh, sstride, mode, d_xofs, d_ialpha, d_yofs, d_ibeta, xmax, \
-                                          dst, dw, dh, dstride, dst_slot, hist)
+#define NVCA_WORK_RESIZE(SRC) NVCA_LAUNCH(k_work_resize<SRC>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, yp, sh, sstride, t, dst, dw, dh, dstride, dst_slot, hist)
     if (yp.fmt == 1) NVCA_WORK_RESIZE(kWorkNv12);
     else if (yp.fmt == 2) NVCA_WORK_RESIZE(kWorkI420);
     else if (bgr) NVCA_WORK_RESIZE(kWorkBgr);
@@ -504,7 +393,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize(const uint8_t *__restrict__ 
     for (int ry = 0; ry < kGrayRows; ry++) {
         const int y = blockIdx.y * kGrayRows + ry;
         if (y >= L.szh) break;
-        if (x < L.szw) d[(size_t)y * L.gpitch + x] = (uint8_t)resize1_value(s, sh, sstride, L.mode, L.xofs, L.ialpha, L.yofs, L.ibeta, L.xmax, x, y);
+        if (x < L.szw) d[(size_t)y * L.gpitch + x] = (uint8_t)resize1_value(s, sh, sstride, L.tab, x, y);
     }
 }
 void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,

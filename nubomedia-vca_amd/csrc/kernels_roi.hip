@@ -354,11 +354,13 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi(const RoiJobDev *__restrict
     if (job.scale_image) {
         // cvHaarDetectObjectsForROC, CV_HAAR_SCALE_IMAGE branch, one factor: resize, integrate, scan the unscaled window on a fixed grid
         const int szw = st.szw, szh = st.szh, P = szw + 1;
-        const int *xofs = (const int *)(tabs + st.xofs_off), *yofs = (const int *)(tabs + st.yofs_off);
-        const short *ialpha = (const short *)(tabs + st.ialpha_off), *ibeta = (const short *)(tabs + st.ibeta_off);
+        const ResizeView rt{st.mode, st.xmax, (const int *)(tabs + st.xofs_off), (const short *)(tabs + st.ialpha_off),
+                            (const int *)(tabs + st.yofs_off), (const short *)(tabs + st.ibeta_off)};
         for (int i = tid; i < szw * szh; i += kRoiThreads) {
             const int y = i / szw, x = i - y * szw;
-            L.lev[i] = (uint8_t)resize_sample_cn(img, job.h, job.stride, 1, st.mode, xofs, ialpha, yofs, ibeta, st.xmax, x, y, 0);
+            int v;
+            resize_sample<1>([&](int r, int c, int *p) { p[0] = img[(size_t)r * job.stride + c]; }, job.h, rt, x, y, &v);
+            L.lev[i] = (uint8_t)v;
         }
         __syncthreads();
         roi_integral([&](int x, int y) { return L.lev[y * szw + x]; }, szw, szh, L.s, L.q, P);

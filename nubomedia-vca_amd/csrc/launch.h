@@ -1,5 +1,7 @@
 // launch.h -- what a kernel file sees of the library: the launch macro and the launch_* function of every kernel, over the
-// device records and the pixel rules.  Nothing of the context.
+// device records and the pixel rules.  Nothing of the context.  A launch that resizes takes its geometry as one ResizeView
+// (device_records.h; GeomPlan::view() for a cached plan, ResizeView{} for the identity) and computes every destination sample
+// with pixel_rules.h's resize_sample.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -26,25 +28,21 @@ hipError_t take_launch_error(const char **kernel);     // returns and clears the
 // Kernel launch wrappers (kernels_gray.hip / kernels_equalize.hip / kernels_integral.hip / kernels_cascade_*.hip / kernels_group.hip)
 // --------------------------------------------------------------------------
 // src[b] pointers are passed as a device array of pointers (frames need not be contiguous)
-void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, int mode,
-                 const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const ResizeView &t,
                  uint8_t *gray, unsigned *hist, int batch, bool aligned4);
 // the same for a 4:2:0 frame (planes `p`); aligned16: every plane and stride of every frame takes 16-byte (I420 chroma: 8-byte) loads.
 // Returns whether k_gray_yuv16 took the launch (identity geometry and aligned16) and not k_gray_yuv_generic.
-bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, int mode,
-                     const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
+bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, const ResizeView &t,
                      uint8_t *gray, unsigned *hist, int batch, bool aligned16);
 void launch_yuv420_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int ystride, const YuvPlanes &p, uint8_t *dst, int dstride);
 void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,
                        int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot);
 void launch_pyr_integral(hipStream_t st, const uint8_t *aux, size_t aux_slot, const PyrLevelDev *levels, int nlev, int nimg,
                          int *sum, unsigned *sq32, size_t sum_slot, int P);
-void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
-                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
-                    int xmax, uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0);
-void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, int mode,
-                    const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta,
-                    int xmax, uint8_t *dst, int dw, int dh, int dstride);
+void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, const ResizeView &t,
+                    uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0);
+void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, const ResizeView &t,
+                    uint8_t *dst, int dw, int dh, int dstride);
 void launch_flip_h(hipStream_t st, const uint8_t *src, int w, int h, int spitch, uint8_t *dst, int dpitch, int batch = 1, size_t src_slot = 0,
                    size_t dst_slot = 0);
 void launch_hist(hipStream_t st, const uint8_t *gray, int w, int h, int pitch, unsigned *hist);
@@ -53,8 +51,7 @@ void launch_lut(hipStream_t st, unsigned *hist, int total, uint8_t *lut, int bat
 void launch_apply_lut(hipStream_t st, const uint8_t *src, int w, int h, int spitch, const uint8_t *lut,
                       uint8_t *dst, int dpitch, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0);
 void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, const int *d_lut_idx, const uint8_t *d_luts, int sh, int sstride,
-                        int mode, const int *d_xofs, const short *d_ialpha, const int *d_yofs, const short *d_ibeta, int xmax,
-                        uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch, const YuvPlanes *yuv = nullptr);
+                        const ResizeView &t, uint8_t *dst, int dw, int dh, int dstride, size_t dst_slot, unsigned *hist, int batch, const YuvPlanes *yuv = nullptr);
 void launch_colsum(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g,
                    unsigned *bandsum, unsigned *bandsq, int batch);
 void launch_bandscan(hipStream_t st, const PreGeom &g, unsigned *bandsum, unsigned *bandsq, int batch);
@@ -93,8 +90,7 @@ void launch_deep(hipStream_t st, const CascadeArgs &a, int batch);          // k
 // groupRectangles per frame on the device; out: [batch][2 + 4*out_cap] ints: count (-1 = host must group), raw count, boxes
 void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, int *out, int out_cap, int batch);     // kernels_group.hip
 // ---- image-to-overlay and view-* outlines on a device frame (kernels_draw.hip)
-void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const uint8_t *img, int ih, int istride, int cn,
-                    int mode, const int *xofs, const short *ialpha, const int *yofs, const short *ibeta, int xmax);
+void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const OverlayImage &o);
 void launch_draw_shapes(hipStream_t st, uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *d_shapes, int n,
                         int bx0, int by0, int bx1, int by1);
 // ---- the way out in 4:2:0 (kernels_yuv_out.hip): cv::cvtColor(CV_BGR2YUV_I420) into the planes of a layout, and the two drawing kernels

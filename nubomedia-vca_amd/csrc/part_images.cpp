@@ -63,13 +63,13 @@ int part_gray_eq(nvca_ctx *ctx, const void *const *bgr, int n, int w, int h, int
         bool wide = yuv_layout_aligned16(*yuv) && w % 16 == 0 && slot % 16 == 0 && ((uintptr_t)gray & 15) == 0;
         for (int k = 0; k < n; k++) wide = wide && ((uintptr_t)bgr[k] & 15) == 0;
         TimedLaunch t(ctx, NVCA_K_GRAY);
-        wide = launch_gray_yuv(ctx->cs(), (const uint8_t *const *)d_ptrs, g, yuv_planes(yuv), 0, nullptr, nullptr, nullptr, nullptr, w, gray, hist, n, wide);
+        wide = launch_gray_yuv(ctx->cs(), (const uint8_t *const *)d_ptrs, g, yuv_planes(yuv), ResizeView{}, gray, hist, n, wide);
         if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 eye gray of %d frame(s) %d x %d: %s\n", n, w, h, wide ? "k_gray_yuv16" : "k_gray_yuv_generic");
     } else {
       bool aligned = stride % 4 == 0 && w % 4 == 0 && slot % 4 == 0 && ((uintptr_t)gray & 3) == 0;
       for (int k = 0; k < n; k++) aligned = aligned && ((uintptr_t)bgr[k] & 3) == 0;
       TimedLaunch t(ctx, NVCA_K_GRAY);
-      launch_gray(ctx->cs(), (const uint8_t *const *)d_ptrs, g, 0, nullptr, nullptr, nullptr, nullptr, w, gray, hist, n, aligned); }
+      launch_gray(ctx->cs(), (const uint8_t *const *)d_ptrs, g, ResizeView{}, gray, hist, n, aligned); }
     { TimedLaunch t(ctx, NVCA_K_LUT); launch_lut(ctx->cs(), hist, w * h, luts, n, 1); }
     NVCA_LAUNCH_CHECK(ctx);
     return NVCA_OK;
@@ -93,8 +93,7 @@ int part_image_batch(nvca_ctx *ctx, const PartImageBatch &b, const uint8_t *luts
     if (b.post_eq && (size_t)(n + 1) * 256 > ctx->pw().luts.bytes) { ctx->set_error("internal: LUT storage"); return NVCA_ERR_ARG; }
     { TimedLaunch t(ctx, NVCA_K_RESIZE1);
       launch_work_resize(ctx->cs(), b.bgr, (const uint8_t *const *)d_tab, with_lut ? (const int *)((uint8_t *)d_tab + (size_t)n * sizeof(void *)) : nullptr, luts,
-                         b.sh, b.sstride, gp->tab.mode, gp->d_xofs.as<int>(), gp->d_ialpha.as<short>(), gp->d_yofs.as<int>(), gp->d_ibeta.as<short>(),
-                         gp->tab.xmax, b.dst, b.dw, b.dh, b.dw, b.slot, hist, n, b.yuv.fmt ? &b.yuv : nullptr); }
+                         b.sh, b.sstride, gp->view(), b.dst, b.dw, b.dh, b.dw, b.slot, hist, n, b.yuv.fmt ? &b.yuv : nullptr); }
     if (b.post_eq) {
         { TimedLaunch t(ctx, NVCA_K_LUT); launch_lut(ctx->cs(), hist, b.dw * b.dh, scratch, n, 1); }
         launch_apply_lut(ctx->cs(), b.dst, b.dw, b.dh, b.dw, scratch, b.dst, b.dw, n, b.slot, b.slot);

@@ -1,5 +1,6 @@
-// pixel_rules.h -- the per-pixel arithmetic that a host loop and a kernel share (one rule, two callers), and the cv::resize
-// tables both read.
+// pixel_rules.h -- the per-pixel arithmetic that a host loop and a kernel share (one rule, two callers): resize_sample, the one
+// statement of cv::resize(INTER_LINEAR) on 8-bit images, over the tables both read (ResizeTab, seen through a ResizeView); shape
+// coverage; the overlay blend; the 4:2:0 conversions.
 #pragma once
 #include <vector>
 #include "../../include/nubovca.h"
@@ -20,8 +21,52 @@ struct ResizeTab {
     int xmax = 0;
     std::vector<int> xofs, yofs;
     std::vector<short> ialpha, ibeta;
+    ResizeView view() const { return ResizeView{mode, xmax, xofs.data(), ialpha.data(), yofs.data(), ibeta.data()}; }
 };
 void build_resize_tab(int sw, int sh, int dw, int dh, ResizeTab &t);
+
+// Destination sample (x, y) of cv::resize(INTER_LINEAR) on an 8-bit image of N channels and `sh` rows (OpenCV 2.4 imgproc/imgwarp.cpp):
+// the identity, the exact-2x area shortcut, or the fixed-point bilinear path -- 11-bit coefficients, rows clamped to the image, the
+// horizontal pass of a row scaled down by 16 before the vertical one.  `tap(r, c, v)` leaves the N channel values of source pixel
+// (r, c) in v: a packed pixel, a gray byte, a gray byte through a LUT, a pixel converted where it is read.  The right-hand column
+// xofs[x] + 1 is tapped ONLY where x < xmax: from xmax on it does not exist, and on the last row of a tightly allocated image its
+// bytes lie outside the buffer.  Returns the integers: the caller keeps its own truncation (& 255, a uint8_t cast, none).
+template <int N, class Tap>
+NVCA_HD_INLINE void resize_sample(Tap tap, int sh, const ResizeView &t, int x, int y, int *out)
+{
+    if (t.mode == 0) { tap(y, x, out); return; }
+    if (t.mode == 2) {
+        int p[4][N];
+        tap(2 * y, 2 * x, p[0]); tap(2 * y, 2 * x + 1, p[1]); tap(2 * y + 1, 2 * x, p[2]); tap(2 * y + 1, 2 * x + 1, p[3]);
+        for (int k = 0; k < N; k++) out[k] = (p[0][k] + p[1][k] + p[2][k] + p[3][k] + 2) >> 2;
+        return;
+    }
+    int sy0 = t.yofs[y], sy1 = sy0 + 1;
+    sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
+    sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
+    const int sx = t.xofs[x], b0 = t.ibeta[2 * y], b1 = t.ibeta[2 * y + 1];
+    // the horizontal pass of the two rows.  Every tap stays inside its branch: a right-hand tap in front of the branch would read past
+    // the image where x >= xmax, and the left-hand taps in front of it make two dependent trips to memory a sample where one serves
+    // (measured on k_work_resize at ROI sizes: 8-11 % of its time)
+    int h0[N], h1[N];
+    if (x < t.xmax) {
+        const int a0 = t.ialpha[2 * x], a1 = t.ialpha[2 * x + 1];
+        int l0[N], r0[N], l1[N], r1[N];
+        tap(sy0, sx, l0); tap(sy0, sx + 1, r0); tap(sy1, sx, l1); tap(sy1, sx + 1, r1);
+        for (int k = 0; k < N; k++) { h0[k] = l0[k] * a0 + r0[k] * a1; h1[k] = l1[k] * a0 + r1[k] * a1; }
+    } else {
+        tap(sy0, sx, h0); tap(sy1, sx, h1);
+        for (int k = 0; k < N; k++) { h0[k] *= 2048; h1[k] *= 2048; }
+    }
+    for (int k = 0; k < N; k++) out[k] = (((b0 * (h0[k] >> 4)) >> 16) + ((b1 * (h1[k] >> 4)) >> 16) + 2) >> 2;
+}
+// channel k of that sample for a packed image of cn interleaved channels, cn known only at run time (the overlay image)
+NVCA_HD_INLINE int resize_sample_cn(const uint8_t *src, int sh, int sstride, int cn, const ResizeView &t, int x, int y, int k)
+{
+    int v;
+    resize_sample<1>([&](int r, int c, int *p) { p[0] = src[(size_t)r * sstride + (size_t)c * cn + k]; }, sh, t, x, y, &v);
+    return v;
+}
 
 // ---- view-* outlines (nvca_draw_shapes): one coverage rule for the host rasteriser and the kernel
 NVCA_HD inline bool shape_covers(const nvca_shape &sh, int px, int py)
@@ -40,6 +85,14 @@ NVCA_HD inline bool shape_covers(const nvca_shape &sh, int px, int py)
     if (py >= y0 && py <= y1 && (ax0 <= 1 || ax1 <= 1)) return true;          // the two vertical edges, 3 columns each
     const int mx = ax0 < ax1 ? ax0 : ax1, my = ay0 < ay1 ? ay0 : ay1;         // round joins: the 4-neighbourhood of a vertex
     return mx + my == 1;
+}
+// the box outside which shape_covers is false, unclipped: what a host loop walks and a launch covers
+struct ShapeBox { int x0, y0, x1, y1; };
+inline ShapeBox shape_bounds(const nvca_shape &sh)
+{
+    if (sh.kind == NVCA_SHAPE_RING4) { const int r = (sh.w > 0 ? sh.w : 0) + 2; return ShapeBox{sh.x - r, sh.y - r, sh.x + r, sh.y + r}; }
+    const int xe = sh.x + sh.w, ye = sh.y + sh.h;
+    return ShapeBox{(sh.x < xe ? sh.x : xe) - 1, (sh.y < ye ? sh.y : ye) - 1, (sh.x > xe ? sh.x : xe) + 1, (sh.y > ye ? sh.y : ye) + 1};
 }
 void draw_shapes_host(uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *shapes, int n);
 
@@ -85,27 +138,8 @@ void bgr_to_yuv420_host(const uint8_t *src, int w, int h, int stride, int channe
 void draw_shapes_yuv420_host(uint8_t *base, int w, int h, int ystride, const YuvPlanes &p, const nvca_shape *shapes, int n);
 
 // ---- image-to-overlay (nvca_overlay_blend): kms_face_detect_display_detections_overlay_img, FACE/kmsfacedetect.cpp:427-502.
-// One arithmetic for the host loop and the kernel (as for the outlines above).
-// Channel k of output pixel (x, y) of cvResize(costume, costumeAux, CV_INTER_LINEAR) on an 8-bit image with cn interleaved
-// channels: cv::resize's fixed-point bilinear path (11-bit coefficients, tables from build_resize_tab), its 2 x 2 area
-// shortcut, or the identity.
-NVCA_HD inline int resize_sample_cn(const uint8_t *src, int sh, int sstride, int cn, int mode, const int *xofs, const short *ialpha,
-                                    const int *yofs, const short *ibeta, int xmax, int x, int y, int k)
-{
-    if (mode == 0) return src[(size_t)y * sstride + (size_t)x * cn + k];
-    if (mode == 2) {
-        const uint8_t *s0 = src + (size_t)(2 * y) * sstride + (size_t)(2 * x) * cn + k, *s1 = s0 + sstride;
-        return (s0[0] + s0[cn] + s1[0] + s1[cn] + 2) >> 2;
-    }
-    int sy0 = yofs[y], sy1 = sy0 + 1;
-    sy0 = sy0 >= 0 ? (sy0 < sh ? sy0 : sh - 1) : 0;
-    sy1 = sy1 >= 0 ? (sy1 < sh ? sy1 : sh - 1) : 0;
-    const uint8_t *s0 = src + (size_t)sy0 * sstride + (size_t)xofs[x] * cn + k, *s1 = src + (size_t)sy1 * sstride + (size_t)xofs[x] * cn + k;
-    const bool inner = x < xmax;
-    const int a0 = inner ? ialpha[2 * x] : 2048, a1 = inner ? ialpha[2 * x + 1] : 0;
-    const int h0 = s0[0] * a0 + (inner ? s0[cn] * a1 : 0), h1 = s1[0] * a0 + (inner ? s1[cn] * a1 : 0);
-    return (((ibeta[2 * y] * (h0 >> 4)) >> 16) + ((ibeta[2 * y + 1] * (h1 >> 4)) >> 16) + 2) >> 2;
-}
+// One arithmetic for the host loop and the kernel (as for the outlines above): the scaled image is resize_sample's
+// (cvResize(costume, costumeAux, CV_INTER_LINEAR), tables from build_resize_tab), channel by channel.
 // the write of one overlay pixel v[0 .. cn) onto a BGR pixel of the frame (:467-490; SRC_OVERLAY is 1)
 NVCA_HD inline void overlay_pixel(uint8_t *px, const int *v, int cn)
 {
@@ -133,7 +167,7 @@ void overlay_blend_host(uint8_t *frame, int W, int H, int stride, const nvca_rec
 // pixel's BGR value as it is: its bytes stay).  A touched pixel's BGR value before the box is A.13 of its Y and the block's chroma;
 // overlay_pixel blends onto it; Y becomes A.14's Y of the result, and the block's chroma A.14's (U, V) of the blended top-left pixel if
 // that one is touched.  Everything is read before anything is written, and nothing outside the block is read: blocks are independent.
-struct OverlayImage { const uint8_t *img; int ih, istride, cn, mode, xmax; const int *xofs; const short *ialpha; const int *yofs; const short *ibeta; };
+struct OverlayImage { const uint8_t *img; int ih, istride, cn; ResizeView tab; };       // the image and its resize to one box's placed size
 NVCA_HD_INLINE void overlay_block_yuv(uint8_t *base, int W, int H, int ystride, const YuvPlanes &yp, const OverlayPlace &p, const OverlayImage &o, int cx, int cy)
 {
     uint8_t *pu = yuv_u_at(base, yp, cx, cy), *pv = yuv_v_at(base, yp, cx, cy);
@@ -145,7 +179,7 @@ NVCA_HD_INLINE void overlay_block_yuv(uint8_t *base, int W, int H, int ystride, 
         ny[j] = -1;
         if (x >= W || y >= H || w < 0 || h < 0 || w >= p.w || h >= p.h) continue;
         int v[4] = {0, 0, 0, 0};
-        for (int k = 0; k < o.cn; k++) v[k] = resize_sample_cn(o.img, o.ih, o.istride, o.cn, o.mode, o.xofs, o.ialpha, o.yofs, o.ibeta, o.xmax, w, h, k);
+        for (int k = 0; k < o.cn; k++) v[k] = resize_sample_cn(o.img, o.ih, o.istride, o.cn, o.tab, w, h, k);
         if (o.cn == 4 && v[3] == 0) continue;
         int B, G, R, Y, U, V;
         yuv_bgr(*yuv_luma_at(base, yp, ystride, x, y), c, B, G, R);

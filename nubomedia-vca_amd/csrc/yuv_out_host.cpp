@@ -26,10 +26,9 @@ void draw_shapes_yuv420_host(uint8_t *base, int w, int h, int ystride, const Yuv
 {
     for (int i = 0; i < n; i++) {
         const nvca_shape &sh = shapes[i];
-        int x0, y0, x1, y1, Y, U, V;
-        if (sh.kind == NVCA_SHAPE_RING4) { const int r = (sh.w > 0 ? sh.w : 0) + 2; x0 = sh.x - r; x1 = sh.x + r; y0 = sh.y - r; y1 = sh.y + r; }
-        else { x0 = std::min(sh.x, sh.x + sh.w) - 1; x1 = std::max(sh.x, sh.x + sh.w) + 1; y0 = std::min(sh.y, sh.y + sh.h) - 1; y1 = std::max(sh.y, sh.y + sh.h) + 1; }
-        x0 = std::max(x0, 0); y0 = std::max(y0, 0); x1 = std::min(x1, w - 1); y1 = std::min(y1, h - 1);
+        const ShapeBox b = shape_bounds(sh);
+        const int x0 = std::max(b.x0, 0), y0 = std::max(b.y0, 0), x1 = std::min(b.x1, w - 1), y1 = std::min(b.y1, h - 1);
+        int Y, U, V;
         bgr_yuv(sh.bgra[0], sh.bgra[1], sh.bgra[2], Y, U, V);
         for (int y = y0; y <= y1; y++)
             for (int x = x0; x <= x1; x++)
@@ -53,7 +52,7 @@ void overlay_blend_yuv420_host(uint8_t *base, int W, int H, int ystride, const Y
         if (x0 > x1 || y0 > y1) continue;
         ResizeTab tab;
         build_resize_tab(ov.width, ov.height, p.w, p.h, tab);
-        const OverlayImage o{(const uint8_t *)ov.data, ov.height, ov.stride, ov.channels, tab.mode, tab.xmax, tab.xofs.data(), tab.ialpha.data(), tab.yofs.data(), tab.ibeta.data()};
+        const OverlayImage o{(const uint8_t *)ov.data, ov.height, ov.stride, ov.channels, tab.view()};
         for (int cy = (int)(y0 >> 1); cy <= (int)(y1 >> 1); cy++)
             for (int cx = (int)(x0 >> 1); cx <= (int)(x1 >> 1); cx++) overlay_block_yuv(base, W, H, ystride, yp, p, o, cx, cy);
     }

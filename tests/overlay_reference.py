@@ -86,3 +86,20 @@ def overlay_blend(frame, boxes, image, off_x=0.0, off_y=0.0, wp=1.0, hp=1.0):
                 original = 1 - overlay
                 dst[:] = (src[:, :3] * overlay + dst.astype(np.float64) * original).astype(np.uint8)          # C cast: truncation
     return frame
+
+
+# (sw, sh, dw, dh) that reach every branch of cv::resize's 8-bit rule: identity, the exact-2x area shortcut, xmax == 0 (a one-column
+# source), rows clamped at both ends, one-row and one-column results, more than one 256-column block -- the table
+# tests/test_overlay_cpu.py (the host rule) and tests/test_gpu_resize_rule.py (every kernel with an entry point) run against the oracle
+RULE_SHAPES = [(1, 1, 5, 3), (2, 2, 1, 1), (3, 1, 7, 1), (2, 4, 1, 2), (1, 7, 4, 7), (5, 3, 1, 1), (4, 4, 2, 2), (2, 2, 3, 3), (33, 2, 7, 1),
+               (6, 2, 3, 1), (3, 3, 2, 2), (257, 5, 300, 9), (255, 3, 256, 3), (16, 16, 257, 2), (50, 40, 120, 90), (97, 61, 41, 29)]
+
+
+def rule_image(sw, sh, cn):
+    """the seeded source image of a RULE_SHAPES case; 4 channels: an alpha plane with zeros, full weights and everything between"""
+    rng = np.random.default_rng(sw * 1009 + sh * 31 + cn)
+    img = rng.integers(0, 256, (sh, sw) if cn == 1 else (sh, sw, cn)).astype(np.uint8)
+    if cn == 4:
+        pick = rng.random((sh, sw))
+        img[:, :, 3] = np.where(pick < 0.25, 0, np.where(pick < 0.5, 255, img[:, :, 3]))
+    return img

@@ -3,7 +3,7 @@
 import numpy as np
 import pytest
 
-from overlay_reference import overlay_blend as ref_blend, resize_linear_cn
+from overlay_reference import RULE_SHAPES, overlay_blend as ref_blend, resize_linear_cn, rule_image
 
 
 def test_reference_resize_equals_the_oracle_on_1_and_3_channels():
@@ -14,6 +14,24 @@ def test_reference_resize_equals_the_oracle_on_1_and_3_channels():
         assert np.array_equal(resize_linear_cn(g, dw, dh), orc.resize_linear(g, dw, dh)), (sh, sw, dh, dw)
         c = rng.integers(0, 256, (sh, sw, 3)).astype(np.uint8)
         assert np.array_equal(resize_linear_cn(c, dw, dh), orc.resize_linear(c, dw, dh)), (sh, sw, dh, dw)
+
+
+@pytest.mark.parametrize("cn", [1, 3])
+def test_host_rule_equals_the_oracle_resize(cn):
+    """the library's one statement of the rule (resize_sample, through the host overlay loop: one box of the destination size on a
+    zeroed frame) against the oracle's cv::resize, byte for byte; a 1-channel image lands replicated on B, G and R"""
+    import orc
+    from nubovca import capi
+    for (sw, sh, dw, dh) in RULE_SHAPES:
+        img = rule_image(sw, sh, cn)
+        exp = orc.resize_linear(img, dw, dh)
+        assert np.array_equal(resize_linear_cn(img, dw, dh), exp), (sw, sh, dw, dh)
+        frame = np.zeros((dh + 5, dw + 7, 3), np.uint8)
+        capi.overlay_blend(None, frame, [(3, 2, dw, dh)], img, 0.0, 0.0, 1.0, 1.0)
+        got = frame[2:2 + dh, 3:3 + dw].copy()
+        assert np.array_equal(got, exp if cn == 3 else np.repeat(exp[:, :, None], 3, axis=2)), (sw, sh, dw, dh)
+        frame[2:2 + dh, 3:3 + dw] = 0
+        assert not frame.any(), (sw, sh, dw, dh)
 
 
 @pytest.mark.parametrize("cn", [1, 3, 4])
