@@ -35,7 +35,9 @@ extern "C" {
 #define NVCA_ERR_IO         -4   /* cascade file unreadable                        */
 #define NVCA_ERR_PARSE      -5   /* cascade XML malformed                          */
 #define NVCA_ERR_UNSUPPORTED -6  /* tree-structured STAGE graph (parent / next), or a
-                                    feature that leaves the image at some scale    */
+                                    feature that leaves the image at some scale; a
+                                    new-format cascade that is not LBP with stumps; an
+                                    LBP cascade handed to a face or part stream      */
 #define NVCA_ERR_OVERFLOW   -7   /* more raw candidates than the context's cap     */
 #define NVCA_ERR_NOMEM      -8
 #define NVCA_ERR_INTERNAL   -9   /* an internal check failed (a device result out of range, an exception caught at the
@@ -153,12 +155,22 @@ const char *nvca_kernel_name(int k);
 /* ---- cascade: replaces cv::CascadeClassifier::load ---------------------
  * FACE/kmsfacedetect.cpp:162-177 (HAAR_CONF_FILE :40), EYE/kmseyedetect.cpp:27-29,
  * NOSE/kmsnosedetect.cpp:31-32, MOUTH/kmsmouthdetect.cpp:37-38, EAR/kmseardetect.cpp:29-31.
- * Old-format ("opencv-haar-classifier") XML only: stump or tree-structured weak classifiers, upright or tilted
- * features (cascades with trees / tilted features run through the general evaluator). */
+ * Both formats cv::CascadeClassifier::load reads (OpenCV 2.4 cascadedetect.cpp), told apart by the type_id of the first child
+ * of <opencv_storage>:
+ *  - old format ("opencv-haar-classifier"): stump or tree-structured weak classifiers, upright or tilted features (cascades
+ *    with trees / tilted features run through the general evaluator);
+ *  - new format ("opencv-cascade-classifier", what opencv_traincascade writes and OpenCV's lbpcascades/ hold): featureType LBP
+ *    with stump weak classifiers.  New-format HAAR and HOG cascades, stage types other than BOOST, trees
+ *    (maxDepth > 1) and maxCatCount != 256 are refused with NVCA_ERR_UNSUPPORTED.
+ * An LBP cascade goes through nvca_detect_multiscale / nvca_detect_raw on single images; the face and part streams refuse it
+ * (NVCA_ERR_UNSUPPORTED).  Its launches are booked under the existing timing slots: the evaluator's kernels under NVCA_K_STRIP
+ * ("window per lane"), the level resize and integral under NVCA_K_RESIZE1 / NVCA_K_INTEGRAL as CV_HAAR_SCALE_IMAGE books them. */
+#define NVCA_CASCADE_HAAR 0
+#define NVCA_CASCADE_LBP  1
 int  nvca_cascade_load_xml(nvca_ctx *ctx, const char *path, nvca_cascade **out);
 int  nvca_cascade_load_mem(nvca_ctx *ctx, const char *xml, int64_t len, nvca_cascade **out);
 void nvca_cascade_free(nvca_cascade *c);
-/* The loader alone: parses an old-format cascade on the host and reports its shape (any out pointer may be NULL) or the
+/* The loader alone: parses a cascade of either format on the host and reports its shape (any out pointer may be NULL) or the
  * loader's error text -- no device and no context needed, so cascade files can be checked on a box without a GPU.
  * Same status codes as nvca_cascade_load_mem. */
 int  nvca_cascade_validate_mem(const char *xml, int64_t len, int *win_w, int *win_h, int *n_stages, int *n_weak,
@@ -176,6 +188,15 @@ int  nvca_cascade_kind(const nvca_cascade *c, int *has_tilted, int *has_trees);
  * stage_sizes/stage_thr[n_stages] (stump cascades only) */
 int  nvca_cascade_dump(const nvca_cascade *c, int *rects, float *weights, float *thr,
                        float *left_val, float *right_val, int *stage_sizes, float *stage_thr);
+/* which branch of cv::CascadeClassifier::load (cascadedetect.cpp) took the file: NVCA_CASCADE_HAAR / NVCA_CASCADE_LBP, and the
+ * length of an LBP cascade's feature list (0 for an old-format cascade); either pointer may be NULL */
+int  nvca_cascade_format(const nvca_cascade *c, int *format, int *n_features);
+/* flat dump of an LBP cascade as cascadedetect.cpp's Data::read / LBPEvaluator::read keep it, for cross-checking the loader
+ * (any pointer may be NULL): rects[n_features*4] (x, y, w, h of the top-left cell), feature_idx[n_weak], subsets[n_weak*8],
+ * leaves[n_weak*2], stage_sizes / stage_thr[n_stages] -- thresholds as evaluated, after the 1e-5f.  NVCA_ERR_ARG for an
+ * old-format cascade (as nvca_cascade_dump answers for an LBP cascade; nvca_cascade_kind reports (0, 0) for one). */
+int  nvca_cascade_dump_lbp(const nvca_cascade *c, int *rects, int *feature_idx, int32_t *subsets, float *leaves,
+                           int *stage_sizes, float *stage_thr);
 
 /* ---- imgproc primitives (each = one cv:: call of the reference) -------- */
 /* cv::cvtColor(CV_BGR2GRAY) FACE/kmsfacedetect.cpp:806, TRK/gstnubotracker.cpp:356 (channels 4) */
@@ -274,7 +295,8 @@ int nvca_detect_multiscale(nvca_ctx *ctx, const nvca_cascade *cascade, const voi
                            int min_neighbors, int flags, int min_w, int min_h, int max_w,
                            int max_h, nvca_rect *out, int cap, int *n_out);
 /* raw candidates before groupRectangles, canonical (scale, y, x) order; not
- * defined for FIND_BIGGEST_OBJECT */
+ * defined for FIND_BIGGEST_OBJECT -- except with an LBP cascade, whose scan (cascadedetect.cpp, detectMultiScale on a
+ * new-format cascade) ignores flags altogether: every flags value gives the answer of 0 there */
 int nvca_detect_raw(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray, int w, int h,
                     int stride, int mem, double scale_factor, int flags, int min_w, int min_h,
                     int max_w, int max_h, nvca_rect *out, int cap, int *n_out);

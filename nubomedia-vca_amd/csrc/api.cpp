@@ -231,8 +231,10 @@ try {
     *out = nullptr;
     std::unique_ptr<nvca_cascade> c(new nvca_cascade());
     std::string err;
-    int rc = parse_cascade_xml(xml, (size_t)len, c->c, err);
+    CascadeFile f;
+    int rc = parse_cascade_file(xml, (size_t)len, f, err);
     if (rc) { ctx->set_error("cascade XML: " + err); return rc; }
+    c->c = std::move(f.haar); c->lbp = std::move(f.lbp); c->format = f.format;
     c->ctx = ctx;
     c->c.uid = ctx->next_uid++;
     *out = c.release();
@@ -246,14 +248,15 @@ int nvca_cascade_validate_mem(const char *xml, int64_t len, int *win_w, int *win
 try {
     if (err && err_cap > 0) err[0] = 0;
     if (!xml || len <= 0) return NVCA_ERR_ARG;
-    Cascade c;
+    CascadeFile f;
     std::string msg;
-    const int rc = parse_cascade_xml(xml, (size_t)len, c, msg);
+    const int rc = parse_cascade_file(xml, (size_t)len, f, msg);
     if (rc) { if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", msg.c_str()); return rc; }
-    if (win_w) *win_w = c.ow;
-    if (win_h) *win_h = c.oh;
-    if (n_stages) *n_stages = (int)c.stages.size();
-    if (n_weak) *n_weak = (int)c.cls.size();
+    const bool lbp = f.format == NVCA_CASCADE_LBP;
+    if (win_w) *win_w = f.haar.ow;
+    if (win_h) *win_h = f.haar.oh;
+    if (n_stages) *n_stages = lbp ? (int)f.lbp.stages.size() : (int)f.haar.stages.size();
+    if (n_weak) *n_weak = lbp ? (int)f.lbp.weak.size() : (int)f.haar.cls.size();
     return NVCA_OK;
 }
 NVCA_API_CATCH(nullptr)
@@ -317,8 +320,38 @@ try {
     if (!c) return NVCA_ERR_ARG;
     if (win_w) *win_w = c->c.ow;
     if (win_h) *win_h = c->c.oh;
-    if (n_stages) *n_stages = (int)c->c.stages.size();
-    if (n_weak) *n_weak = (int)c->c.cls.size();
+    const bool lbp = c->format == NVCA_CASCADE_LBP;
+    if (n_stages) *n_stages = lbp ? (int)c->lbp.stages.size() : (int)c->c.stages.size();
+    if (n_weak) *n_weak = lbp ? (int)c->lbp.weak.size() : (int)c->c.cls.size();
+    return NVCA_OK;
+}
+NVCA_API_CATCH((c ? c->ctx : nullptr))
+
+// which branch of cv::CascadeClassifier::load (cascadedetect.cpp) took the file
+int nvca_cascade_format(const nvca_cascade *c, int *format, int *n_features)
+try {
+    if (!c) return NVCA_ERR_ARG;
+    if (format) *format = c->format;
+    if (n_features) *n_features = c->format == NVCA_CASCADE_LBP ? (int)c->lbp.features.size() : 0;
+    return NVCA_OK;
+}
+NVCA_API_CATCH((c ? c->ctx : nullptr))
+
+// what cascadedetect.cpp's Data::read / LBPEvaluator::read keep of an LBP cascade, flat
+int nvca_cascade_dump_lbp(const nvca_cascade *c, int *rects, int *feature_idx, int32_t *subsets, float *leaves, int *stage_sizes, float *stage_thr)
+try {
+    if (!c || c->format != NVCA_CASCADE_LBP) return NVCA_ERR_ARG;
+    const LbpCascade &l = c->lbp;
+    for (size_t i = 0; i < l.features.size() && rects; i++) { rects[i * 4] = l.features[i].x; rects[i * 4 + 1] = l.features[i].y; rects[i * 4 + 2] = l.features[i].w; rects[i * 4 + 3] = l.features[i].h; }
+    for (size_t i = 0; i < l.weak.size(); i++) {
+        if (feature_idx) feature_idx[i] = l.weak[i].feature;
+        if (subsets) memcpy(subsets + i * 8, l.weak[i].subset, sizeof(int32_t) * 8);
+        if (leaves) { leaves[i * 2] = l.weak[i].leaf[0]; leaves[i * 2 + 1] = l.weak[i].leaf[1]; }
+    }
+    for (size_t s = 0; s < l.stages.size(); s++) {
+        if (stage_sizes) stage_sizes[s] = l.stages[s].count;
+        if (stage_thr) stage_thr[s] = l.stages[s].threshold;
+    }
     return NVCA_OK;
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))
@@ -335,7 +368,7 @@ NVCA_API_CATCH((c ? c->ctx : nullptr))
 int nvca_cascade_dump(const nvca_cascade *c, int *rects, float *weights, float *thr, float *left_val,
                       float *right_val, int *stage_sizes, float *stage_thr)
 try {
-    if (!c) return NVCA_ERR_ARG;
+    if (!c || c->format != NVCA_CASCADE_HAAR) return NVCA_ERR_ARG;
     if (!c->c.stump_based) return NVCA_ERR_UNSUPPORTED;
     for (size_t i = 0; i < c->c.cls.size(); i++) {
         const HaarNode &n = c->c.nodes[c->c.cls[i].first_node];

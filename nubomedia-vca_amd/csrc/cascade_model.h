@@ -35,7 +35,25 @@ struct Cascade {
     mutable std::vector<unsigned char> stage_rec_cache;   // StageRec[] (plan.cpp, built on first use: the summation-order proof is per cascade)
 };
 
+// --------------------------------------------------------------------------
+// Cascade as loaded from new-format XML (type_id="opencv-cascade-classifier"), featureType LBP, stump weak classifiers:
+// what OpenCV 2.4 cascadedetect.cpp (CascadeClassifier::Data::read, LBPEvaluator::read) keeps.  SURVEY.md A.15.
+// --------------------------------------------------------------------------
+struct LbpFeature { int x, y, w, h; };          // top-left cell of the 3 x 3 grid of w x h cells, window-relative
+struct LbpWeak { int feature; int32_t subset[8]; float leaf[2]; };      // vote = subset[code >> 5] & (1 << (code & 31)) ? leaf[0] : leaf[1]
+struct LbpStage { int first, count; float threshold; /* as evaluated: (float)value - 1e-5f */ };
+struct LbpCascade {
+    int ow = 0, oh = 0;
+    std::vector<LbpFeature> features;
+    std::vector<LbpWeak> weak;
+    std::vector<LbpStage> stages;
+};
+
+// a cascade file of either format: `format` says which model the loader filled (haar.ow / haar.oh hold the window either way)
+struct CascadeFile { int format = NVCA_CASCADE_HAAR; Cascade haar; LbpCascade lbp; };
+
 // returns NVCA_OK or NVCA_ERR_PARSE / NVCA_ERR_UNSUPPORTED; err gets a message
-int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err);
+int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err);      // old-format files only
+int parse_cascade_file(const char *text, size_t len, CascadeFile &out, std::string &err); // both formats, by the type_id of the first child of <opencv_storage>
 
 } // namespace nvca

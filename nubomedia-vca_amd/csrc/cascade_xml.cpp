@@ -10,6 +10,8 @@
 #include <cstdlib>
 #include <cmath>
 #include <cfloat>
+#include <cerrno>
+#include <climits>
 
 namespace nvca {
 namespace {
@@ -106,15 +108,18 @@ bool to_int(const std::string &s, int &v) {
     v = (int)l; return true;
 }
 
-} // namespace
-
-int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err)
+int parse_root(const char *text, size_t len, XNode &root, std::string &err)
 {
     XParser xp{text, text + len, {}};
     if (!xp.skip_misc()) { err = xp.err; return NVCA_ERR_PARSE; }
-    XNode root;
     if (!xp.parse_elem(root, 0)) { err = xp.err; return NVCA_ERR_PARSE; }
     if (root.name != "opencv_storage") { err = "root element is not <opencv_storage>"; return NVCA_ERR_PARSE; }
+    return NVCA_OK;
+}
+
+// the old-format branch (icvReadHaarClassifier)
+int parse_haar(const XNode &root, Cascade &out, std::string &err)
+{
     const XNode *cn = nullptr;
     for (auto &k : root.kids) if (k->type_id == "opencv-haar-classifier") { cn = k.get(); break; }
     if (!cn) { err = "no opencv-haar-classifier node (new-format cascades are not Haar old-format)"; return NVCA_ERR_PARSE; }
@@ -197,6 +202,134 @@ int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &e
     }
     if (out.stages.empty()) { err = "cascade has no stages"; return NVCA_ERR_PARSE; }
     return NVCA_OK;
+}
+
+// whitespace-separated decimal integers of a sequence node, each inside int32
+bool to_ints(const std::string &s, std::vector<int> &v)
+{
+    v.clear();
+    const char *p = s.c_str();
+    for (;;) {
+        while (*p == ' ' || *p == '\n' || *p == '\r' || *p == '\t') ++p;
+        if (!*p) return true;
+        char *e = nullptr;
+        errno = 0;
+        const long long l = strtoll(p, &e, 10);
+        if (e == p || errno == ERANGE || l < INT32_MIN || l > INT32_MAX) return false;
+        if (*e && *e != ' ' && *e != '\n' && *e != '\r' && *e != '\t') return false;
+        v.push_back((int)l);
+        p = e;
+    }
+}
+bool to_doubles(const std::string &s, std::vector<double> &v)
+{
+    v.clear();
+    const char *p = s.c_str();
+    for (;;) {
+        while (*p == ' ' || *p == '\n' || *p == '\r' || *p == '\t') ++p;
+        if (!*p) return true;
+        char *e = nullptr;
+        const double d = strtod(p, &e);
+        if (e == p || (*e && *e != ' ' && *e != '\n' && *e != '\r' && *e != '\t')) return false;
+        v.push_back(d);
+        p = e;
+    }
+}
+bool one_int(const XNode *n, int &v) { std::vector<int> t; if (!n || !to_ints(n->text, t) || t.size() != 1) return false; v = t[0]; return true; }
+std::string word(const XNode *n)
+{
+    std::string s = n ? n->text : std::string();
+    while (!s.empty() && (s.back() == ' ' || s.back() == '\n' || s.back() == '\r' || s.back() == '\t')) s.pop_back();
+    size_t b = 0;
+    while (b < s.size() && (s[b] == ' ' || s[b] == '\n' || s[b] == '\r' || s[b] == '\t')) b++;
+    return s.substr(b);
+}
+
+// the new-format branch (type_id="opencv-cascade-classifier"): what OpenCV 2.4 cascadedetect.cpp's CascadeClassifier::Data::read
+// and LBPEvaluator::read keep of an LBP cascade of stumps -- numbers parsed as double and kept as float, the stage threshold
+// less 1e-5f (subtracted in float), a stump's subset as eight int32 words
+int parse_lbp(const XNode &cn, LbpCascade &out, std::string &err)
+{
+    const XNode *stype = cn.child("stageType"), *ftype = cn.child("featureType"), *hn = cn.child("height"), *wn = cn.child("width");
+    const XNode *sparams = cn.child("stageParams"), *fparams = cn.child("featureParams"), *snum = cn.child("stageNum");
+    const XNode *stages = cn.child("stages"), *features = cn.child("features");
+    if (!stype || !ftype || !hn || !wn || !sparams || !fparams || !snum || !stages || !features) {
+        err = "new-format cascade without stageType/featureType/height/width/stageParams/featureParams/stageNum/stages/features"; return NVCA_ERR_PARSE;
+    }
+    if (word(stype) != "BOOST") { err = "stageType '" + word(stype) + "' is not supported (BOOST only)"; return NVCA_ERR_UNSUPPORTED; }
+    const std::string ft = word(ftype);
+    if (ft == "HAAR" || ft == "HOG") { err = "new-format " + ft + " cascades are not supported (LBP only)"; return NVCA_ERR_UNSUPPORTED; }
+    if (ft != "LBP") { err = "unknown featureType"; return NVCA_ERR_PARSE; }
+    if (!one_int(wn, out.ow) || !one_int(hn, out.oh) || out.ow <= 2 || out.oh <= 2 || out.ow > 1024 || out.oh > 1024) { err = "bad <width> / <height>"; return NVCA_ERR_PARSE; }
+    int v = 0, nstages = 0;
+    if (!one_int(sparams->child("maxWeakCount"), v)) { err = "stageParams without maxWeakCount"; return NVCA_ERR_PARSE; }
+    if (const XNode *md = sparams->child("maxDepth")) {
+        if (!one_int(md, v)) { err = "bad <maxDepth>"; return NVCA_ERR_PARSE; }
+        if (v > 1) { err = "weak classifiers with maxDepth > 1 (trees) are not supported"; return NVCA_ERR_UNSUPPORTED; }
+    }
+    if (!one_int(fparams->child("maxCatCount"), v)) { err = "featureParams without maxCatCount"; return NVCA_ERR_PARSE; }
+    if (v != 256) { err = "maxCatCount is not 256 (LBP codes are 8 bits)"; return NVCA_ERR_UNSUPPORTED; }
+    if (!one_int(snum, nstages)) { err = "bad <stageNum>"; return NVCA_ERR_PARSE; }
+
+    out.features.clear(); out.weak.clear(); out.stages.clear();
+    std::vector<int> iv; std::vector<double> dv;
+    for (auto &f : features->kids) {
+        const XNode *r = f->child("rect");
+        if (!r || !to_ints(r->text, iv) || iv.size() != 4) { err = "feature without a <rect> of four integers"; return NVCA_ERR_PARSE; }
+        // the 3 x 3 cells of w x h pixels lie inside the window: every corner the evaluator reads exists at every window position
+        if (iv[0] < 0 || iv[1] < 0 || iv[2] <= 0 || iv[3] <= 0 || iv[2] > out.ow || iv[3] > out.oh ||
+            (long long)iv[0] + 3ll * iv[2] > out.ow || (long long)iv[1] + 3ll * iv[3] > out.oh) { err = "feature rect outside the window"; return NVCA_ERR_PARSE; }
+        out.features.push_back(LbpFeature{iv[0], iv[1], iv[2], iv[3]});
+    }
+    for (auto &st : stages->kids) {
+        const XNode *sthr = st->child("stageThreshold"), *wk = st->child("weakClassifiers");
+        int mwc = 0; double d;
+        if (!sthr || !wk || !one_int(st->child("maxWeakCount"), mwc) || !to_double(sthr->text, d)) { err = "stage without maxWeakCount/stageThreshold/weakClassifiers"; return NVCA_ERR_PARSE; }
+        LbpStage ls; ls.first = (int)out.weak.size(); ls.count = (int)wk->kids.size();
+        ls.threshold = (float)d - 1e-5f;                  // THRESHOLD_EPS, subtracted in float
+        if (ls.count <= 0) { err = "empty stage"; return NVCA_ERR_PARSE; }
+        if (ls.count != mwc) { err = "stage's maxWeakCount disagrees with its weak classifiers"; return NVCA_ERR_PARSE; }
+        for (auto &w : wk->kids) {
+            const XNode *in = w->child("internalNodes"), *lv = w->child("leafValues");
+            if (!in || !lv || !to_ints(in->text, iv) || !to_doubles(lv->text, dv)) { err = "weak classifier without internalNodes/leafValues"; return NVCA_ERR_PARSE; }
+            if (iv.size() > 11 && iv.size() % 11 == 0 && dv.size() == iv.size() / 11 + 1) { err = "weak classifiers with more than one internal node (trees) are not supported"; return NVCA_ERR_UNSUPPORTED; }
+            if (iv.size() != 11 || iv[0] != 0 || iv[1] != -1 || dv.size() != 2) { err = "internalNodes is not '0 -1 featureIdx' and 8 subset words with two leaf values"; return NVCA_ERR_PARSE; }
+            if (iv[2] < 0 || (size_t)iv[2] >= out.features.size()) { err = "featureIdx outside the feature list"; return NVCA_ERR_PARSE; }
+            LbpWeak lw; lw.feature = iv[2];
+            for (int k = 0; k < 8; k++) lw.subset[k] = iv[3 + k];
+            lw.leaf[0] = (float)dv[0]; lw.leaf[1] = (float)dv[1];
+            out.weak.push_back(lw);
+        }
+        out.stages.push_back(ls);
+    }
+    if (out.stages.empty()) { err = "cascade has no stages"; return NVCA_ERR_PARSE; }
+    if ((int)out.stages.size() != nstages) { err = "stageNum disagrees with the stages"; return NVCA_ERR_PARSE; }
+    return NVCA_OK;
+}
+
+} // namespace
+
+int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err)
+{
+    XNode root;
+    if (int rc = parse_root(text, len, root, err)) return rc;
+    return parse_haar(root, out, err);
+}
+
+// cv::CascadeClassifier::load's dispatch (cascadedetect.cpp: Data::read, else the old-format cvLoad): the type_id of the first
+// child of <opencv_storage> decides the branch
+int parse_cascade_file(const char *text, size_t len, CascadeFile &out, std::string &err)
+{
+    XNode root;
+    if (int rc = parse_root(text, len, root, err)) return rc;
+    if (!root.kids.empty() && root.kids[0]->type_id == "opencv-cascade-classifier") {
+        out.format = NVCA_CASCADE_LBP;
+        const int rc = parse_lbp(*root.kids[0], out.lbp, err);
+        if (rc == NVCA_OK) { out.haar.ow = out.lbp.ow; out.haar.oh = out.lbp.oh; }
+        return rc;
+    }
+    out.format = NVCA_CASCADE_HAAR;
+    return parse_haar(root, out.haar, err);
 }
 
 } // namespace nvca

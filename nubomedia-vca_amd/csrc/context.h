@@ -92,7 +92,7 @@ struct KernelTimer {
 
 } // namespace nvca
 
-struct nvca_cascade { nvca::Cascade c; nvca_ctx *ctx; };
+struct nvca_cascade { nvca::Cascade c; nvca_ctx *ctx; nvca::LbpCascade lbp; int format = NVCA_CASCADE_HAAR; };      // format LBP: `lbp` is the model, c holds the window size and the uid
 
 namespace nvca {
 static constexpr int kLanes = 10;         // lane 0: the context's stream; 1 .. 7: the batched part detectors; 8: the face detector's second batch in flight; 9: the trackers

@@ -41,7 +41,7 @@ int nvca_detect_raw(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray
                     int cap, int *n_out)
 try {
     if (!n_out || cap < 0 || (cap > 0 && !out)) return NVCA_ERR_ARG;
-    if (flags & NVCA_HAAR_FIND_BIGGEST_OBJECT) return NVCA_ERR_ARG;
+    if ((flags & NVCA_HAAR_FIND_BIGGEST_OBJECT) && !(cascade && cascade->format == NVCA_CASCADE_LBP)) return NVCA_ERR_ARG;       // (an LBP cascade's scan ignores flags)
     std::vector<nvca_rect> r;
     int rc = detect_gray(ctx, cascade, gray, w, h, stride, mem, scale_factor, 0, flags, min_w, min_h, max_w, max_h, true, r);
     if (rc) return rc;

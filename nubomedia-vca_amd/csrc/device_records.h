@@ -218,6 +218,38 @@ struct CascadeArgs {
 #endif
 };
 
+// ---- new-format LBP cascades (kernels_cascade_lbp.hip)
+// A weak classifier as the evaluator reads it, wave-uniform (scalar loads): the 16 corners of its feature's 3 x 3 cells as element
+// offsets from the window's origin at ONE pitch (corner (r, c) at off[r * 4 + c]), the subset, the two leaves.  A plan holds the table
+// twice: at the pitch of the levels' sum planes and at the pitch of the stage-0 kernel's LDS tile.
+struct LbpWeakDev { int off[16]; int subset[8]; float leaf[2]; int pad[6]; };
+static_assert(sizeof(LbpWeakDev) == 128, "LbpWeakDev is fetched with wide scalar loads");
+struct LbpStageDev { int first, count; float thr; int pad; };
+// one pyramid level's scan grid: window origins (gx * step, gy * step), gx < nx, gy < ny; its stage-0 pass bits lie at
+// bits[bit_off + gy * wpr + (gx >> 5)], bit gx & 31; row_first: the level's first row in the walk kernel's row numbering
+struct LbpLevelDev { int plane_off, szw, szh, nx, ny, step, wpr, bit_off, row_first, pad0, pad1, pad2; };
+struct LbpTile { int level, tx, ty, pad; };       // 32 x 16 grid positions of a level from (tx * 32, ty * 16)
+static constexpr int kLbpTileW = 32, kLbpTileH = 16;
+// the stage-0 tile of the level's sum plane: every corner a 32 x 16-window tile reads at step 2 (step-1 tiles use its top-left part)
+NVCA_HD inline int lbp_tile_pitch(int ow) { return (kLbpTileW - 1) * 2 + ow + 1; }
+NVCA_HD inline int lbp_tile_rows(int oh, int step) { return (kLbpTileH - 1) * step + oh + 1; }
+struct LbpArgs {
+    const int *sum;                 // the levels' sum planes (one image)
+    int P, TP;                      // pitch of the planes / of the LDS tile (elements)
+    int ow, oh;
+    const LbpLevelDev *levels; int nlev;
+    const LbpStageDev *stages; int nstages;
+    const LbpWeakDev *gweak, *tweak;        // offsets at pitch P / at pitch TP
+    const LbpTile *tiles; int ntiles;
+    unsigned *bits, *bits2;         // per grid position of every level: passed stage 0 / passed the tile kernel's stages
+    int tile_stages;                // stages the tile kernel evaluates (the first min(nstages, 3))
+    int nrows;                      // scan rows of all levels
+    int key_sy, key_ss;             // candidate key = level << key_ss | gy << key_sy | gx
+    unsigned *cnt;                  // [0]: entries of the list the walk kernel fills, [g]: of the list stage group g leaves
+    unsigned *list[2]; unsigned list_cap;     // survivor keys, ping-pong between stage groups
+    unsigned long long *hits; unsigned hit_cap;       // hits[0] = exact count, hits[1 .. cap] = key (slot 0)
+};
+
 // ---- detectMultiScale on a small image in one workgroup (kernels_roi.hip)
 struct RoiStep {                  // one ladder step (scale-cascade scan) or one pyramid level (CV_HAAR_SCALE_IMAGE) of a job
     const TStumpRec *trecs;       // the cascade's stumps at this step's factor (levels: factor 1)

@@ -67,6 +67,7 @@ NVCA_API_CATCH_VOID
 int nvca_face_stream_create(nvca_ctx *ctx, const nvca_cascade *cascade, const nvca_face_params *params, nvca_face_stream **out)
 try {
     if (!ctx || !cascade || !out) return NVCA_ERR_ARG;
+    if (cascade->format != NVCA_CASCADE_HAAR) { ctx->set_error("face streams do not take an LBP cascade (nvca_detect_multiscale does)"); return NVCA_ERR_UNSUPPORTED; }
     nvca_face_stream *s = new (std::nothrow) nvca_face_stream();
     if (!s) return NVCA_ERR_NOMEM;
     s->ctx = ctx; s->cascade = cascade;

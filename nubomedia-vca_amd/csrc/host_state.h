@@ -62,7 +62,17 @@ struct RowCopy {
     int first = 0, period = 0, run = 0, count = 0;
 };
 
+// new-format LBP cascades (detect_job.cpp, lbp_plan): the evaluator's tables on the device and its arguments but for the
+// per-call buffers; the pyramid and the scan grids (hit_valid / hit_rect) are the GeomPlan's lv / det.specs
+struct LbpPlan {
+    DevBuf d_blob; LbpArgs args{};
+    size_t bit_words = 0, positions = 0;      // stage-0 pass bits (u32 words) and grid positions of all levels
+    int lds = 0;                              // bytes of the stage-0 tile (0: the window is too large, stage 0 gathers from the plane)
+    ~LbpPlan() { d_blob.release(); }
+};
+
 struct GeomPlan {
+    LbpPlan lbp;
     ResizeTab tab;
     RowCopy rowcopy;
     DevBuf d_xofs, d_yofs, d_ialpha, d_ibeta;
@@ -144,7 +154,7 @@ bool frames_aligned4(const nvca_frame *frames, const int *idx, int n);
 bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l);
 
 // ---- detectMultiScale jobs (detect_job.cpp, detect_rounds.cpp) and their small-image batches (roi_batch.cpp)
-enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT
+enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2, kJobLbp = 3 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT, a new-format LBP cascade (whatever the flags)
 enum JobPhase { kJobNew = 0, kJobFirstQueued = 1, kJobNarrowedQueued = 2, kJobDone = 3 };      // (narrowed: the second set of a FIND_BIGGEST search)
 
 struct DetectJob {
@@ -207,6 +217,8 @@ int roi_collect(nvca_ctx *ctx, RoiBatch &rb);
 // the pyramid levels of a CV_HAAR_SCALE_IMAGE call, smallest factor first, at most `cap` of them
 struct SiLevel { double factor; int szw, szh, winw, winh; };
 std::vector<SiLevel> si_levels(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t cap);
+// ... of detectMultiScale on a new-format cascade
+std::vector<SiLevel> lbp_levels(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t cap);
 int detect_job_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total);       // queue the job's next launch set
 int detect_job_advance(nvca_ctx *ctx, DetectJob &j);                          // after the stream has drained: consume what the set produced
 

@@ -1,0 +1,219 @@
+// kernels_cascade_lbp.hip -- the evaluator of new-format LBP cascades: OpenCV 2.4 cascadedetect.cpp, CascadeClassifierInvoker over
+// LBPEvaluator / predictCategoricalStump.  A window per lane, wave64; the weak-classifier records are
+// wave-uniform (scalar loads), the stage loop is wave-uniform.
+//
+//   k_lbp_stage0   the first stages (LbpArgs::tile_stages, at most 3) at EVERY grid position of every level, 32 x 16 positions per
+//                  workgroup, corners read from a tile of the level's sum plane staged in LDS; leaves two bits per position: passed
+//                  stage 0 (what the skip rule depends on), passed all of the tile's stages
+//   k_lbp_walk     a thread per scan row replays the serial walk's skip rule on the stage-0 bits (a stage-0 reject skips the next grid
+//                  column: visited[i] = visited[i-1] & pass[i-1] | visited[i-2] & !pass[i-2]) and lists the VISITED survivors of the
+//                  tile's stages -- a skipped column may have been evaluated there, it is never listed and so never emitted
+//   k_lbp_rest     stages [s0, s1) on a list of survivors, corners gathered from the plane; the survivors are compacted into the next
+//                  list (the host launches one per stage group), the last group appends to the candidate list
+//
+// The subset word of a vote is picked per lane by code >> 5 from eight words held in scalar registers: with seven compares and
+// selects -- indexing scalar registers by a vector value would make the compiler wrap the read in a waterfall loop, and an LDS copy
+// of the subsets would bound the cascade's length by the LDS left beside the tile.
+#include "launch.h"
+
+namespace nvca {
+
+// the LBP code of the window at `p` (its origin in the plane or in the tile; w.off at that array's pitch)
+__device__ __forceinline__ int lbp_code(const int *__restrict__ p, const LbpWeakDev &w)
+{
+    int v[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) v[k] = p[w.off[k]];
+    auto cell = [&](int r, int c) { return v[r * 4 + c] - v[r * 4 + c + 1] - v[r * 4 + 4 + c] + v[r * 4 + 5 + c]; };
+    const int ctr = cell(1, 1);
+    return (cell(0, 0) >= ctr ? 128 : 0) | (cell(0, 1) >= ctr ? 64 : 0) | (cell(0, 2) >= ctr ? 32 : 0) | (cell(1, 2) >= ctr ? 16 : 0) |
+           (cell(2, 2) >= ctr ? 8 : 0) | (cell(2, 1) >= ctr ? 4 : 0) | (cell(2, 0) >= ctr ? 2 : 0) | (cell(1, 0) >= ctr ? 1 : 0);
+}
+
+// predictCategoricalStump's vote: one of the two leaves
+__device__ __forceinline__ float lbp_vote(int code, const LbpWeakDev &w)
+{
+    const int i = code >> 5;
+    int word = w.subset[0];
+    word = i == 1 ? w.subset[1] : word; word = i == 2 ? w.subset[2] : word; word = i == 3 ? w.subset[3] : word;
+    word = i == 4 ? w.subset[4] : word; word = i == 5 ? w.subset[5] : word; word = i == 6 ? w.subset[6] : word;
+    word = i == 7 ? w.subset[7] : word;
+    return ((unsigned)word >> (code & 31)) & 1u ? w.leaf[0] : w.leaf[1];
+}
+
+// a stage on the window at p: the f32 sum of the votes in file order, one rounding per addition (this file is compiled with
+// -ffp-contract=off); false: tmp < thr, the window is rejected
+__device__ __forceinline__ bool lbp_stage(const int *__restrict__ p, const LbpWeakDev *__restrict__ weak, const LbpStageDev st)
+{
+    float tmp = 0.f;
+#pragma unroll 2          // the corner loads of two weak classifiers in flight at a time; the votes are still added one by one, in file order
+    for (int k = 0; k < st.count; k++) {
+        const LbpWeakDev &w = weak[st.first + k];
+        tmp += lbp_vote(lbp_code(p, w), w);
+    }
+    return !(tmp < st.thr);
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kLbpTileW * kLbpTileH) void k_lbp_stage0(LbpArgs a)
+{
+    extern __shared__ int lbp_tile[];
+    const LbpTile t = a.tiles[blockIdx.x];
+    if ((unsigned)t.level >= (unsigned)a.nlev) return;
+    const LbpLevelDev L = a.levels[t.level];
+    const int tid = threadIdx.x, lx = tid & (kLbpTileW - 1), ly = tid / kLbpTileW;
+    const int gx = t.tx * kLbpTileW + lx, gy = t.ty * kLbpTileH + ly;
+    const int X0 = t.tx * kLbpTileW * L.step, Y0 = t.ty * kLbpTileH * L.step;
+    const bool active = gx < L.nx && gy < L.ny;
+    const int *__restrict__ plane = a.sum + L.plane_off;
+    const int *p;
+    const LbpWeakDev *weak;
+    if (LDS) {
+        // every corner the tile's windows read: columns X0 .. X0 + 31 step + ow, rows Y0 .. Y0 + 15 step + oh of the (szw + 1) x (szh + 1) plane
+        const int tw = (kLbpTileW - 1) * L.step + a.ow + 1, th = lbp_tile_rows(a.oh, L.step);
+        for (int i = tid; i < tw * th; i += kLbpTileW * kLbpTileH) {
+            const int r = i / tw, c = i - r * tw;
+            lbp_tile[r * a.TP + c] = (Y0 + r <= L.szh && X0 + c <= L.szw) ? plane[(size_t)(Y0 + r) * a.P + X0 + c] : 0;
+        }
+        __syncthreads();
+        p = lbp_tile + ly * L.step * a.TP + lx * L.step; weak = a.tweak;        // (an idle lane's window lies inside the tile as well)
+    } else {
+        p = plane + (active ? (size_t)(gy * L.step) * a.P + gx * L.step : 0); weak = a.gweak;
+    }
+    const bool pass0 = lbp_stage(p, weak, a.stages[0]) && active;
+    bool alive = pass0;
+    for (int s = 1; s < a.tile_stages; s++) {          // (wave-uniform: a wave leaves when none of its windows is left)
+        if (!__ballot(alive)) break;
+        if (alive) alive = lbp_stage(p, weak, a.stages[s]);
+    }
+    // lanes 0 .. 31: row gy of the even lane rows, 32 .. 63: the row below
+    const unsigned long long m0 = __ballot(pass0), m1 = __ballot(alive);
+    if (lx == 0 && gy < L.ny) {
+        const size_t w = L.bit_off + (size_t)gy * L.wpr + t.tx;
+        a.bits[w] = (unsigned)(m0 >> (tid & 32));
+        a.bits2[w] = (unsigned)(m1 >> (tid & 32));
+    }
+}
+
+// The serial walk of a row (CascadeClassifierInvoker: "if result == 0, x += yStep") over the row's stage-0 bits, eight grid columns
+// a step: the walk is a two-state machine (the next column is jumped over or not), so a table gives, per state and byte of pass
+// bits, the columns visited and the state behind them.
+__global__ __launch_bounds__(64) void k_lbp_walk(LbpArgs a)
+{
+    __shared__ unsigned short lut[512];           // [state << 8 | pass bits] -> visited bits | state behind << 8
+    for (int e = threadIdx.x; e < 512; e += 64) {
+        bool skip = e >> 8;
+        unsigned vis = 0;
+        for (int b = 0; b < 8; b++) {
+            if (!skip) { vis |= 1u << b; skip = !((e >> b) & 1); }
+            else skip = false;
+        }
+        lut[e] = (unsigned short)(vis | (skip ? 256u : 0u));
+    }
+    __syncthreads();
+    // a lane per row; the lanes of the wave step through their rows' words together, so that the wave appends what its 64 rows
+    // found in a word with ONE atomic (a lane whose row has ended, or that has no row, takes part with nothing)
+    const int row = blockIdx.x * 64 + threadIdx.x, lane = threadIdx.x;
+    int lv = 0, gy = -1, wpr = 0;
+    const unsigned *rb = nullptr, *rb2 = nullptr;
+    if (row < a.nrows) {
+        while (lv + 1 < a.nlev && row >= a.levels[lv + 1].row_first) lv++;
+        const LbpLevelDev &L = a.levels[lv];
+        gy = row - L.row_first;
+        if (gy >= 0 && gy < L.ny) { wpr = L.wpr; rb = a.bits + L.bit_off + (size_t)gy * L.wpr; rb2 = a.bits2 + L.bit_off + (size_t)gy * L.wpr; }
+    }
+    const bool final = a.nstages <= a.tile_stages;
+    unsigned state = 0;                  // 256: the next column is jumped over (the one before it was visited and failed stage 0)
+    for (int k = 0; __ballot(k < wpr); k++) {
+        unsigned surv = 0;
+        if (k < wpr) {
+            const unsigned p = rb[k];
+            unsigned vis = 0;
+            for (int b = 0; b < 32; b += 8) {
+                const unsigned e = lut[state | ((p >> b) & 255u)];
+                vis |= (e & 255u) << b; state = e & 256u;
+            }
+            surv = vis & rb2[k];          // (bits behind the row's end are zero)
+        }
+        const int n = __popc(surv);
+        int incl = n;                     // inclusive prefix sum of n over the wave's lanes
+        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+        const int total = __shfl(incl, 63);
+        if (!total) continue;
+        unsigned long long base = 0;
+        if (lane == 0) base = final ? atomicAdd(a.hits, (unsigned long long)total) : (unsigned long long)atomicAdd(a.cnt, (unsigned)total);
+        base = __shfl(base, 0) + (unsigned long long)(incl - n);
+        for (int i = 0; surv; i++, surv &= surv - 1) {
+            const unsigned key = ((unsigned)lv << a.key_ss) | ((unsigned)gy << a.key_sy) | (unsigned)(k * 32 + __ffs(surv) - 1);
+            if (final) { if (base + i < a.hit_cap) a.hits[1 + base + i] = key; }
+            else if (base + i < a.list_cap) a.list[0][base + i] = key;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lbp_rest(LbpArgs a, int s0, int s1, int in, int in_cnt)
+{
+    unsigned n = a.cnt[in_cnt];
+    if (n > a.list_cap) n = a.list_cap;
+    const unsigned *__restrict__ src = in ? a.list[1] : a.list[0];
+    unsigned *__restrict__ dst = in ? a.list[0] : a.list[1];
+    const bool final = s1 >= a.nstages;
+    const int lane = threadIdx.x & 63;
+    for (unsigned i0 = blockIdx.x * 256u; i0 < n; i0 += gridDim.x * 256u) {          // (uniform per workgroup: the ballots below see whole waves)
+        const unsigned i = i0 + threadIdx.x;
+        bool alive = i < n;
+        unsigned key = 0; size_t off = 0;
+        if (alive) {
+            // a key comes from device memory: it is checked against the grids before it indexes the planes
+            key = src[i];
+            const unsigned lv = key >> a.key_ss, gy = (key >> a.key_sy) & ((1u << (a.key_ss - a.key_sy)) - 1u), gx = key & ((1u << a.key_sy) - 1u);
+            alive = lv < (unsigned)a.nlev;
+            if (alive) {
+                const LbpLevelDev &L = a.levels[lv];
+                alive = gx < (unsigned)L.nx && gy < (unsigned)L.ny;
+                if (alive) off = (size_t)L.plane_off + (size_t)(gy * L.step) * a.P + gx * L.step;
+            }
+        }
+        for (int s = s0; s < s1 && s < a.nstages; s++) {
+            if (!__ballot(alive)) break;
+            if (alive) alive = lbp_stage(a.sum + off, a.gweak, a.stages[s]);
+        }
+        const unsigned long long m = __ballot(alive);
+        if (!m) continue;
+        const int cntm = __popcll(m), rank = __popcll(m & ((1ull << lane) - 1ull));
+        if (final) {
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(a.hits, (unsigned long long)cntm);
+            base = __shfl(base, 0);
+            if (alive && base + rank < a.hit_cap) a.hits[1 + base + rank] = key;
+        } else {
+            unsigned base = 0;
+            if (lane == 0) base = atomicAdd(a.cnt + in_cnt + 1, (unsigned)cntm);
+            base = __shfl(base, 0);
+            if (alive && base + rank < a.list_cap) dst[base + rank] = key;
+        }
+    }
+}
+
+void launch_lbp_stage0(hipStream_t st, const LbpArgs &a, int lds)
+{
+    if (a.ntiles <= 0) return;
+    if (lds > 0) NVCA_LAUNCH(k_lbp_stage0<true>, dim3((unsigned)a.ntiles), dim3(kLbpTileW * kLbpTileH), (size_t)lds, st, a);
+    else NVCA_LAUNCH(k_lbp_stage0<false>, dim3((unsigned)a.ntiles), dim3(kLbpTileW * kLbpTileH), 0, st, a);
+}
+
+void launch_lbp_walk(hipStream_t st, const LbpArgs &a)
+{
+    if (a.nrows <= 0) return;
+    NVCA_LAUNCH(k_lbp_walk, dim3((unsigned)(a.nrows + 63) / 64), dim3(64), 0, st, a);
+}
+
+void launch_lbp_rest(hipStream_t st, const LbpArgs &a, int s0, int s1, int in, int in_cnt, unsigned max_items)
+{
+    if (max_items == 0 || s0 >= a.nstages) return;
+    unsigned blocks = (max_items + 255u) / 256u;
+    if (blocks > 4096u) blocks = 4096u;
+    NVCA_LAUNCH(k_lbp_rest, dim3(blocks), dim3(256), 0, st, a, s0, s1, in, in_cnt);
+}
+
+} // namespace nvca

@@ -89,6 +89,12 @@ int launch_band(hipStream_t st, const CascadeArgs &a, int batch, int *lds_grant)
 void launch_deep(hipStream_t st, const CascadeArgs &a, int batch);          // kernels_cascade_deep.hip
 // groupRectangles per frame on the device; out: [batch][2 + 4*out_cap] ints: count (-1 = host must group), raw count, boxes
 void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, int *out, int out_cap, int batch);     // kernels_group.hip
+// ---- new-format LBP cascades (kernels_cascade_lbp.hip): stage 0 of every grid position (pass bits), the serial walk's skip rule
+// per row + compaction of the visited survivors, then stages [s0, s1) on the survivors of list `in` (count cnt[in_cnt]) -- into the
+// other list and cnt[in_cnt + 1], or, when s1 is the last stage, into the candidate list.  lds: stage-0 tile bytes (0: gather from global)
+void launch_lbp_stage0(hipStream_t st, const LbpArgs &a, int lds);
+void launch_lbp_walk(hipStream_t st, const LbpArgs &a);
+void launch_lbp_rest(hipStream_t st, const LbpArgs &a, int s0, int s1, int in, int in_cnt, unsigned max_items);
 // ---- image-to-overlay and view-* outlines on a device frame (kernels_draw.hip)
 void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const OverlayImage &o);
 void launch_draw_shapes(hipStream_t st, uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *d_shapes, int n,

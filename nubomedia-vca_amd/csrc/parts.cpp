@@ -46,6 +46,9 @@ int nvca_part_stream_create(nvca_ctx *ctx, const nvca_part_params *params, const
 try {
     if (!ctx || !params || !face || !a || !out || params->kind < NVCA_PART_EYE || params->kind > NVCA_PART_EAR) return NVCA_ERR_ARG;
     if ((params->kind == NVCA_PART_EYE || params->kind == NVCA_PART_EAR) && !b) return NVCA_ERR_ARG;
+    if (face->format != NVCA_CASCADE_HAAR || a->format != NVCA_CASCADE_HAAR || (b && b->format != NVCA_CASCADE_HAAR)) {
+        ctx->set_error("part streams do not take an LBP cascade in any role (nvca_detect_multiscale does)"); return NVCA_ERR_UNSUPPORTED;
+    }
     nvca_part_stream *s = new (std::nothrow) nvca_part_stream();
     if (!s) return NVCA_ERR_NOMEM;
     s->ctx = ctx; s->p = *params; s->face = face; s->a = a; s->b = b;

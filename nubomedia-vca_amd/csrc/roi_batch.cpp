@@ -17,7 +17,7 @@ static constexpr int kRoiMaxWords = 14848;          // (cols + 1) * (rows + 2) w
 bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round)
 {
     const Cascade &c = j.rq.casc->c;
-    if (!ctx->sw.roi) return false;
+    if (!ctx->sw.roi || j.rq.kind == kJobLbp) return false;
     if (!c.stump_based || c.has_tilted || (j.rq.nimg != 1 && j.rq.mem != NVCA_MEM_DEVICE)) return false;
     if ((long long)(j.rq.cols + 1) * (j.rq.rows + 2) > kRoiMaxWords || j.rq.cols < 1 || j.rq.rows < 1) return false;
     if (j.rq.mem != NVCA_MEM_DEVICE && njobs_in_round != 1) return false;       // a host image is staged in the lane's one gray buffer

@@ -19,6 +19,7 @@ HAAR_DO_CANNY_PRUNING, HAAR_SCALE_IMAGE, HAAR_FIND_BIGGEST_OBJECT, HAAR_DO_ROUGH
 SUM_F32PAIR, SUM_F64 = 0, 1
 K_COUNT = 14
 PIX_BGR, PIX_NV12, PIX_I420 = 0, 1, 2
+CASCADE_HAAR, CASCADE_LBP = 0, 1
 
 
 class NvcaError(RuntimeError):
@@ -98,7 +99,7 @@ SYMBOLS = [
     "nvca_cascade_validate_mem", "nvca_abi_selftest", "nvca_ctx_set_option", "nvca_ctx_get_option", "nvca_overlay_blend",
     "nvca_part_batch_submit", "nvca_part_batch_collect", "nvca_face_stream_set_input", "nvca_yuv420_to_bgr",
     "nvca_part_stream_set_input", "nvca_tracker_set_input", "nvca_bgr_to_yuv420", "nvca_draw_shapes_yuv420",
-    "nvca_overlay_blend_yuv420",
+    "nvca_overlay_blend_yuv420", "nvca_cascade_format", "nvca_cascade_dump_lbp",
 ]
 
 _lib = None
@@ -169,6 +170,8 @@ def load():
     L.nvca_integral.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.nvca_integral_tilted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
     L.nvca_cascade_kind.argtypes = [vp, ip, ip]
+    L.nvca_cascade_format.argtypes = [vp, ip, ip]
+    L.nvca_cascade_dump_lbp.argtypes = [vp, ip, ip, C.POINTER(C.c_int32), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
     L.nvca_detect_multiscale.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
     L.nvca_detect_raw.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
@@ -509,6 +512,24 @@ class Cascade:
                                                     thr.ctypes.data_as(fp), lv.ctypes.data_as(fp), rv.ctypes.data_as(fp),
                                                     ss.ctypes.data_as(ip), st.ctypes.data_as(fp)))
         return dict(size=(ow, oh), rects=rects, weights=wts, thr=thr, left=lv, right=rv, stage_sizes=ss, stage_thr=st)
+
+    def format(self):
+        """(CASCADE_HAAR or CASCADE_LBP, length of an LBP cascade's feature list)"""
+        f, n = C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.L.nvca_cascade_format(self.h, C.byref(f), C.byref(n)))
+        return f.value, n.value
+
+    def dump_lbp(self):
+        """an LBP cascade as the loader keeps it (stage thresholds as evaluated, after the 1e-5f); ERR_ARG for an old-format cascade"""
+        ow, oh, ns, nw = self.info()
+        nf = self.format()[1]
+        rects, fidx = np.zeros((nf, 4), np.int32), np.zeros(nw, np.int32)
+        subsets, leaves = np.zeros((nw, 8), np.int32), np.zeros((nw, 2), np.float32)
+        ss, st = np.zeros(ns, np.int32), np.zeros(ns, np.float32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        self.ctx.check(self.ctx.L.nvca_cascade_dump_lbp(self.h, rects.ctypes.data_as(ip), fidx.ctypes.data_as(ip), subsets.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        leaves.ctypes.data_as(fp), ss.ctypes.data_as(ip), st.ctypes.data_as(fp)))
+        return dict(size=(ow, oh), rects=rects, feature_idx=fidx, subsets=subsets, leaves=leaves, stage_sizes=ss, stage_thr=st)
 
     def free(self):
         if self.h:

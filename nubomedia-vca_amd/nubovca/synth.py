@@ -541,3 +541,135 @@ def calibrated_part_cascade_xml(name, seed=None, n_images=8, pass_rate=0.65):
         c["name"] = "synthetic_%s_calibrated" % name
         _CALIB_CACHE[key] = cascade_to_xml(c)
     return _CALIB_CACHE[key]
+
+
+# ------------------------------------------------------------------ new-format LBP cascades
+_LBP_BITS = ((0, 0, 128), (0, 1, 64), (0, 2, 32), (1, 2, 16), (2, 2, 8), (2, 1, 4), (2, 0, 2), (1, 0, 1))
+
+
+def _lbp_codes(S, feat, xs, ys):
+    """LBP codes of feature (x, y, w, h) at the window origins ys x xs of an image with integral S: [len(ys), len(xs)] ints"""
+    x, y, w, h = feat
+    P = [[S[np.ix_(ys + y + r * h, xs + x + c * w)] for c in range(4)] for r in range(4)]
+    cell = [[P[r][c] - P[r][c + 1] - P[r + 1][c] + P[r + 1][c + 1] for c in range(3)] for r in range(3)]
+    code = np.zeros(cell[0][0].shape, np.int64)
+    for r, c, bit in _LBP_BITS:
+        code += bit * (cell[r][c] >= cell[1][1])
+    return code
+
+
+def _integral_np(img):
+    S = np.zeros((img.shape[0] + 1, img.shape[1] + 1), np.int64)
+    S[1:, 1:] = np.cumsum(np.cumsum(img.astype(np.int64), axis=0), axis=1)
+    return S
+
+
+def lbp_template(ow, oh):
+    """TEMPLATE stretched to an ow x oh window (float)"""
+    T = template()
+    n = T.shape[0]
+    ys = (np.arange(oh) + 0.5) * n / oh - 0.5
+    xs = (np.arange(ow) + 0.5) * n / ow - 0.5
+    y0 = np.clip(np.floor(ys).astype(int), 0, n - 2); x0 = np.clip(np.floor(xs).astype(int), 0, n - 2)
+    fy = np.clip(ys - y0, 0, 1)[:, None]; fx = np.clip(xs - x0, 0, 1)[None, :]
+    return (T[y0][:, x0] * (1 - fx) + T[y0][:, x0 + 1] * fx) * (1 - fy) + (T[y0 + 1][:, x0] * (1 - fx) + T[y0 + 1][:, x0 + 1] * fx) * fy
+
+
+def paste_lbp_faces(gray, faces, ow, oh, seed=0):
+    """copy of `gray` with the ow x oh template pasted at every (x, y, scale): a box of round(ow * scale) x round(oh * scale)"""
+    rng = np.random.default_rng(seed ^ 0x1B9)
+    g = gray.astype(np.float64)
+    H, W = g.shape
+    for (x, y, scale) in faces:
+        w, h = int(round(ow * scale)), int(round(oh * scale))
+        patch = lbp_template(w, h) + rng.normal(0, 1.0, size=(h, w))
+        g[y:y + h, x:x + w] = patch[:max(0, min(h, H - y)), :max(0, min(w, W - x))]
+    return np.clip(np.rint(g), 0, 255).astype(np.uint8)
+
+
+def lbp_calibration_images(n=4, W=320, H=240):
+    """the images make_lbp_cascade calibrates on by default: seeds no test image uses (frame_seed(7, 9000 + i))"""
+    return [make_gray(W, H, frame_seed(7, 9000 + i), "natural") for i in range(n)]
+
+
+def make_lbp_cascade(ow=24, oh=24, seed=1, stage_sizes=(3, 4, 5, 6, 7, 8, 9), pass_rate=0.5, calibrate_on=None):
+    """A new-format LBP cascade of stumps as a dict: size=(ow, oh), features=[(x, y, w, h)], stages=[dict(threshold=the file's
+    value, weak=[dict(feature=index, subset=[8 int32], leaves=(l0, l1))])].  Every weak classifier votes its higher leaf for the
+    stretched TEMPLATE (and for the codes one bit away from the template's), so pasted templates pass every stage; the stage
+    thresholds are calibrated on `calibrate_on` (gray images disjoint from any test image; default lbp_calibration_images()) so
+    that each stage passes about `pass_rate` of the windows that reach it, for as long as the sample lasts."""
+    rng = np.random.default_rng(seed)
+    imgs = lbp_calibration_images() if calibrate_on is None else list(calibrate_on)
+    tmpl = np.clip(np.rint(lbp_template(ow, oh)), 0, 255).astype(np.uint8)
+    St = _integral_np(tmpl)
+    z = np.zeros(1, np.int64)
+    # the calibration sample: every second window of each image and of its 2x decimation
+    sample = []
+    for im in imgs:
+        for lev in (im, im[::2, ::2]):
+            if lev.shape[0] > oh and lev.shape[1] > ow:
+                sample.append((_integral_np(lev), np.arange(0, lev.shape[1] - ow, 2), np.arange(0, lev.shape[0] - oh, 2)))
+    alive = [np.ones((len(ys), len(xs)), bool) for (_, xs, ys) in sample]
+    features, stages = [], []
+    for n in stage_sizes:
+        weak, sums, hi = [], [np.zeros(a.shape, np.float32) for a in alive], np.float32(0)
+        for _ in range(n):
+            w = int(rng.integers(1, max(2, ow // 3 + 1))); h = int(rng.integers(1, max(2, oh // 3 + 1)))
+            x = int(rng.integers(0, ow - 3 * w + 1)); y = int(rng.integers(0, oh - 3 * h + 1))
+            features.append((x, y, w, h))
+            ct = int(_lbp_codes(St, features[-1], z, z)[0, 0])
+            good = np.zeros(256, bool)
+            good[rng.random(256) < 0.3] = True
+            good[[ct] + [ct ^ (1 << b) for b in range(8)]] = True
+            a, b = np.float32(rng.uniform(0.3, 1.0)), np.float32(rng.uniform(0.3, 1.0))
+            flip = bool(rng.integers(0, 2))                 # which leaf is the high one: a set subset bit selects leaves[0]
+            bits = good if not flip else ~good
+            words = np.packbits(bits.reshape(8, 32), axis=1, bitorder="little").view("<u4").reshape(8).astype(np.uint32).view(np.int32)
+            leaves = (float(a), float(-b)) if not flip else (float(-b), float(a))
+            weak.append(dict(feature=len(features) - 1, subset=[int(v) for v in words], leaves=leaves))
+            hi = np.float32(hi + a)
+            lut = np.where(bits, np.float32(leaves[0]), np.float32(leaves[1])).astype(np.float32)
+            for k, (S, xs, ys) in enumerate(sample):
+                sums[k] = (sums[k] + lut[_lbp_codes(S, features[-1], xs, ys)]).astype(np.float32)
+        reach = np.concatenate([s[a] for s, a in zip(sums, alive)]) if alive else np.zeros(0, np.float32)
+        thr = float(np.quantile(reach, 1.0 - pass_rate)) if len(reach) >= 16 else 0.35 * float(hi)
+        thr = min(thr, 0.7 * float(hi))                     # pasted templates (every vote high, but for noise) stay in
+        thr = float(np.float32(thr))
+        alive = [a & (s >= np.float32(thr)) for s, a in zip(sums, alive)]
+        stages.append(dict(threshold=thr, weak=weak))
+    return dict(name="synthetic_lbp", size=(ow, oh), features=features, stages=stages)
+
+
+def lbp_cascade_to_xml(casc, style="traincascade"):
+    """The cascade as opencv_traincascade writes it (style "traincascade": every stageParams / featureParams field, stage
+    comments) or as lbpcascade_frontalface.xml holds it (style "minimal": stageParams with maxWeakCount alone)."""
+    assert style in ("traincascade", "minimal")
+    ow, oh = casc["size"]
+    mwc = max(len(s["weak"]) for s in casc["stages"])
+    o = ['<?xml version="1.0"?>', "<opencv_storage>", '<cascade type_id="opencv-cascade-classifier">', "  <stageType>BOOST</stageType>",
+         "  <featureType>LBP</featureType>", "  <height>%d</height>" % oh, "  <width>%d</width>" % ow, "  <stageParams>"]
+    if style == "traincascade":
+        o += ["    <boostType>GAB</boostType>", "    <minHitRate>9.9500000476837158e-01</minHitRate>", "    <maxFalseAlarm>5.0000000000000000e-01</maxFalseAlarm>",
+              "    <weightTrimRate>9.4999999999999996e-01</weightTrimRate>", "    <maxDepth>1</maxDepth>"]
+    o += ["    <maxWeakCount>%d</maxWeakCount></stageParams>" % mwc, "  <featureParams>", "    <maxCatCount>256</maxCatCount>"]
+    if style == "traincascade":
+        o += ["    <featSize>1</featSize>"]
+    o[-1] += "</featureParams>"
+    o += ["  <stageNum>%d</stageNum>" % len(casc["stages"]), "  <stages>"]
+    for si, st in enumerate(casc["stages"]):
+        if style == "traincascade":
+            o.append("    <!-- stage %d -->" % si)
+        o += ["    <_>", "      <maxWeakCount>%d</maxWeakCount>" % len(st["weak"]), "      <stageThreshold>%s</stageThreshold>" % _f(st["threshold"]), "      <weakClassifiers>"]
+        for w in st["weak"]:
+            o += ["        <_>", "          <internalNodes>", "            0 -1 %d %s</internalNodes>" % (w["feature"], " ".join(str(int(v)) for v in w["subset"])),
+                  "          <leafValues>", "            %s %s</leafValues></_>" % (_f(w["leaves"][0]), _f(w["leaves"][1]))]
+        o += ["      </weakClassifiers></_>"]
+    o += ["  </stages>", "  <features>"]
+    for (x, y, w, h) in casc["features"]:
+        o += ["    <_>", "      <rect>", "        %d %d %d %d</rect></_>" % (x, y, w, h)]
+    o += ["  </features></cascade>", "</opencv_storage>", ""]
+    return "\n".join(o)
+
+
+def lbp_cascade_xml(style="traincascade", **kw):
+    return lbp_cascade_to_xml(make_lbp_cascade(**kw), style)
