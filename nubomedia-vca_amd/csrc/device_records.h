@@ -179,6 +179,15 @@ struct CompAcc { int minx, miny, maxx, maxy, seed, pad; };   // per root, stored
 inline size_t tracker_count_offset(int w, int h, int batch) { return ((size_t)((w + 255) / 256) * h * batch + 63) & ~(size_t)63; }
 inline size_t tracker_flag_bytes(int w, int h, int batch) { return tracker_count_offset(w, h, batch) + sizeof(int) * (size_t)batch; }   // flag bytes, then a live-segment count per slot
 
+// A candidate's key is scale << key_ss | row << key_sy | column of its window, each field as wide as the plan's own grids need
+// (CascadeArgs / LbpArgs: key_sy = bx, key_ss = bx + by): the widths for grids of at most max_nx x max_ny windows on nscales
+// scales.  A field is at least one bit wide; whether the three fit a key is the caller's refusal.
+inline int key_field_bits(size_t n) { int b = 1; while ((1ull << b) < n) b++; return b; }
+inline void candidate_key_bits(size_t max_nx, size_t max_ny, size_t nscales, int *bx, int *by, int *bs)
+{
+    *bx = key_field_bits(max_nx); *by = key_field_bits(max_ny); *bs = key_field_bits(nscales);
+}
+
 struct CascadeArgs {
     const int *sum; const unsigned long long *sqsum;
     size_t sum_slot;               // elements between slots

@@ -1,13 +1,15 @@
 // host_state.h -- host-side state and helpers that the library's host sources share (not part of the ABI): the workspace, the
-// cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect_job.cpp, detect_rounds.cpp,
-// roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, part_logic.cpp, fb_search.cpp, part_stats.cpp,
-// options.cpp, cascade_xml.cpp and work_pool.cpp do not include it: the CPU drivers under tests/ build those without it (part_logic.cpp,
-// fb_search.cpp, part_stats.cpp and options.cpp without any HIP header, the others with host doubles of their own).
+// cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect_job.cpp, lbp_job.cpp, pyramid.cpp,
+// detect_rounds.cpp, roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, part_logic.cpp, fb_search.cpp,
+// part_stats.cpp, options.cpp, cascade_xml.cpp, pyr_levels.cpp, lbp_tables.cpp and work_pool.cpp do not include it: the CPU drivers under
+// tests/ build those without it (part_logic.cpp, fb_search.cpp, part_stats.cpp, options.cpp, pyr_levels.cpp and lbp_tables.cpp without any
+// HIP header, the others with host doubles of their own).
 #pragma once
 #include "context.h"
 #include "plan.h"
 #include "fb_search.h"
 #include "host_math.h"
+#include "pyr_levels.h"
 
 namespace nvca {
 
@@ -53,7 +55,6 @@ struct Workspace {
 };
 
 // one cached geometry: source frame -> working image -> scan tables
-struct PyrLevel { double f; int szw, szh, winw, winh; size_t gray_off; int gpitch; int plane_off; };
 // Source rows a shrinking bilinear resize reads, when they form equal runs at a fixed period (integer ratios: a 1080p
 // frame shrunk by 12 reads rows 12k + 5 and 12k + 6 only).  Host frames then cross PCIe as one strided 2-D copy of those
 // rows -- into their natural places of the staged frame, so the kernels are unchanged -- instead of whole.
@@ -62,7 +63,7 @@ struct RowCopy {
     int first = 0, period = 0, run = 0, count = 0;
 };
 
-// new-format LBP cascades (detect_job.cpp, lbp_plan): the evaluator's tables on the device and its arguments but for the
+// new-format LBP cascades (lbp_job.cpp, lbp_plan; the tables: lbp_tables.cpp): the evaluator's tables on the device and its arguments but for the
 // per-call buffers; the pyramid and the scan grids (hit_valid / hit_rect) are the GeomPlan's lv / det.specs
 struct LbpPlan {
     DevBuf d_blob; LbpArgs args{};
@@ -82,7 +83,7 @@ struct GeomPlan {
     bool has_det = false;
     uint64_t last_use = 0;                                    // plan cache is LRU-bounded (store_plan)
     int inflight = 0;                                         // batches in flight that reference this plan: never evicted
-    // CV_HAAR_SCALE_IMAGE: pyramid levels, their resize tables, plane layout
+    // CV_HAAR_SCALE_IMAGE / LBP: pyramid levels, their resize tables, plane layout (pyr_layout's result)
     std::vector<PyrLevel> lv;
     std::vector<std::unique_ptr<GeomPlan>> level_tabs;
     size_t gray_total = 0, plane_total = 0; int P = 0;
@@ -109,6 +110,13 @@ struct CascadeJob {
 };
 
 // ---- plans.cpp
+// several tables in one device allocation and one copy: add() copies an item in (h == nullptr: zeros) and returns its offset, a
+// multiple of 256; after upload() the items lie at blob.p + offset
+struct TableBlob {
+    std::vector<unsigned char> bytes;
+    size_t add(const void *h, size_t n);
+    int upload(nvca_ctx *ctx, DevBuf &blob);
+};
 void make_geom(PreGeom &g, int sw, int sh, int sstride, int cn, int w, int h);
 int ensure_ws(nvca_ctx *ctx, const PreGeom &g, int batch);
 int upload_tabs(nvca_ctx *ctx, std::vector<std::unique_ptr<GeomPlan>> &levels, DevBuf &blob);
@@ -212,13 +220,21 @@ bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round);
 int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j);
 int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap);
 int roi_collect(nvca_ctx *ctx, RoiBatch &rb);
+// the candidates roi_collect handed a job, in the serial order, as rectangles (sc: their ladder steps)
+int roi_job_candidates(nvca_ctx *ctx, DetectJob &j, std::vector<std::vector<nvca_rect>> &raw, std::vector<char> &grouped, std::vector<std::vector<int>> &sc);
+
+// ---- pyramid.cpp: a plan's pyramid (layout: pyr_levels.h) on the device, and a job's images resized to its levels and integrated
+int pyr_plan_tabs(nvca_ctx *ctx, GeomPlan &np, int cols, int rows, const std::vector<SiLevel> &levels);      // layout and resize tables
+int pyr_upload_levels(nvca_ctx *ctx, GeomPlan &np);                                                         // the device level table
+int pyr_plan_init(nvca_ctx *ctx, GeomPlan &np, int cols, int rows, const std::vector<SiLevel> &levels);      // both, one after the other
+ScaleSpec level_spec(int P, const PyrLevel &L, int ow, int oh, int adaptive);                                // a level's scan grid
+bool job_images_in_place(const DetectJob &j, size_t *slot);
+int pyr_build(nvca_ctx *ctx, DetectJob &j, GeomPlan *pp, bool has_tilted);
+
+// ---- lbp_job.cpp
+int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total);              // the launch set of a job on a new-format LBP cascade
 
 // ---- detect_job.cpp
-// the pyramid levels of a CV_HAAR_SCALE_IMAGE call, smallest factor first, at most `cap` of them
-struct SiLevel { double factor; int szw, szh, winw, winh; };
-std::vector<SiLevel> si_levels(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t cap);
-// ... of detectMultiScale on a new-format cascade
-std::vector<SiLevel> lbp_levels(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t cap);
 int detect_job_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total);       // queue the job's next launch set
 int detect_job_advance(nvca_ctx *ctx, DetectJob &j);                          // after the stream has drained: consume what the set produced
 

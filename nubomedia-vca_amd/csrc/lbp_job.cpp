@@ -1,0 +1,108 @@
+// lbp_job.cpp -- the launch set of a detectMultiScale job on a new-format LBP cascade: its cached plan (pyramid: pyramid.cpp; tables:
+// lbp_tables.cpp) and the evaluator's launches (kernels_cascade_lbp.hip).
+#include "host_state.h"
+#include "lbp_tables.h"
+#include <cstdio>
+#include <cstring>
+#include <algorithm>
+
+using namespace nvca;
+
+namespace nvca {
+
+// cv::CascadeClassifier::detectMultiScale on a new-format LBP cascade (OpenCV 2.4 cascadedetect.cpp): the pyramid of
+// CV_HAAR_SCALE_IMAGE with its own level rules, scanned by the LBP evaluator (kernels_cascade_lbp.hip).  The plan holds the pyramid
+// (layout, resize tables), one scan grid per level and the cascade's tables at the pitch of the planes and of the stage-0 tile.
+static int lbp_plan(nvca_ctx *ctx, const DetectJob &j, GeomPlan **out)
+{
+    const LbpCascade &c = j.rq.casc->lbp;
+    const int cols = j.rq.cols, rows = j.rq.rows;
+    int rc;
+    char key[256];
+    snprintf(key, sizeof(key), "LBP|%llu|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)j.rq.casc->c.uid, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh);
+    GeomPlan *pp = find_plan(ctx, key);
+    if (!pp) {
+        std::unique_ptr<GeomPlan> np(new GeomPlan());
+        if ((rc = pyr_plan_init(ctx, *np, cols, rows, lbp_levels(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, 63)))) return rc;
+        if (!np->lv.empty()) {
+            // the scan grids: what hit_valid / hit_rect check and map a candidate key with
+            for (const PyrLevel &L : np->lv) np->det.specs.push_back(level_spec(np->P, L, c.ow, c.oh, 1));
+            LbpTables t; std::string err;
+            if ((rc = build_lbp_tables(c, np->lv, np->P, t, err))) { ctx->set_error(err); return rc; }
+            np->det.key_sy = t.key_sy; np->det.key_ss = t.key_ss;
+            LbpPlan &lp = np->lbp;
+            TableBlob blob;
+            const size_t o_levels = blob.add(t.levels.data(), t.levels.size() * sizeof(LbpLevelDev)), o_tiles = blob.add(t.tiles.data(), t.tiles.size() * sizeof(LbpTile)),
+                         o_stages = blob.add(t.stages.data(), t.stages.size() * sizeof(LbpStageDev)), o_gweak = blob.add(t.gweak.data(), t.gweak.size() * sizeof(LbpWeakDev)),
+                         o_tweak = blob.add(t.tweak.data(), t.tweak.size() * sizeof(LbpWeakDev));
+            if ((rc = blob.upload(ctx, lp.d_blob))) return rc;
+            LbpArgs &a = lp.args; memset(&a, 0, sizeof(a));
+            const unsigned char *base = lp.d_blob.as<unsigned char>();
+            a.levels = (const LbpLevelDev *)(base + o_levels); a.nlev = (int)t.levels.size();
+            a.tiles = (const LbpTile *)(base + o_tiles); a.ntiles = (int)t.tiles.size();
+            a.stages = (const LbpStageDev *)(base + o_stages); a.nstages = (int)t.stages.size();
+            a.gweak = (const LbpWeakDev *)(base + o_gweak); a.tweak = (const LbpWeakDev *)(base + o_tweak);
+            a.P = np->P; a.TP = t.TP; a.ow = c.ow; a.oh = c.oh; a.nrows = t.nrows;
+            a.key_sy = t.key_sy; a.key_ss = t.key_ss; a.tile_stages = t.tile_stages;
+            lp.bit_words = t.bit_words; lp.positions = t.positions; lp.lds = t.lds;
+        }
+        pp = store_plan(ctx, key, std::move(np));
+    }
+    *out = pp;
+    return NVCA_OK;
+}
+
+int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
+{
+    Workspace &ws = *ctx->ws;
+    ResultBufs &rb = ws.res[ws.cur_res];
+    GeomPlan *pp = nullptr;
+    int rc;
+    if ((rc = lbp_plan(ctx, j, &pp))) return rc;
+    j.q.phase = kJobFirstQueued; j.q.dp = nullptr;
+    if (pp->lv.empty()) return NVCA_OK;
+    // (the pyramid launchers write the squared integral with the sum: it is computed and ignored here)
+    if ((rc = pyr_build(ctx, j, pp, false))) return rc;
+    const LbpPlan &lp = pp->lbp;
+    const int tot = std::max(total, r0 + 1);
+    const size_t hits_stride = (size_t)ctx->hit_cap + 1;
+    constexpr size_t kCnt = 64;                       // list counters in front of the first list
+    if (ws.ln().failbits.ensure(2 * lp.bit_words * sizeof(unsigned) + 8) || ws.ln().deep.ensure((kCnt + lp.positions) * sizeof(unsigned)) ||
+        ws.ln().vnf.ensure(lp.positions * sizeof(unsigned) + 8) ||
+        rb.hits.ensure(hits_stride * tot * sizeof(unsigned long long)) || rb.h_hits.ensure(hits_stride * tot * sizeof(unsigned long long))) {
+        ctx->set_error("device allocation failed for the cascade workspace"); return NVCA_ERR_NOMEM;
+    }
+    CascadeJob &cj = j.q.cj;
+    cj = CascadeJob(); cj.r0 = r0; cj.n = 1; cj.total = total;
+    cj.cap = (unsigned)ctx->hit_cap;
+    cj.d_hits = rb.hits.as<unsigned long long>() + hits_stride * r0;
+    cj.h_hits = rb.h_hits.as<unsigned long long>() + hits_stride * r0;
+    NVCA_HIP_CHECK(ctx, hipMemsetAsync(cj.d_hits, 0, sizeof(unsigned long long), ctx->cs()));
+    NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.ln().deep.p, 0, kCnt * sizeof(unsigned), ctx->cs()));
+    LbpArgs a = lp.args;
+    a.sum = ws.ln().sum.as<int>();
+    a.bits = ws.ln().failbits.as<unsigned>(); a.bits2 = a.bits + lp.bit_words;
+    a.cnt = ws.ln().deep.as<unsigned>();
+    a.list[0] = ws.ln().deep.as<unsigned>() + kCnt; a.list[1] = ws.ln().vnf.as<unsigned>(); a.list_cap = (unsigned)lp.positions;
+    a.hits = cj.d_hits; a.hit_cap = cj.cap;
+    {   // the first stages everywhere, the serial walk's skip rule, then the later stages group by group on ever shorter survivor
+        // lists (groups of 2, 3, 4 ... stages: survivors thin out by about half per stage).  All booked as "window per lane".
+        TimedLaunch t(ctx, NVCA_K_STRIP);
+        launch_lbp_stage0(ctx->cs(), a, lp.lds);
+        launch_lbp_walk(ctx->cs(), a);
+        int g = 0;
+        for (int s0 = a.tile_stages, len = 2; s0 < a.nstages && g + 1 < (int)kCnt; s0 += len, len++, g++) {
+            // (the last group takes every stage that is left: the counters bound the number of groups)
+            const int s1 = g + 2 == (int)kCnt ? a.nstages : std::min(a.nstages, s0 + len);
+            launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)lp.positions);
+            if (s1 >= a.nstages) break;
+        }
+    }
+    NVCA_LAUNCH_CHECK(ctx);
+    cj.first = std::min<size_t>(cj.cap, 2048);
+    NVCA_HIP_CHECK(ctx, hipMemcpyAsync(cj.h_hits, cj.d_hits, (cj.first + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->cs()));
+    j.q.gp = pp; pp->inflight++; j.q.dp = &pp->det;
+    return NVCA_OK;
+}
+
+} // namespace nvca

@@ -302,10 +302,10 @@ int DetectPlan::build_tables(nvca_ctx *ctx, const Cascade &c, bool allow_tiles, 
     {   // the candidate key: scale | row | column of the window, each field as wide as THIS plan's grids need (the reference installs
         // multi-scale-factor with range 0 .. 51 and no clamp, FACE/kmsfacedetect.cpp:540-542: 1.01 on a 640 x 360 working image is a
         // ladder of 288 scales -- next to grids of at most 310 x 170 windows that is 9 + 8 + 9 bits)
-        auto bits = [](size_t n) { int b = 1; while ((1ull << b) < n) b++; return b; };
         size_t mx = 1, my = 1;
         for (const ScaleSpec &sp : specs) { mx = std::max(mx, sp.xs.size()); my = std::max(my, sp.ys.size()); }
-        const int bx = bits(mx), by = bits(my), bs = bits(std::max<size_t>(specs.size(), 1));
+        int bx, by, bs;
+        candidate_key_bits(mx, my, std::max<size_t>(specs.size(), 1), &bx, &by, &bs);
         if (bx + by + bs > 32 || specs.size() > 4095) { err = "scan too large for the candidate key (scales x rows x columns of windows beyond 2^32)"; return NVCA_ERR_ARG; }
         key_sy = bx; key_ss = bx + by;
     }

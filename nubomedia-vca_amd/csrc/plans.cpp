@@ -35,9 +35,24 @@ DetectPlan::~DetectPlan()
     d_scales.release(); d_stages.release(); d_strips.release(); d_pos.release(); d_order.release(); d_tasks.release(); d_tiles.release(); d_tile_order.release(); d_tcoords.release(); d_bands.release(); d_band_order.release(); d_deeprecs.release(); d_stage_hint.release(); d_stage_first.release(); d_stage_thr.release(); d_blob.release();
 }
 
+// one device allocation and one copy for all tables of a plan (a FIND_BIGGEST scan builds a plan per scale, per call)
+size_t TableBlob::add(const void *h, size_t n)
+{
+    const size_t off = bytes.size();
+    bytes.resize(off + ((n + 255) & ~(size_t)255));
+    if (n && h) memcpy(bytes.data() + off, h, n);
+    return off;
+}
+int TableBlob::upload(nvca_ctx *ctx, DevBuf &blob)
+{
+    if (blob.ensure(bytes.size())) { ctx->set_error("hipMalloc failed for plan tables"); return NVCA_ERR_NOMEM; }
+    NVCA_HIP_CHECK(ctx, hipMemcpy(blob.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+    return NVCA_OK;
+}
+
 int DetectPlan::upload(nvca_ctx *ctx)
 {
-    struct Item { DevBuf *d; const void *h; size_t n; } items[] = {
+    struct Item { DevBuf *d; const void *h; size_t n; size_t off; } items[] = {
         {&d_scales, scales.data(), scales.size() * sizeof(ScaleRec)},
         {&d_stages, stages.data(), stages.size() * sizeof(StageRec)},
         {&d_strips, strips.data(), strips.size() * sizeof(StripRec)},
@@ -54,21 +69,13 @@ int DetectPlan::upload(nvca_ctx *ctx)
         {&d_stage_first, stage_first.data(), stage_first.size() * sizeof(int)},
         {&d_stage_thr, stage_thr.data(), stage_thr.size() * sizeof(float)},
     };
-    // one device allocation and one copy for all tables (a FIND_BIGGEST scan builds a plan per scale, per call)
-    size_t total = 0;
-    for (auto &it : items) total += (it.n + 255) & ~(size_t)255;
-    if (total == 0) return NVCA_OK;
-    std::vector<unsigned char> blob(total);
-    size_t off = 0;
-    for (auto &it : items) { if (it.n && it.h) memcpy(blob.data() + off, it.h, it.n); off += (it.n + 255) & ~(size_t)255; }
+    TableBlob blob;
+    for (auto &it : items) it.off = blob.add(it.h, it.n);
+    if (blob.bytes.empty()) return NVCA_OK;
     for (auto &it : items) it.d->release();
-    if (d_blob.ensure(total)) { ctx->set_error("hipMalloc failed for plan tables"); return NVCA_ERR_NOMEM; }
-    NVCA_HIP_CHECK(ctx, hipMemcpy(d_blob.p, blob.data(), total, hipMemcpyHostToDevice));
-    off = 0;
-    for (auto &it : items) {
-        it.d->p = it.n ? (unsigned char *)d_blob.p + off : nullptr; it.d->bytes = 0;       // views
-        off += (it.n + 255) & ~(size_t)255;
-    }
+    int rc;
+    if ((rc = blob.upload(ctx, d_blob))) return rc;
+    for (auto &it : items) { it.d->p = it.n ? (unsigned char *)d_blob.p + it.off : nullptr; it.d->bytes = 0; }       // views
     return NVCA_OK;
 }
 

@@ -71,7 +71,7 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
             const int szw = sl.szw, szh = sl.szh, winw = sl.winw, winh = sl.winh;
             if (!t1 && !(t1 = roi_table(ctx, rb, c, 1.))) return NVCA_ERR_NOMEM;
             RoiStep st; roi_step_common(st, *t1);
-            st.szw = szw; st.szh = szh; st.step = factor > 2 ? 1 : 2; st.startX = 0; st.endX = szw - c.ow; st.startY = 0; st.endY = szh - c.oh;
+            st.szw = szw; st.szh = szh; st.step = level_step(factor); st.startX = 0; st.endX = szw - c.ow; st.startY = 0; st.endY = szh - c.oh;
             if (st.endX <= 0 || st.endY <= 0) continue;
             ResizeTab tab; build_resize_tab(cols, rows, szw, szh, tab);
             st.mode = tab.mode; st.xmax = tab.xmax;
@@ -243,6 +243,31 @@ int roi_collect(nvca_ctx *ctx, RoiBatch &rb)
         }
         rb.owners[slot]->sm.rkeys[rb.owner_img[slot]].push_back(key);
     }
+    return NVCA_OK;
+}
+// candidates of the round's k_roi launch, sorted into the serial order (step, row, column) -> rectangle
+int roi_job_candidates(nvca_ctx *ctx, DetectJob &j, std::vector<std::vector<nvca_rect>> &raw, std::vector<char> &grouped, std::vector<std::vector<int>> &sc)
+{
+    raw.assign(j.rq.nimg, {}); sc.assign(j.rq.nimg, {}); grouped.assign(j.rq.nimg, 0);
+    for (int k = 0; k < j.rq.nimg; k++) {
+        std::sort(j.sm.rkeys[k].begin(), j.sm.rkeys[k].end());
+        raw[k].reserve(j.sm.rkeys[k].size()); sc[k].reserve(j.sm.rkeys[k].size());
+        for (unsigned key : j.sm.rkeys[k]) {
+            const DetectJob::RoiStepInfo &ri = j.sm.rinfo[key >> 26];
+            const int iy = (key >> 13) & 8191, ix = key & 8191;
+            if (j.sm.dense && k == 0) {
+                // a dense launch reports every window that passes the cascade; the serial walk of the FULL grid (start column 0) visits only some
+                const int seen = j.fb.dense_candidate((size_t)ri.ladder, ix, iy);
+                if (seen < 0) { ctx->set_error("internal: dense candidate outside its reject bitmap (device result rejected)"); j.q.phase = kJobDone; return NVCA_ERR_INTERNAL; }
+                if (!seen) continue;
+            }
+            if (ri.out_factor != 0) raw[k].push_back(nvca_rect{cv_round(ix * ri.out_factor), cv_round(iy * ri.out_factor), ri.winw, ri.winh});
+            else raw[k].push_back(nvca_rect{cv_round(ix * ri.ystep), cv_round(iy * ri.ystep), ri.winw, ri.winh});
+            sc[k].push_back(ri.ladder);
+        }
+        j.sm.rkeys[k].clear();
+    }
+    j.sm.fused = false;
     return NVCA_OK;
 }
 

@@ -26,7 +26,7 @@ for p in ("nubomedia-vca_amd", "oracle", "tests"):
     sys.path.insert(0, os.path.join(ROOT, p))
 
 W, H, SF, MN = 1920, 1080, 1.1, 3
-TILE_STAGES = 3          # csrc/detect_job.cpp, lbp_plan: stages the LDS tile kernel evaluates
+TILE_STAGES = 3          # csrc/lbp_tables.cpp, build_lbp_tables (tile_stages): stages the LDS tile kernel evaluates
 STAGES = (3, 4, 4, 5, 5, 6, 6, 6, 7, 7, 7, 8, 8, 8, 8, 9, 9, 9, 10, 10)
 
 

@@ -1,5 +1,5 @@
-"""New-format LBP cascades on the device (csrc/kernels_cascade_lbp.hip, detect_job.cpp's lbp_plan / lbp_enqueue) against the numpy
-statement of SURVEY.md A.15 (tests/lbp_reference.py): bit for bit, raw lists and grouped boxes.  The cases and the hand-derived
+"""New-format LBP cascades on the device (csrc/kernels_cascade_lbp.hip, lbp_job.cpp's lbp_plan / lbp_enqueue on lbp_tables.cpp's
+tables) against the numpy statement of SURVEY.md A.15 (tests/lbp_reference.py): bit for bit, raw lists and grouped boxes.  The cases and the hand-derived
 lists are tests/lbp_cases.py's; tests/test_lbp_cpu.py asserts on the statement alone that they are not empty comparisons."""
 import ctypes as C
 import os
