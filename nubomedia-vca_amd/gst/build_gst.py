@@ -13,6 +13,8 @@ INC = ["-I%s/include/gstreamer-1.0" % CONDA, "-I%s/include/glib-2.0" % CONDA, "-
 LIBS = ["-L%s/lib" % CONDA, "-lgstvideo-1.0", "-lgstbase-1.0", "-lgstreamer-1.0", "-lgobject-2.0", "-lglib-2.0",
         # system libstdc++ must win over conda's older copy (libnubovca_hip needs GLIBCXX_3.4.29)
         "-Wl,--disable-new-dtags", "-Wl,-rpath,/usr/lib/x86_64-linux-gnu:%s/lib" % CONDA]
+SHIM_SOURCES = ["gstnubovca.cpp", "element_output.cpp"]      # one library: the elements, and what they emit as pure code
+SHIM_HEADERS = ["combiner.h", "element_output.h"]
 PLUGIN = os.path.join(HERE, "libgstnubovca.so")
 HARNESS = os.path.join(HERE, "gst_harness")
 # the reference's six plugins by their own library and plugin names (plugin_alias.cpp): (library, plugin name, element factory)
@@ -35,10 +37,10 @@ def build(required=True):
         if required:
             raise RuntimeError("GStreamer development files not found under %s" % CONDA)
         return None
-    src = os.path.join(HERE, "gstnubovca.cpp")
-    hdr = os.path.join(ROOT, "include", "nubovca.h")
-    if _stale(PLUGIN, [src, hdr, __file__]):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-deprecated-declarations", src, "-o", PLUGIN]
+    srcs = [os.path.join(HERE, f) for f in SHIM_SOURCES]
+    hdrs = [os.path.join(HERE, f) for f in SHIM_HEADERS] + [os.path.join(ROOT, "include", "nubovca.h")]
+    if _stale(PLUGIN, srcs + hdrs + [__file__]):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-deprecated-declarations"] + srcs + ["-o", PLUGIN]
                               + INC + LIBS + ["-L" + PKG, "-lnubovca_hip", "-Wl,-rpath,$ORIGIN/.."])
     alias_src = os.path.join(HERE, "plugin_alias.cpp")
     os.makedirs(ALIAS_DIR, exist_ok=True)

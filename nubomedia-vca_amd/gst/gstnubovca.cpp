@@ -11,8 +11,9 @@
 //                     EYE/kmseyedetect.cpp:1274-1320 (props), :220-308 (event: eye_left*, eye_right*), :192-218,680-764 (faces in)
 //                     NOSE/kmsnosedetect.cpp:1089-1135, :212-273 (event "noses")   MOUTH/kmsmouthdetect.cpp:205-282 (faces + mouths)
 //                     EAR/kmseardetect.cpp:994-1038 ("meta-data"), :196-290 (signal only: the event is built but never pushed)
-// All pixel work happens in the library (HIP); this file is glue only.  One plugin
-// ("nubovca") registers every factory; the reference ships one plugin per element.
+// All pixel work happens in the library (HIP); the shim is glue only: this file holds the per-GPU frontend, the one batching
+// round and the GObject surface, combiner.h the leader election, element_output.cpp what an element emits for a frame.  One
+// plugin ("nubovca") registers every factory; the reference ships one plugin per element.
 #include <gst/gst.h>
 #include <gst/video/video.h>
 #include <gst/video/gstvideofilter.h>
@@ -23,12 +24,14 @@
 #include <string>
 #include <mutex>
 #include <atomic>
-#include <condition_variable>
 #include <map>
+#include <memory>
 #include <vector>
 #include <algorithm>
-#include <math.h>
 #include "nubovca.h"
+#include "combiner.h"
+#include "element_output.h"
+using namespace nvca_gst;
 
 GST_DEBUG_CATEGORY_STATIC(nubovca_debug);
 // No C++ exception crosses into GLib / GStreamer's C frames: every GObject / GstBaseTransform callback of the elements is a
@@ -70,46 +73,16 @@ static std::mutex g_ctx_mutex;
 static std::vector<GpuSlot *> g_slots;          // filled once, entries live for the process
 static bool g_slots_ready = false;
 static int g_instances = 0;                     // elements that have taken a slot so far
-// Frames of different elements of one kind that arrive while the GPU is busy are combined into one batched call.  The
-// first streaming thread to arrive leads: it takes whatever has queued up (its own frame included), runs the batched
-// entry point on the lot and wakes the owners; threads that arrive meanwhile queue up for the next round, so the batch
-// grows with the load and an idle pipeline still sees single-frame latency.  Results are those of per-frame calls:
-// streams are independent and a batch keeps the order of each stream's frames.
-template <class Req> struct Combiner {
-    std::mutex m;
-    std::condition_variable cv;
-    std::vector<Req *> q;
-    bool leader = false;
-    int max_batch = 0;                                      /* largest batch seen (NVCA_GST_STATS) */
-    template <class Run> int process(Req *req, Run run)
-    {
-        static const bool off = getenv("NVCA_GST_NO_COMBINE") != NULL;     /* A/B switch: every frame on its own */
-        if (off) { std::vector<Req *> one(1, req); run(one); return req->rc; }
-        std::unique_lock<std::mutex> lk(m);
-        req->done = false;
-        q.push_back(req);
-        while (!req->done) {
-            if (leader) { cv.wait(lk); continue; }
-            leader = true;
-            std::vector<Req *> round;
-            round.swap(q);
-            lk.unlock();
-            run(round);
-            lk.lock();
-            if ((int)round.size() > max_batch) max_batch = (int)round.size();
-            for (Req *r : round) r->done = true;
-            leader = false;
-            cv.notify_all();
-        }
-        return req->rc;
-    }
+// One frame on its way through a Combiner: the owner's handle, frame and result buffers (Lists lists of Cap rectangles) go in,
+// status and counts come back.  kFaceCap, kTrkCap and kPartCap are the capacities of every buffer and call of their family.
+static const int kFaceCap = 256, kTrkCap = 4096, kPartCap = 64;
+template <class Handle, int Lists, int Cap> struct Req {
+    static constexpr int lists = Lists, cap = Cap;
+    Handle *h; nvca_frame frame; nvca_rect *out[Lists]; int n[Lists]; int rc; bool done;
 };
-
-static const int kFaceCap = 256, kTrkCap = 4096;
-struct FaceReq { nvca_face_stream *stream; nvca_frame frame; nvca_rect *out; int n, rc; bool done; };
-struct TrkReq { nvca_tracker *trk; nvca_frame frame; double ts; nvca_rect *out; int n, rc; bool done; };
-static const int kPartCap = 64;
-struct PartReq { nvca_part_stream *stream; nvca_frame frame; nvca_rect *a, *b; int na, nb, rc; bool done; };
+typedef Req<nvca_face_stream, 1, kFaceCap> FaceReq;
+typedef Req<nvca_part_stream, 2, kPartCap> PartReq;         // out[0] / out[1]: the library's lists a / b
+struct TrkReq : Req<nvca_tracker, 1, kTrkCap> { double ts; };
 struct GpuSlot {
     int index = 0, device = 0;
     nvca_ctx *ctx = nullptr;
@@ -199,81 +172,71 @@ static void release_cascade(GpuSlot *g, nvca_cascade *h)
         }
 }
 
-static void face_run_round(nvca_ctx *ctx, std::vector<FaceReq *> &round)
+// One round of a Combiner, for every family.  More than one request: the batched entry point is tried; when the family accepts
+// its status, every owner gets that status, its counts and its rectangles.  Otherwise -- a single frame, or a batch not accepted --
+// each request gets its own call and its own status, so one bad frame does not fail its neighbours.
+// A family states its batched call, its single call and which batch statuses it accepts.
+template <class Family, class R> static void run_round(nvca_ctx *ctx, std::vector<R *> &round)
 {
     const int n = (int)round.size();
     bool batched = false;
     if (n > 1) {
-        std::vector<nvca_face_stream *> streams(n);
+        std::vector<decltype(R::h)> handles(n);
         std::vector<nvca_frame> frames(n);
-        std::vector<nvca_rect> out((size_t)n * kFaceCap);
-        std::vector<int> n_out(n, 0);
-        for (int i = 0; i < n; i++) { streams[i] = round[i]->stream; frames[i] = round[i]->frame; }
-        const int rc = nvca_face_batch_process(ctx, n, streams.data(), frames.data(), out.data(), NULL, kFaceCap, n_out.data());
-        batched = rc != NVCA_ERR_ARG;
+        std::vector<nvca_rect> out[R::lists];
+        std::vector<int> n_out[R::lists];
+        for (int l = 0; l < R::lists; l++) { out[l].resize((size_t)n * R::cap); n_out[l].assign(n, 0); }
+        for (int i = 0; i < n; i++) { handles[i] = round[i]->h; frames[i] = round[i]->frame; }
+        const int rc = Family::batch(ctx, round, handles.data(), frames.data(), out, n_out);
+        batched = Family::accepts(rc);
         for (int i = 0; batched && i < n; i++) {
-            FaceReq *r = round[i];
-            r->rc = rc; r->n = rc == NVCA_OK ? n_out[i] : 0;
-            memcpy(r->out, out.data() + (size_t)i * kFaceCap, sizeof(nvca_rect) * (size_t)std::min(n_out[i], kFaceCap));
-        }
-    }
-    // a single frame, or a batch refused with NVCA_ERR_ARG (every frame is validated before any stream is touched): one
-    // bad frame must not fail its neighbours, so each gets its own call and its own status.  Any other failure came
-    // after the streams' frame gates advanced and is reported to every owner as it is.
-    if (!batched)
-        for (FaceReq *r : round) r->rc = nvca_face_stream_process(r->stream, &r->frame, r->out, NULL, kFaceCap, &r->n);
-}
-static void part_run_round(nvca_ctx *ctx, std::vector<PartReq *> &round)
-{
-    const int n = (int)round.size();
-    bool batched = false;
-    if (n > 1) {
-        std::vector<nvca_part_stream *> streams(n);
-        std::vector<nvca_frame> frames(n);
-        std::vector<nvca_rect> a((size_t)n * kPartCap), b((size_t)n * kPartCap);
-        std::vector<int> na(n, 0), nb(n, 0);
-        for (int i = 0; i < n; i++) { streams[i] = round[i]->stream; frames[i] = round[i]->frame; }
-        const int rc = nvca_part_batch_process(ctx, n, streams.data(), frames.data(), a.data(), kPartCap, na.data(), b.data(), kPartCap, nb.data());
-        batched = rc == NVCA_OK;                            // any failure leaves every stream of the call as it was (part_logic.cpp: PartSnap; part_call.h: PartCall):
-                                                            // each frame then runs on its own, so one bad frame does not fail its neighbours
-        for (int i = 0; batched && i < n; i++) {
-            PartReq *r = round[i];
-            r->rc = rc; r->na = rc == NVCA_OK ? na[i] : 0; r->nb = rc == NVCA_OK ? nb[i] : 0;
-            memcpy(r->a, a.data() + (size_t)i * kPartCap, sizeof(nvca_rect) * (size_t)std::min(r->na, kPartCap));
-            memcpy(r->b, b.data() + (size_t)i * kPartCap, sizeof(nvca_rect) * (size_t)std::min(r->nb, kPartCap));
+            R *r = round[i];
+            r->rc = rc;
+            for (int l = 0; l < R::lists; l++) {
+                r->n[l] = rc == NVCA_OK ? n_out[l][i] : 0;
+                memcpy(r->out[l], out[l].data() + (size_t)i * R::cap, sizeof(nvca_rect) * (size_t)std::min(r->n[l], (int)R::cap));
+            }
         }
     }
     if (!batched)
-        for (PartReq *r : round) r->rc = nvca_part_stream_process(r->stream, &r->frame, r->a, kPartCap, &r->na, r->b, kPartCap, &r->nb);
+        for (R *r : round) r->rc = Family::single(r);
 }
+struct FaceCalls {
+    static int batch(nvca_ctx *ctx, std::vector<FaceReq *> &round, nvca_face_stream **h, nvca_frame *f, std::vector<nvca_rect> *out, std::vector<int> *n_out)
+    { return nvca_face_batch_process(ctx, (int)round.size(), h, f, out[0].data(), NULL, kFaceCap, n_out[0].data()); }
+    static int single(FaceReq *r) { return nvca_face_stream_process(r->h, &r->frame, r->out[0], NULL, kFaceCap, &r->n[0]); }
+    // a batch is refused with NVCA_ERR_ARG before any stream is touched (every frame is validated first): then each frame
+    // runs alone.  Any other failure came after the streams' frame gates advanced and is reported to every owner as it is.
+    static bool accepts(int rc) { return rc != NVCA_ERR_ARG; }
+};
+struct TrkCalls {
+    static int batch(nvca_ctx *ctx, std::vector<TrkReq *> &round, nvca_tracker **h, nvca_frame *f, std::vector<nvca_rect> *out, std::vector<int> *n_out)
+    {
+        std::vector<double> ts(round.size());
+        for (size_t i = 0; i < round.size(); i++) ts[i] = round[i]->ts;
+        return nvca_tracker_batch_process(ctx, (int)round.size(), h, f, ts.data(), out[0].data(), kTrkCap, n_out[0].data());
+    }
+    static int single(TrkReq *r) { return nvca_tracker_process(r->h, &r->frame, r->ts, r->out[0], kTrkCap, &r->n[0]); }
+    static bool accepts(int rc) { return FaceCalls::accepts(rc); }
+};
+struct PartCalls {
+    static int batch(nvca_ctx *ctx, std::vector<PartReq *> &round, nvca_part_stream **h, nvca_frame *f, std::vector<nvca_rect> *out, std::vector<int> *n_out)
+    { return nvca_part_batch_process(ctx, (int)round.size(), h, f, out[0].data(), kPartCap, n_out[0].data(), out[1].data(), kPartCap, n_out[1].data()); }
+    static int single(PartReq *r) { return nvca_part_stream_process(r->h, &r->frame, r->out[0], kPartCap, &r->n[0], r->out[1], kPartCap, &r->n[1]); }
+    // any failure leaves every stream of the call as it was (part_logic.cpp: PartSnap; part_call.h: PartCall): each frame then
+    // runs on its own, so one bad frame does not fail its neighbours
+    static bool accepts(int rc) { return rc == NVCA_OK; }
+};
 
-static void trk_run_round(nvca_ctx *ctx, std::vector<TrkReq *> &round)
+// the slot's shared handle of a file of the cascade directory; a failure is logged, not fatal (FACE/kmsfacedetect.cpp:167-176)
+static bool need_cascade(GpuSlot *g, const char *file, nvca_cascade **c)
 {
-    const int n = (int)round.size();
-    bool batched = false;
-    if (n > 1) {
-        std::vector<nvca_tracker *> trks(n);
-        std::vector<nvca_frame> frames(n);
-        std::vector<double> ts(n);
-        std::vector<nvca_rect> out((size_t)n * kTrkCap);
-        std::vector<int> n_out(n, 0);
-        for (int i = 0; i < n; i++) { trks[i] = round[i]->trk; frames[i] = round[i]->frame; ts[i] = round[i]->ts; }
-        const int rc = nvca_tracker_batch_process(ctx, n, trks.data(), frames.data(), ts.data(), out.data(), kTrkCap, n_out.data());
-        batched = rc != NVCA_ERR_ARG;
-        for (int i = 0; batched && i < n; i++) {
-            TrkReq *r = round[i];
-            r->rc = rc; r->n = rc == NVCA_OK ? n_out[i] : 0;
-            memcpy(r->out, out.data() + (size_t)i * kTrkCap, sizeof(nvca_rect) * (size_t)std::min(n_out[i], kTrkCap));
-        }
-    }
-    if (!batched)
-        for (TrkReq *r : round) r->rc = nvca_tracker_process(r->trk, &r->frame, r->ts, r->out, kTrkCap, &r->n);
-}
-
-static std::string cascade_path(const char *file)
-{
+    if (!file || *c) return true;
     const char *dir = getenv("NVCA_CASCADE_DIR");
-    return std::string(dir ? dir : OPENCV_CASCADE_DIR) + "/" + file;
+    const std::string path = std::string(dir ? dir : OPENCV_CASCADE_DIR) + "/" + file;
+    *c = acquire_cascade(g, path);
+    if (!*c) GST_ERROR("Error charging cascade %s: %s", path.c_str(), nvca_last_error(g->ctx));
+    return *c != nullptr;
 }
 static double now_ms()
 {
@@ -281,36 +244,80 @@ static double now_ms()
     return t.tv_sec * 1000.0 + t.tv_usec / 1000.0;
 }
 
-// ---------------------------------------------------------------- view-* drawing (host side, on the mapped frame)
-// The reference draws on the frame in place when a view property is on: cvRectangle(..., thickness 3, line type 8)
-// around every box and cv::circle(..., thickness 4) around the eyes (FACE/BaseFace.cpp:70-82, NOSE :898-905,
-// MOUTH :896-903, EAR :750-758, EYE :1069-1099, TRK :389).  Frames are host memory here, so this stays on the host
-// ("stays on host"); it is written from the documented geometry of OpenCV's thick primitives -- a 3-pixel
-// band centred on each edge with radius-1 round joins, a 4-pixel ring -- and is NOT pixel-verified against OpenCV,
-// which is not available offline.  Boxes, events and signals do not depend on it.
-// view-* outlines: the library draws them (nvca_draw_shapes, host frames here), so a pipeline that keeps its frames in HBM
-// gets the same pixels from the device kernel
-struct Canvas { nvca_ctx *ctx; nvca_frame f; int bpp; };
-static void draw_shape(const Canvas &c, int kind, int x, int y, int w, int h, const guint8 *col)
+// ---------------------------------------------------------------- what the three element families share
+static nvca_frame frame_of(GstVideoFrame *frame)
 {
-    // host frames need no context (nvca_draw_shapes): outlines are drawn even where no GPU slot came up
-    nvca_shape sh; sh.kind = kind; sh.x = x; sh.y = y; sh.w = w; sh.h = h;
-    for (int k = 0; k < 4; k++) sh.bgra[k] = col[k];
-    nvca_draw_shapes(c.f.mem == NVCA_MEM_HOST ? NULL : c.ctx, &c.f, c.bpp, &sh, 1);
+    nvca_frame nf;
+    nf.data = GST_VIDEO_FRAME_PLANE_DATA(frame, 0);
+    nf.width = GST_VIDEO_FRAME_WIDTH(frame); nf.height = GST_VIDEO_FRAME_HEIGHT(frame);
+    nf.stride = GST_VIDEO_FRAME_PLANE_STRIDE(frame, 0);
+    nf.mem = NVCA_MEM_HOST; nf.pts = GST_BUFFER_PTS(frame->buffer);
+    return nf;
 }
-// corners (x0, y0) and (x1, y1) inclusive, as cvRectangle takes them
-static void draw_rect3(const Canvas &c, int x0, int y0, int x1, int y1, const guint8 *col) { draw_shape(c, NVCA_SHAPE_RECT3, x0, y0, x1 - x0, y1 - y0, col); }
-static void draw_ring4(const Canvas &c, int cx, int cy, int radius, const guint8 *col) { draw_shape(c, NVCA_SHAPE_RING4, cx, cy, radius, 0, col); }
-#define BGR_OF_RGB(r, g, b) {b, g, r, 0}
-static Canvas canvas_of(nvca_ctx *ctx, GstVideoFrame *frame)
+// view-* outlines (element_output.cpp lists them): the library draws them on the mapped frame, in place, with the rasterisation
+// rules nubovca.h states for nvca_draw_shapes (checked by tests/test_draw_cpu.py and tests/test_gpu_draw.py).  Host frames need
+// no context, so outlines are drawn even where no GPU slot came up.
+static void draw_outlines(GstVideoFrame *frame, const std::vector<nvca_shape> &shapes)
 {
-    Canvas c;
-    c.ctx = ctx;
-    c.f.data = GST_VIDEO_FRAME_PLANE_DATA(frame, 0);
-    c.f.width = GST_VIDEO_FRAME_WIDTH(frame); c.f.height = GST_VIDEO_FRAME_HEIGHT(frame);
-    c.f.stride = GST_VIDEO_FRAME_PLANE_STRIDE(frame, 0); c.f.mem = NVCA_MEM_HOST; c.f.pts = 0;
-    c.bpp = GST_VIDEO_FRAME_COMP_PSTRIDE(frame, 0);
-    return c;
+    if (shapes.empty()) return;
+    const nvca_frame nf = frame_of(frame);
+    nvca_draw_shapes(NULL, &nf, GST_VIDEO_FRAME_COMP_PSTRIDE(frame, 0), shapes.data(), (int)shapes.size());
+}
+// activate-events / events-ms: the string signal goes out at most once per events-ms (signal_due)
+struct EventsThrottle { int server_events, events_ms; double last_ms; };
+static void throttle_init(EventsThrottle &t) { t.server_events = 0; t.events_ms = 30001; t.last_ms = 0; }
+static void emit_if_due(gpointer element, guint signal, EventsThrottle &t, int n, const std::string &payload)
+{
+    const double now = now_ms();
+    if (!signal_due(n, t.server_events, now, t.last_ms, t.events_ms)) return;
+    t.last_ms = now;
+    g_signal_emit(element, signal, 0, payload.c_str());
+}
+static void push_event(gpointer element, ElementOutput &out)
+{
+    if (out.event) gst_pad_push_event(GST_BASE_TRANSFORM(element)->srcpad, gst_event_new_custom(GST_EVENT_CUSTOM_DOWNSTREAM, out.event.release()));
+}
+static void install_pads(gpointer klass, const char *caps_string)
+{
+    GstCaps *caps = gst_caps_from_string(caps_string);
+    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("src", GST_PAD_SRC, GST_PAD_ALWAYS, caps));
+    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("sink", GST_PAD_SINK, GST_PAD_ALWAYS, caps));
+    gst_caps_unref(caps);
+}
+// NVCA_GST_STATS, at finalize: the largest round of the element's combiner
+template <class Q> static void print_batch_stats(Q &q, const char *what, int slot)
+{
+    std::lock_guard<std::mutex> lk(q.m);
+    fprintf(stderr, "nubovca: largest combined %s batch %d (slot %d)\n", what, q.max_batch, slot);
+}
+// Properties, for every family: each is an int -- prop_int(element, id, set) names the field a write or a read goes to -- but
+// set_max_area (long) and image-to-overlay (boxed), which prop_other(element, id, value to set or NULL, value to fill) handles.
+template <class E> static void set_property(GObject *o, guint id, const GValue *v, GParamSpec *ps)
+try {
+    E *e = (E *)o;
+    NvcaRecLock nvca_lock_(&e->mutex);
+    int *field = prop_int(e, id, true);
+    if (field) *field = g_value_get_int(v);
+    else if (!prop_other(e, id, v, NULL)) G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps);
+    if (field == &e->events.server_events) e->events.last_ms = now_ms();
+    sync_params(e);
+}
+NVCA_GST_CATCH_VOID(E::set_where)
+template <class E> static void get_property(GObject *o, guint id, GValue *v, GParamSpec *ps)
+try {
+    E *e = (E *)o;
+    NvcaRecLock nvca_lock_(&e->mutex);
+    if (const int *field = prop_int(e, id, false)) g_value_set_int(v, *field);
+    else if (!prop_other(e, id, NULL, v)) G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps);
+}
+NVCA_GST_CATCH_VOID(E::get_where)
+// image-to-overlay: accepted and kept; overlay drawing is out of scope
+static bool overlay_prop(GstStructure **held, const GValue *set, GValue *get)
+{
+    if (!set) { g_value_set_boxed(get, *held); return true; }
+    if (*held) gst_structure_free(*held);
+    *held = (GstStructure *)g_value_dup_boxed(set);
+    return true;
 }
 
 // =====================================================================================
@@ -322,10 +329,11 @@ struct NvcaFace {
     GpuSlot *slot;                  /* the GPU this stream lives on (taken at the first frame) */
     nvca_cascade *cascade; nvca_face_stream *stream;
     nvca_face_params p;
-    int view_faces, send_meta_data, server_events, events_ms;
-    double time_events_ms;
+    int view_faces, send_meta_data;
+    EventsThrottle events;
     GQueue *events_queue;
     GstStructure *image_to_overlay;
+    static constexpr const char *set_where = "nvca_face_set_property", *get_where = "nvca_face_get_property";
 };
 struct NvcaFaceClass { GstVideoFilterClass parent; };
 G_DEFINE_TYPE(NvcaFace, nvca_face, GST_TYPE_VIDEO_FILTER)
@@ -334,65 +342,26 @@ enum { FP_0, FP_VIEW, FP_DETECT_EVENT, FP_META, FP_WIDTH, FP_X_EVERY_4, FP_EUCLI
        FP_EVENTS_MS, FP_OVERLAY };
 static guint face_signal = 0;
 
-static void face_sync_params(NvcaFace *f) { if (f->stream) nvca_face_stream_set_params(f->stream, &f->p); }
-
-static void nvca_face_set_property(GObject *o, guint id, const GValue *v, GParamSpec *ps)
-try {
-    NvcaFace *f = (NvcaFace *)o;
-    NvcaRecLock nvca_lock_(&f->mutex);
-    switch (id) {
-    case FP_VIEW: f->view_faces = g_value_get_int(v); break;
-    case FP_DETECT_EVENT: f->p.detect_event = g_value_get_int(v); break;
-    case FP_META: f->send_meta_data = g_value_get_int(v); break;
-    case FP_X_EVERY_4: f->p.process_x_every_4 = g_value_get_int(v); break;
-    case FP_WIDTH: f->p.width_to_process = g_value_get_int(v); break;
-    case FP_SCALE: f->p.scale_factor_pct = g_value_get_int(v); break;
-    case FP_EUCLID: f->p.euclidean_threshold = g_value_get_int(v); break;
-    case FP_TRACK: f->p.euclidean_threshold = g_value_get_int(v); break;   /* sic: FACE/kmsfacedetect.cpp:548-550 */
-    case FP_AREA: f->p.area_threshold = g_value_get_int(v); break;
-    case FP_EVENTS: f->server_events = g_value_get_int(v); f->time_events_ms = now_ms(); break;
-    case FP_EVENTS_MS: f->events_ms = g_value_get_int(v); break;
-    case FP_OVERLAY:
-        if (f->image_to_overlay) gst_structure_free(f->image_to_overlay);
-        f->image_to_overlay = (GstStructure *)g_value_dup_boxed(v);      /* accepted; overlay drawing is out of scope */
-        break;
-    default: G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps); break;
-    }
-    face_sync_params(f);
-}
-NVCA_GST_CATCH_VOID("nvca_face_set_property")
-static void nvca_face_get_property(GObject *o, guint id, GValue *v, GParamSpec *ps)
-try {
-    NvcaFace *f = (NvcaFace *)o;
-    NvcaRecLock nvca_lock_(&f->mutex);
-    switch (id) {
-    case FP_VIEW: g_value_set_int(v, f->view_faces); break;
-    case FP_DETECT_EVENT: g_value_set_int(v, f->p.detect_event); break;
-    case FP_META: g_value_set_int(v, f->send_meta_data); break;
-    case FP_X_EVERY_4: g_value_set_int(v, f->p.process_x_every_4); break;
-    case FP_WIDTH: g_value_set_int(v, f->p.width_to_process); break;
-    case FP_SCALE: g_value_set_int(v, f->p.scale_factor_pct); break;
-    case FP_EUCLID: g_value_set_int(v, f->p.euclidean_threshold); break;
-    case FP_TRACK: g_value_set_int(v, f->p.track_threshold); break;
-    case FP_AREA: g_value_set_int(v, f->p.area_threshold); break;
-    case FP_EVENTS: g_value_set_int(v, f->server_events); break;
-    case FP_EVENTS_MS: g_value_set_int(v, f->events_ms); break;
-    case FP_OVERLAY: g_value_set_boxed(v, f->image_to_overlay); break;
-    default: G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps); break;
-    }
-}
-NVCA_GST_CATCH_VOID("nvca_face_get_property")
-
-// a queued upstream "message": does it carry a "motion" structure?  (FACE/kmsfacedetect.cpp:680-712)
-static bool message_has_motion(const GstStructure *m)
+// the int behind a property, for a write (set) or a read
+static int *prop_int(NvcaFace *f, guint id, bool set)
 {
-    const gint len = gst_structure_n_fields(m);
-    for (gint i = 0; i < len; i++) {
-        const gchar *name = gst_structure_nth_field_name(m, i);
-        if (g_strcmp0(name, "motion") == 0 && gst_structure_has_field_typed(m, name, GST_TYPE_STRUCTURE)) return true;
+    switch (id) {
+    case FP_VIEW: return &f->view_faces;
+    case FP_DETECT_EVENT: return &f->p.detect_event;
+    case FP_META: return &f->send_meta_data;
+    case FP_X_EVERY_4: return &f->p.process_x_every_4;
+    case FP_WIDTH: return &f->p.width_to_process;
+    case FP_SCALE: return &f->p.scale_factor_pct;
+    case FP_EUCLID: return &f->p.euclidean_threshold;
+    case FP_TRACK: return set ? &f->p.euclidean_threshold : &f->p.track_threshold;   /* sic: FACE/kmsfacedetect.cpp:548-550 */
+    case FP_AREA: return &f->p.area_threshold;
+    case FP_EVENTS: return &f->events.server_events;
+    case FP_EVENTS_MS: return &f->events.events_ms;
     }
-    return false;
+    return NULL;
 }
+static bool prop_other(NvcaFace *f, guint id, const GValue *set, GValue *get) { return id == FP_OVERLAY && overlay_prop(&f->image_to_overlay, set, get); }
+static void sync_params(NvcaFace *f) { if (f->stream) nvca_face_stream_set_params(f->stream, &f->p); }
 
 static gboolean nvca_face_sink_event(GstBaseTransform *trans, GstEvent *event)
 try {
@@ -411,14 +380,7 @@ static void face_lazy_init(NvcaFace *f)
     if (!f->slot) f->slot = take_slot();
     nvca_ctx *ctx = f->slot->ctx;
     if (!ctx) return;
-    if (!f->cascade) {
-        const std::string path = cascade_path("haarcascade_frontalface_alt.xml");
-        f->cascade = acquire_cascade(f->slot, path);
-        if (!f->cascade) {
-            GST_ERROR("Error charging cascade %s: %s", path.c_str(), nvca_last_error(ctx));   /* :167-176: logged, not fatal */
-            return;
-        }
-    }
+    if (!need_cascade(f->slot, "haarcascade_frontalface_alt.xml", &f->cascade)) return;
     if (nvca_face_stream_create(ctx, f->cascade, &f->p, &f->stream) != NVCA_OK) f->stream = nullptr;
 }
 
@@ -436,52 +398,17 @@ try {
         }
         GST_OBJECT_UNLOCK(f);
         note_frame_memory(f->slot, frame);
-        nvca_frame nf;
-        nf.data = GST_VIDEO_FRAME_PLANE_DATA(frame, 0);
-        nf.width = GST_VIDEO_FRAME_WIDTH(frame); nf.height = GST_VIDEO_FRAME_HEIGHT(frame);
-        nf.stride = GST_VIDEO_FRAME_PLANE_STRIDE(frame, 0);
-        nf.mem = NVCA_MEM_HOST; nf.pts = GST_BUFFER_PTS(frame->buffer);
-        nvca_rect boxes[256]; int n = 0;
-        FaceReq req{f->stream, nf, boxes, 0, NVCA_OK, false};
+        nvca_rect boxes[kFaceCap];
+        FaceReq req{f->stream, frame_of(frame), {boxes}, {0}, NVCA_OK, false};
         nvca_ctx *ctx = f->slot->ctx;
-        const int rc = f->slot->face_q.process(&req, [ctx](std::vector<FaceReq *> &round) { face_run_round(ctx, round); });
-        n = req.n;
+        const int rc = f->slot->face_q.process(&req, [ctx](std::vector<FaceReq *> &round) { run_round<FaceCalls>(ctx, round); });
         if (rc != NVCA_OK) GST_ERROR("nvca_face_stream_process: %d", rc);
         else {
-            if (n > 256) n = 256;
-            // kms_face_send_event :179-249
-            GstStructure *message = gst_structure_new_empty("message");
-            GstStructure *ts = gst_structure_new("time", "pts", G_TYPE_UINT64, GST_BUFFER_PTS(frame->buffer), NULL);
-            gst_structure_set(message, "timestamp", GST_TYPE_STRUCTURE, ts, NULL);
-            gst_structure_free(ts);
-            std::string faces_str;
-            for (int i = 0; i < n; i++) {
-                GstStructure *face = gst_structure_new("face", "type", G_TYPE_STRING, "face", "x", G_TYPE_UINT, (guint)boxes[i].x,
-                                                       "y", G_TYPE_UINT, (guint)boxes[i].y, "width", G_TYPE_UINT, (guint)boxes[i].w,
-                                                       "height", G_TYPE_UINT, (guint)boxes[i].h, NULL);
-                char id[16]; snprintf(id, sizeof(id), "%d", i);
-                gst_structure_set(message, id, GST_TYPE_STRUCTURE, face, NULL);
-                gst_structure_free(face);
-                faces_str += "x:" + std::to_string((guint)boxes[i].x) + ",y:" + std::to_string((guint)boxes[i].y) +
-                             ",width:" + std::to_string((guint)boxes[i].w) + ",height:" + std::to_string((guint)boxes[i].h) + ";";
-            }
-            gst_pad_push_event(GST_BASE_TRANSFORM(f)->srcpad, gst_event_new_custom(GST_EVENT_CUSTOM_DOWNSTREAM, message));
-            if (f->view_faces > 0 && !f->image_to_overlay) {
-                // Faces::draw: (x, y) .. (x + w - 1, y + h - 1) of the working-image box, times the integer scale, in
-                // colors[1] = CV_RGB(0,128,255)  (FACE/BaseFace.cpp:70-82, FACE/kmsfacedetect.cpp:144-151,832-850)
-                static const guint8 col[4] = BGR_OF_RGB(0, 128, 255);
-                const Canvas cv = canvas_of(f->slot->ctx, frame);
-                const int scale = nf.width / f->p.width_to_process;
-                for (int i = 0; i < n; i++)
-                    draw_rect3(cv, boxes[i].x, boxes[i].y, boxes[i].x + boxes[i].w - scale, boxes[i].y + boxes[i].h - scale, col);
-            }
-            if (n > 0) {
-                const double t = now_ms();
-                if (1 == f->server_events && t - f->time_events_ms > f->events_ms) {
-                    f->time_events_ms = t;
-                    g_signal_emit(G_OBJECT(f), face_signal, 0, faces_str.c_str());
-                }
-            }
+            const int n = std::min(req.n[0], kFaceCap);
+            ElementOutput out = face_output(boxes, n, req.frame.width, req.frame.pts, f->p.width_to_process, f->view_faces, f->image_to_overlay != NULL);
+            push_event(f, out);
+            draw_outlines(frame, out.shapes);
+            emit_if_due(f, face_signal, f->events, n, out.payload);
         }
     }
     return GST_FLOW_OK;                                     /* always: FACE/kmsfacedetect.cpp:897 */
@@ -492,8 +419,7 @@ static void nvca_face_finalize(GObject *o)
 try {
     NvcaFace *f = (NvcaFace *)o;
     if (getenv("NVCA_GST_STATS") && f->slot) {
-        std::lock_guard<std::mutex> lk(f->slot->face_q.m);
-        fprintf(stderr, "nubovca: largest combined face batch %d (slot %d)\n", f->slot->face_q.max_batch, f->slot->index);
+        print_batch_stats(f->slot->face_q, "face", f->slot->index);
         fprintf(stderr, "nubovca: page-locked pool memories %d (slot %d)\n", f->slot->registered.load(), f->slot->index);
     }
     if (f->stream) nvca_face_stream_destroy(f->stream);
@@ -508,7 +434,8 @@ NVCA_GST_CATCH_VOID("nvca_face_finalize")
 static void nvca_face_init(NvcaFace *f)
 try {
     nvca_face_params_default(&f->p);                        /* defaults of FACE/kmsfacedetect.cpp:979-999 */
-    f->view_faces = 0; f->send_meta_data = 0; f->server_events = 0; f->events_ms = 30001; f->time_events_ms = 0;
+    f->view_faces = 0; f->send_meta_data = 0;
+    throttle_init(f->events);
     f->cascade = nullptr; f->stream = nullptr; f->image_to_overlay = nullptr;
     f->events_queue = g_queue_new();
     g_rec_mutex_init(&f->mutex);
@@ -522,13 +449,10 @@ static void nvca_face_class_init(NvcaFaceClass *klass)
 {
     GObjectClass *go = G_OBJECT_CLASS(klass);
     GstVideoFilterClass *vf = GST_VIDEO_FILTER_CLASS(klass);
-    GstCaps *caps = gst_caps_from_string(GST_VIDEO_CAPS_MAKE("{ BGR }"));
-    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("src", GST_PAD_SRC, GST_PAD_ALWAYS, caps));
-    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("sink", GST_PAD_SINK, GST_PAD_ALWAYS, caps));
-    gst_caps_unref(caps);
+    install_pads(klass, GST_VIDEO_CAPS_MAKE("{ BGR }"));
     gst_element_class_set_static_metadata(GST_ELEMENT_CLASS(klass), "face detection filter element", "Video/Filter",
                                           "Haar face detector (MI355X / HIP implementation of NuboFaceDetector)", "nubovca-hip");
-    go->set_property = nvca_face_set_property; go->get_property = nvca_face_get_property; go->finalize = nvca_face_finalize;
+    go->set_property = set_property<NvcaFace>; go->get_property = get_property<NvcaFace>; go->finalize = nvca_face_finalize;
     INT_PROP(go, FP_VIEW, "view-faces", "view faces", "draw or hide the detected faces on the stream", 0, 1);
     INT_PROP(go, FP_DETECT_EVENT, "detect-event", "detect event", "0 => always; 1 => only after a motion event", 0, 1);
     INT_PROP(go, FP_META, "send-meta-data", "send meta data", "0 (default) => no meta data; 1 => send the face boxes as metadata", 0, 1);
@@ -558,47 +482,34 @@ struct NvcaTrk {
     GpuSlot *slot;
     nvca_tracker *trk;
     nvca_tracker_params p;
-    int visual_mode, server_events, events_ms;
-    double time_events_ms;
+    int visual_mode;
+    EventsThrottle events;
+    static constexpr const char *set_where = "nvca_trk_set_property", *get_where = "nvca_trk_get_property";
 };
 struct NvcaTrkClass { GstVideoFilterClass parent; };
 G_DEFINE_TYPE(NvcaTrk, nvca_trk, GST_TYPE_VIDEO_FILTER)
 enum { TP_0, TP_THRESHOLD, TP_MIN_AREA, TP_MAX_AREA, TP_DISTANCE, TP_VISUAL, TP_EVENTS, TP_EVENTS_MS };
 static guint trk_signal = 0;
 
-static void nvca_trk_set_property(GObject *o, guint id, const GValue *v, GParamSpec *ps)
-try {
-    NvcaTrk *t = (NvcaTrk *)o;
-    NvcaRecLock nvca_lock_(&t->mutex);
+static int *prop_int(NvcaTrk *t, guint id, bool)
+{
     switch (id) {
-    case TP_THRESHOLD: t->p.threshold = g_value_get_int(v); break;
-    case TP_MIN_AREA: t->p.min_area = g_value_get_int(v); break;
-    case TP_MAX_AREA: t->p.max_area = g_value_get_long(v); break;
-    case TP_DISTANCE: t->p.distance = g_value_get_int(v); break;
-    case TP_VISUAL: t->visual_mode = g_value_get_int(v); break;
-    case TP_EVENTS: t->server_events = g_value_get_int(v); t->time_events_ms = now_ms(); break;
-    case TP_EVENTS_MS: t->events_ms = g_value_get_int(v); break;
-    default: G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps); break;
+    case TP_THRESHOLD: return &t->p.threshold;
+    case TP_MIN_AREA: return &t->p.min_area;
+    case TP_DISTANCE: return &t->p.distance;
+    case TP_VISUAL: return &t->visual_mode;
+    case TP_EVENTS: return &t->events.server_events;
+    case TP_EVENTS_MS: return &t->events.events_ms;
     }
-    if (t->trk) nvca_tracker_set_params(t->trk, &t->p);
+    return NULL;
 }
-NVCA_GST_CATCH_VOID("nvca_trk_set_property")
-static void nvca_trk_get_property(GObject *o, guint id, GValue *v, GParamSpec *ps)
-try {
-    NvcaTrk *t = (NvcaTrk *)o;
-    NvcaRecLock nvca_lock_(&t->mutex);
-    switch (id) {
-    case TP_THRESHOLD: g_value_set_int(v, t->p.threshold); break;
-    case TP_MIN_AREA: g_value_set_int(v, t->p.min_area); break;
-    case TP_MAX_AREA: g_value_set_long(v, t->p.max_area); break;
-    case TP_DISTANCE: g_value_set_int(v, t->p.distance); break;
-    case TP_VISUAL: g_value_set_int(v, t->visual_mode); break;
-    case TP_EVENTS: g_value_set_int(v, t->server_events); break;
-    case TP_EVENTS_MS: g_value_set_int(v, t->events_ms); break;
-    default: G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps); break;
-    }
+static bool prop_other(NvcaTrk *t, guint id, const GValue *set, GValue *get)
+{
+    if (id != TP_MAX_AREA) return false;
+    if (set) t->p.max_area = g_value_get_long(set); else g_value_set_long(get, t->p.max_area);
+    return true;
 }
-NVCA_GST_CATCH_VOID("nvca_trk_get_property")
+static void sync_params(NvcaTrk *t) { if (t->trk) nvca_tracker_set_params(t->trk, &t->p); }
 
 static GstFlowReturn nvca_trk_transform_frame_ip(GstVideoFilter *filter, GstVideoFrame *frame)
 try {
@@ -607,38 +518,18 @@ try {
     if (!t->trk) { if (!t->slot) t->slot = take_slot(); nvca_ctx *ctx = t->slot->ctx; if (ctx && nvca_tracker_create(ctx, &t->p, &t->trk) != NVCA_OK) t->trk = nullptr; }
     if (t->trk) {
         note_frame_memory(t->slot, frame);
-        nvca_frame nf;
-        nf.data = GST_VIDEO_FRAME_PLANE_DATA(frame, 0);
-        nf.width = GST_VIDEO_FRAME_WIDTH(frame); nf.height = GST_VIDEO_FRAME_HEIGHT(frame);
-        nf.stride = GST_VIDEO_FRAME_PLANE_STRIDE(frame, 0);
-        nf.mem = NVCA_MEM_HOST; nf.pts = GST_BUFFER_PTS(frame->buffer);
         const double timestamp = 1000.0 * clock() / CLOCKS_PER_SEC;          /* TRK/gstnubotracker.cpp:349 */
-        int n = 0;
-        nvca_rect *bx = (nvca_rect *)g_malloc(sizeof(nvca_rect) * kTrkCap);
-        TrkReq req{t->trk, nf, timestamp, bx, 0, NVCA_OK, false};
+        const std::unique_ptr<nvca_rect[]> bx(new nvca_rect[kTrkCap]);
+        TrkReq req{{t->trk, frame_of(frame), {bx.get()}, {0}, NVCA_OK, false}, timestamp};
         nvca_ctx *ctx = t->slot->ctx;
-        const int rc = t->slot->trk_q.process(&req, [ctx](std::vector<TrkReq *> &round) { trk_run_round(ctx, round); });
-        n = req.n;
+        const int rc = t->slot->trk_q.process(&req, [ctx](std::vector<TrkReq *> &round) { run_round<TrkCalls>(ctx, round); });
         if (rc != NVCA_OK) GST_ERROR("nvca_tracker_process: %d", rc);
-        else if (n > 0) {
-            if (n > 4096) n = 4096;
-            if (t->visual_mode > 0) {                        /* TRK/gstnubotracker.cpp:389: tl() .. br(), Scalar(0,0,255) */
-                static const guint8 col[4] = {0, 0, 255, 0};
-                const Canvas cv = canvas_of(t->slot->ctx, frame);
-                for (int i = 0; i < n; i++) draw_rect3(cv, bx[i].x, bx[i].y, bx[i].x + bx[i].w, bx[i].y + bx[i].h, col);
-            }
-            std::string s;
-            if (1 == t->server_events)
-                for (int i = 0; i < n; i++)
-                    s += "x:" + std::to_string((guint)bx[i].x) + ",y:" + std::to_string((guint)bx[i].y) + ",width:" +
-                         std::to_string((guint)bx[i].w) + ",height:" + std::to_string((guint)bx[i].h) + ";";
-            const double now = now_ms();
-            if (1 == t->server_events && now - t->time_events_ms > t->events_ms) {   /* :402-414 */
-                t->time_events_ms = now;
-                g_signal_emit(G_OBJECT(t), trk_signal, 0, s.c_str());
-            }
+        else {
+            const int n = std::min(req.n[0], kTrkCap);
+            const ElementOutput out = tracker_output(bx.get(), n, t->visual_mode);
+            draw_outlines(frame, out.shapes);
+            emit_if_due(t, trk_signal, t->events, n, out.payload);
         }
-        g_free(bx);
     }
     return GST_FLOW_OK;
 }
@@ -647,10 +538,7 @@ NVCA_GST_CATCH("nvca_trk_transform_frame_ip", GST_FLOW_OK)
 static void nvca_trk_finalize(GObject *o)
 try {
     NvcaTrk *t = (NvcaTrk *)o;
-    if (getenv("NVCA_GST_STATS") && t->slot) {
-        std::lock_guard<std::mutex> lk(t->slot->trk_q.m);
-        fprintf(stderr, "nubovca: largest combined tracker batch %d (slot %d)\n", t->slot->trk_q.max_batch, t->slot->index);
-    }
+    if (getenv("NVCA_GST_STATS") && t->slot) print_batch_stats(t->slot->trk_q, "tracker", t->slot->index);
     if (t->trk) nvca_tracker_destroy(t->trk);
     g_rec_mutex_clear(&t->mutex);
     G_OBJECT_CLASS(nvca_trk_parent_class)->finalize(o);
@@ -659,20 +547,18 @@ NVCA_GST_CATCH_VOID("nvca_trk_finalize")
 static void nvca_trk_init(NvcaTrk *t)
 try {
     nvca_tracker_params_default(&t->p);                     /* TRK/gstnubotracker.cpp:457-466 */
-    t->visual_mode = 0; t->server_events = 0; t->events_ms = 30001; t->time_events_ms = 0; t->trk = nullptr;
+    t->visual_mode = 0; t->trk = nullptr;
+    throttle_init(t->events);
     g_rec_mutex_init(&t->mutex);
 }
 NVCA_GST_CATCH_VOID("nvca_trk_init")
 static void nvca_trk_class_init(NvcaTrkClass *klass)
 {
     GObjectClass *go = G_OBJECT_CLASS(klass);
-    GstCaps *caps = gst_caps_from_string(GST_VIDEO_CAPS_MAKE("{ BGRA }"));
-    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("src", GST_PAD_SRC, GST_PAD_ALWAYS, caps));
-    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("sink", GST_PAD_SINK, GST_PAD_ALWAYS, caps));
-    gst_caps_unref(caps);
+    install_pads(klass, GST_VIDEO_CAPS_MAKE("{ BGRA }"));
     gst_element_class_set_static_metadata(GST_ELEMENT_CLASS(klass), "motion tracker filter element", "Video/Filter",
                                           "Motion-history tracker (MI355X / HIP implementation of NuboTracker)", "nubovca-hip");
-    go->set_property = nvca_trk_set_property; go->get_property = nvca_trk_get_property; go->finalize = nvca_trk_finalize;
+    go->set_property = set_property<NvcaTrk>; go->get_property = get_property<NvcaTrk>; go->finalize = nvca_trk_finalize;
     INT_PROP(go, TP_THRESHOLD, "set_threshold", "threshold", "motion threshold (20 default)", 0, 255);
     INT_PROP(go, TP_MIN_AREA, "set_min_area", "min area", "minimum object area (50 default)", 0, 10000);
     g_object_class_install_property(go, TP_MAX_AREA, g_param_spec_long("set_max_area", "max area", "maximum object area (30000 default)",
@@ -685,7 +571,6 @@ static void nvca_trk_class_init(NvcaTrkClass *klass)
     trk_signal = g_signal_new("tracker-event", G_TYPE_FROM_CLASS(klass), G_SIGNAL_RUN_LAST, 0, NULL, NULL, NULL, G_TYPE_NONE, 1,
                               G_TYPE_STRING);
 }
-
 
 // =====================================================================================
 // nuboeyedetector / nubonosedetector / nubomouthdetector / nuboeardetector  (one implementation, four GTypes)
@@ -712,53 +597,30 @@ struct NvcaPart {
     GpuSlot *slot;
     nvca_cascade *cf, *ca, *cb; nvca_part_stream *stream;
     nvca_part_params p;
-    int view, meta_data, server_events, events_ms;
-    double time_events_ms;
+    int view, meta_data;
+    EventsThrottle events;
     GstStructure *image_to_overlay;
+    static constexpr const char *set_where = "nvca_part_set_property", *get_where = "nvca_part_get_property";
 };
 struct NvcaPartClass { GstVideoFilterClass parent; PartDesc *desc; };
 enum { PP_0, PP_VIEW, PP_DETECT_EVENT, PP_META, PP_WIDTH, PP_X_EVERY_4, PP_SCALE, PP_EVENTS, PP_EVENTS_MS, PP_OVERLAY };
 
-static void nvca_part_set_property(GObject *o, guint id, const GValue *v, GParamSpec *ps)
-try {
-    NvcaPart *f = (NvcaPart *)o;
-    NvcaRecLock nvca_lock_(&f->mutex);
+static int *prop_int(NvcaPart *f, guint id, bool)
+{
     switch (id) {
-    case PP_VIEW: f->view = g_value_get_int(v); break;
-    case PP_DETECT_EVENT: f->p.detect_event = g_value_get_int(v); break;
-    case PP_META: f->meta_data = g_value_get_int(v); break;
-    case PP_WIDTH: f->p.width_to_process = g_value_get_int(v); break;
-    case PP_X_EVERY_4: f->p.process_x_every_4 = g_value_get_int(v); break;
-    case PP_SCALE: f->p.scale_factor_pct = g_value_get_int(v); break;
-    case PP_EVENTS: f->server_events = g_value_get_int(v); f->time_events_ms = now_ms(); break;
-    case PP_EVENTS_MS: f->events_ms = g_value_get_int(v); break;
-    case PP_OVERLAY:
-        if (f->image_to_overlay) gst_structure_free(f->image_to_overlay);
-        f->image_to_overlay = (GstStructure *)g_value_dup_boxed(v);
-        break;
-    default: G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps); break;
+    case PP_VIEW: return &f->view;
+    case PP_DETECT_EVENT: return &f->p.detect_event;
+    case PP_META: return &f->meta_data;
+    case PP_WIDTH: return &f->p.width_to_process;
+    case PP_X_EVERY_4: return &f->p.process_x_every_4;
+    case PP_SCALE: return &f->p.scale_factor_pct;
+    case PP_EVENTS: return &f->events.server_events;
+    case PP_EVENTS_MS: return &f->events.events_ms;
     }
-    if (f->stream) nvca_part_stream_set_params(f->stream, &f->p);
+    return NULL;
 }
-NVCA_GST_CATCH_VOID("nvca_part_set_property")
-static void nvca_part_get_property(GObject *o, guint id, GValue *v, GParamSpec *ps)
-try {
-    NvcaPart *f = (NvcaPart *)o;
-    NvcaRecLock nvca_lock_(&f->mutex);
-    switch (id) {
-    case PP_VIEW: g_value_set_int(v, f->view); break;
-    case PP_DETECT_EVENT: g_value_set_int(v, f->p.detect_event); break;
-    case PP_META: g_value_set_int(v, f->meta_data); break;
-    case PP_WIDTH: g_value_set_int(v, f->p.width_to_process); break;
-    case PP_X_EVERY_4: g_value_set_int(v, f->p.process_x_every_4); break;
-    case PP_SCALE: g_value_set_int(v, f->p.scale_factor_pct); break;
-    case PP_EVENTS: g_value_set_int(v, f->server_events); break;
-    case PP_EVENTS_MS: g_value_set_int(v, f->events_ms); break;
-    case PP_OVERLAY: g_value_set_boxed(v, f->image_to_overlay); break;
-    default: G_OBJECT_WARN_INVALID_PROPERTY_ID(o, id, ps); break;
-    }
-}
-NVCA_GST_CATCH_VOID("nvca_part_get_property")
+static bool prop_other(NvcaPart *f, guint id, const GValue *set, GValue *get) { return id == PP_OVERLAY && overlay_prop(&f->image_to_overlay, set, get); }
+static void sync_params(NvcaPart *f) { if (f->stream) nvca_part_stream_set_params(f->stream, &f->p); }
 
 static void part_lazy_init(NvcaPart *f)
 {
@@ -766,20 +628,12 @@ static void part_lazy_init(NvcaPart *f)
     if (!f->slot) f->slot = take_slot();
     nvca_ctx *ctx = f->slot->ctx;
     if (!ctx) return;
-    struct { nvca_cascade **c; const char *file; } need[3] = {{&f->cf, f->desc->face_file}, {&f->ca, f->desc->a_file}, {&f->cb, f->desc->b_file}};
-    for (auto &n : need) {
-        if (!n.file || *n.c) continue;
-        const std::string path = cascade_path(n.file);
-        *n.c = acquire_cascade(f->slot, path);
-        if (!*n.c) {
-            GST_ERROR("Error charging cascade %s: %s", path.c_str(), nvca_last_error(ctx));
-            return;
-        }
-    }
+    const PartDesc *d = f->desc;
+    if (!need_cascade(f->slot, d->face_file, &f->cf) || !need_cascade(f->slot, d->a_file, &f->ca) || !need_cascade(f->slot, d->b_file, &f->cb)) return;
     if (nvca_part_stream_create(ctx, &f->p, f->cf, f->ca, f->cb, &f->stream) != NVCA_OK) f->stream = nullptr;
 }
 
-// faces handed over by an upstream element (EYE/kmseyedetect.cpp:680-724): sub-structures whose type == "face"
+// faces handed over by an upstream element (message_faces)
 static gboolean nvca_part_sink_event(GstBaseTransform *trans, GstEvent *event)
 try {
     NvcaPart *f = (NvcaPart *)trans;
@@ -788,41 +642,14 @@ try {
         NvcaRecLock nvca_lock_(&f->mutex);
         if (m && f->p.detect_event) {
             part_lazy_init(f);
-            nvca_rect faces[64]; int n = 0;
-            const gint len = gst_structure_n_fields(m);
-            for (gint i = 0; i < len && n < 64; i++) {
-                const gchar *name = gst_structure_nth_field_name(m, i);
-                if (g_strcmp0(name, "timestamp") == 0) continue;
-                GstStructure *d = NULL;
-                if (!gst_structure_get(m, name, GST_TYPE_STRUCTURE, &d, NULL) || !d) continue;
-                const gchar *type = gst_structure_get_string(d, "type");
-                if (g_strcmp0(type, "face") == 0) {
-                    guint x = 0, y = 0, w = 0, h = 0;
-                    gst_structure_get(d, "x", G_TYPE_UINT, &x, "y", G_TYPE_UINT, &y, "width", G_TYPE_UINT, &w, "height", G_TYPE_UINT, &h, NULL);
-                    faces[n++] = nvca_rect{(int)x, (int)y, (int)w, (int)h};
-                }
-                gst_structure_free(d);
-            }
+            nvca_rect faces[kPartCap];
+            const int n = message_faces(m, faces, kPartCap);
             if (f->stream) nvca_part_stream_push_faces(f->stream, faces, n);
         }
     }
     return GST_BASE_TRANSFORM_CLASS(f->desc->parent_class)->sink_event(trans, event);
 }
 NVCA_GST_CATCH("nvca_part_sink_event", FALSE)
-
-static void add_box(GstStructure *message, const char *sname, const char *type, int idx, const nvca_rect &r, int mul)
-{
-    GstStructure *st = gst_structure_new(sname, "type", G_TYPE_STRING, type, "x", G_TYPE_UINT, (guint)r.x * mul, "y", G_TYPE_UINT,
-                                         (guint)r.y * mul, "width", G_TYPE_UINT, (guint)r.w * mul, "height", G_TYPE_UINT, (guint)r.h * mul, NULL);
-    char id[16]; snprintf(id, sizeof(id), "%d", idx);
-    gst_structure_set(message, id, GST_TYPE_STRUCTURE, st, NULL);
-    gst_structure_free(st);
-}
-static std::string box_str(const nvca_rect &r)
-{
-    return "x:" + std::to_string((guint)r.x) + ",y:" + std::to_string((guint)r.y) + ",width:" + std::to_string((guint)r.w) +
-           ",height:" + std::to_string((guint)r.h) + ";";
-}
 
 static GstFlowReturn nvca_part_transform_frame_ip(GstVideoFilter *filter, GstVideoFrame *frame)
 try {
@@ -831,80 +658,21 @@ try {
     part_lazy_init(f);
     if (f->stream && f->p.width_to_process > 0) {
         note_frame_memory(f->slot, frame);
-        nvca_frame nf;
-        nf.data = GST_VIDEO_FRAME_PLANE_DATA(frame, 0);
-        nf.width = GST_VIDEO_FRAME_WIDTH(frame); nf.height = GST_VIDEO_FRAME_HEIGHT(frame);
-        nf.stride = GST_VIDEO_FRAME_PLANE_STRIDE(frame, 0);
-        nf.mem = NVCA_MEM_HOST; nf.pts = GST_BUFFER_PTS(frame->buffer);
-        nvca_rect a[64], b[64], faces[64]; int na = 0, nb = 0, nfaces = 0;
+        nvca_rect a[kPartCap], b[kPartCap], faces[kPartCap];
         // part detectors of other streams (and other kinds) that arrive meanwhile share the call: nvca_part_batch_process
-        PartReq req{f->stream, nf, a, b, 0, 0, NVCA_OK, false};
+        PartReq req{f->stream, frame_of(frame), {a, b}, {0, 0}, NVCA_OK, false};
         nvca_ctx *ctx = f->slot->ctx;
-        const int rc = f->slot->part_q.process(&req, [ctx](std::vector<PartReq *> &round) { part_run_round(ctx, round); });
-        na = req.na; nb = req.nb;
+        const int rc = f->slot->part_q.process(&req, [ctx](std::vector<PartReq *> &round) { run_round<PartCalls>(ctx, round); });
         if (rc != NVCA_OK) GST_ERROR("nvca_part_stream_process: %d", rc);
         else {
-            na = MIN(na, 64); nb = MIN(nb, 64);
-            nvca_part_stream_faces(f->stream, faces, 64, &nfaces); nfaces = MIN(nfaces, 64);
-            const int kind = f->desc->kind;
-            std::string str; int i = 0;
-            GstStructure *message = gst_structure_new_empty(kind == NVCA_PART_NOSE ? "noses" : "message");
-            if (kind != NVCA_PART_NOSE) {
-                GstStructure *ts = gst_structure_new("time", "pts", G_TYPE_UINT64, GST_BUFFER_PTS(frame->buffer), NULL);
-                gst_structure_set(message, "timestamp", GST_TYPE_STRUCTURE, ts, NULL);
-                gst_structure_free(ts);
-            }
-            if (kind == NVCA_PART_EYE) {                 // left eyes first, then right eyes (EYE :245-284)
-                for (int k = 0; k < nb; k++, i++) { add_box(message, "eye_left", "eye", i, b[k], 1); str += box_str(b[k]); }
-                for (int k = 0; k < na; k++, i++) { add_box(message, "eye_right", "eye", i, a[k], 1); str += box_str(a[k]); }
-            } else if (kind == NVCA_PART_NOSE) {
-                for (int k = 0; k < na; k++, i++) { add_box(message, "noses", "nose", i, a[k], 1); str += box_str(a[k]); }
-            } else if (kind == NVCA_PART_MOUTH) {        // faces x norm_faces (int of scale_o2f), then mouths (MOUTH :221-255)
-                const int norm_faces = f->p.detect_event ? 1 : (int)(((float)nf.width) / ((float)160));
-                for (int k = 0; k < nfaces; k++, i++) add_box(message, "face", "face", i, faces[k], norm_faces);
-                for (int k = 0; k < na; k++, i++) { add_box(message, "mouth", "mouth", i, a[k], 1); str += box_str(a[k]); }
-            } else {                                     // EAR: right list then left list; the event is never pushed (:196-290)
-                for (int k = 0; k < nb; k++) str += box_str(b[k]);
-                for (int k = 0; k < na; k++) str += box_str(a[k]);
-            }
-            if (1 == f->view && !f->image_to_overlay) {
-                const Canvas cv = canvas_of(f->slot->ctx, frame);
-                if (kind == NVCA_PART_EYE) {                 // one circle per side, first box only (EYE :1069-1099)
-                    static const guint8 col[4] = {255, 0, 0, 0};              /* Scalar(255, 0, 0) */
-                    int radius = -1;
-                    if (na > 0) {
-                        radius = (int)lrint((a[0].w + a[0].h) * 0.25);
-                        draw_ring4(cv, a[0].x + a[0].w / 2, a[0].y + a[0].h / 2, radius, col);
-                    }
-                    if (nb > 0) {
-                        if (radius < 0) radius = (int)lrint((b[0].w + b[0].h) * 0.25);
-                        draw_ring4(cv, b[0].x + b[0].w / 2, b[0].y + b[0].h / 2, radius, col);
-                    }
-                } else {
-                    // palettes and corner arithmetic as written in NOSE :808-815,902-905 (x + w, y + h - 1),
-                    // MOUTH :814-821,900-903 (x + w - 1, y + h - 1), EAR :736-743,754-758 (x + w, y + h - 1)
-                    static const guint8 nose_col[8][4] = {BGR_OF_RGB(255, 0, 255), BGR_OF_RGB(255, 0, 0), BGR_OF_RGB(255, 255, 0), BGR_OF_RGB(255, 128, 0),
-                                                          BGR_OF_RGB(0, 255, 0), BGR_OF_RGB(0, 255, 255), BGR_OF_RGB(0, 128, 255), BGR_OF_RGB(0, 0, 255)};
-                    static const guint8 mouth_col[8][4] = {BGR_OF_RGB(255, 255, 0), BGR_OF_RGB(255, 128, 0), BGR_OF_RGB(255, 0, 0), BGR_OF_RGB(255, 0, 255),
-                                                           BGR_OF_RGB(0, 128, 255), BGR_OF_RGB(0, 0, 255), BGR_OF_RGB(0, 255, 255), BGR_OF_RGB(0, 255, 0)};
-                    static const guint8 ear_col[8][4] = {BGR_OF_RGB(0, 0, 255), BGR_OF_RGB(0, 128, 255), BGR_OF_RGB(0, 255, 255), BGR_OF_RGB(0, 255, 0),
-                                                         BGR_OF_RGB(255, 128, 0), BGR_OF_RGB(255, 255, 0), BGR_OF_RGB(255, 0, 0), BGR_OF_RGB(255, 0, 255)};
-                    const guint8 (*pal)[4] = kind == NVCA_PART_NOSE ? nose_col : kind == NVCA_PART_MOUTH ? mouth_col : ear_col;
-                    const int dx = kind == NVCA_PART_MOUTH ? -1 : 0;
-                    int j = 0;
-                    if (kind == NVCA_PART_EAR) for (int k = 0; k < nb; k++, j++) draw_rect3(cv, b[k].x, b[k].y, b[k].x + b[k].w + dx, b[k].y + b[k].h - 1, pal[j % 8]);
-                    for (int k = 0; k < na; k++, j++) draw_rect3(cv, a[k].x, a[k].y, a[k].x + a[k].w + dx, a[k].y + a[k].h - 1, pal[j % 8]);
-                }
-            }
-            if (kind == NVCA_PART_EAR) gst_structure_free(message);
-            else gst_pad_push_event(GST_BASE_TRANSFORM(f)->srcpad, gst_event_new_custom(GST_EVENT_CUSTOM_DOWNSTREAM, message));
-            if (na > 0 || nb > 0) {
-                const double t = now_ms();
-                if (1 == f->server_events && t - f->time_events_ms > f->events_ms) {
-                    f->time_events_ms = t;
-                    g_signal_emit(G_OBJECT(f), f->desc->signal_id, 0, str.c_str());
-                }
-            }
+            const int na = std::min(req.n[0], kPartCap), nb = std::min(req.n[1], kPartCap);
+            int nfaces = 0;
+            nvca_part_stream_faces(f->stream, faces, kPartCap, &nfaces);
+            ElementOutput out = part_output(f->desc->kind, a, na, b, nb, faces, std::min(nfaces, kPartCap), req.frame.width, req.frame.pts,
+                                            f->p.detect_event, f->view, f->image_to_overlay != NULL);
+            draw_outlines(frame, out.shapes);
+            push_event(f, out);
+            emit_if_due(f, f->desc->signal_id, f->events, na + nb, out.payload);
         }
     }
     return GST_FLOW_OK;
@@ -914,10 +682,7 @@ NVCA_GST_CATCH("nvca_part_transform_frame_ip", GST_FLOW_OK)
 static void nvca_part_finalize(GObject *o)
 try {
     NvcaPart *f = (NvcaPart *)o;
-    if (getenv("NVCA_GST_STATS") && f->slot) {
-        std::lock_guard<std::mutex> lk(f->slot->part_q.m);
-        fprintf(stderr, "nubovca: largest combined part-detector batch %d (slot %d)\n", f->slot->part_q.max_batch, f->slot->index);
-    }
+    if (getenv("NVCA_GST_STATS") && f->slot) print_batch_stats(f->slot->part_q, "part-detector", f->slot->index);
     if (f->stream) nvca_part_stream_destroy(f->stream);
     if (f->cf) release_cascade(f->slot, f->cf);
     if (f->ca) release_cascade(f->slot, f->ca);
@@ -932,7 +697,8 @@ try {
     NvcaPart *f = (NvcaPart *)inst;
     f->desc = ((NvcaPartClass *)klass)->desc;
     nvca_part_params_default(&f->p, f->desc->kind);      /* width-to-process 320, process 4 of 4, scale factor 25 */
-    f->view = 0; f->meta_data = 0; f->server_events = 0; f->events_ms = 30001; f->time_events_ms = 0;
+    f->view = 0; f->meta_data = 0;
+    throttle_init(f->events);
     f->cf = f->ca = f->cb = nullptr; f->stream = nullptr; f->image_to_overlay = nullptr;
     g_rec_mutex_init(&f->mutex);
 }
@@ -943,13 +709,10 @@ static void nvca_part_class_init(gpointer klass, gpointer class_data)
     ((NvcaPartClass *)klass)->desc = d;
     d->parent_class = g_type_class_peek_parent(klass);
     GObjectClass *go = G_OBJECT_CLASS(klass);
-    GstCaps *caps = gst_caps_from_string(GST_VIDEO_CAPS_MAKE("{ BGR }"));
-    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("src", GST_PAD_SRC, GST_PAD_ALWAYS, caps));
-    gst_element_class_add_pad_template(GST_ELEMENT_CLASS(klass), gst_pad_template_new("sink", GST_PAD_SINK, GST_PAD_ALWAYS, caps));
-    gst_caps_unref(caps);
+    install_pads(klass, GST_VIDEO_CAPS_MAKE("{ BGR }"));
     gst_element_class_set_static_metadata(GST_ELEMENT_CLASS(klass), d->longname, "Video/Filter",
                                           "Haar part detector (MI355X / HIP implementation)", "nubovca-hip");
-    go->set_property = nvca_part_set_property; go->get_property = nvca_part_get_property; go->finalize = nvca_part_finalize;
+    go->set_property = set_property<NvcaPart>; go->get_property = get_property<NvcaPart>; go->finalize = nvca_part_finalize;
     INT_PROP(go, PP_VIEW, d->view_prop, "view", "draw or hide the detections on the stream", 0, 1);
     INT_PROP(go, PP_DETECT_EVENT, "detect-event", "detect event", "0 => own face pass; 1 => faces come from upstream events", 0, 1);
     INT_PROP(go, PP_META, d->meta_prop, "send meta data", "0 (default) => no meta data", 0, 1);
@@ -981,14 +744,6 @@ static void debug_category_once()
         g_once_init_leave(&once, 1);
     }
 }
-static gboolean plugin_init(GstPlugin *plugin)
-{
-    debug_category_once();
-    gboolean ok = gst_element_register(plugin, "nubofacedetector", GST_RANK_NONE, nvca_face_get_type()) &&
-                  gst_element_register(plugin, "nubotracker", GST_RANK_NONE, nvca_trk_get_type());
-    for (PartDesc &d : part_descs) ok = ok && gst_element_register(plugin, d.factory, GST_RANK_NONE, nvca_part_type(&d));
-    return ok;
-}
 // One element under a plugin of its own: the reference ships six plugins (libnubofacedetector.so with plugin name
 // nubofacedetector, libnuboeyedetector.so / eyefilter, libnubonosedetector.so / nubonosedetector, libnubomouthdetector.so /
 // nubomouthdetector, libnuboeardetector.so / earfilter, libnubotracker.so / nubotracker -- modules/nubo_*/.../src/gst-plugins/
@@ -1005,6 +760,13 @@ extern "C" __attribute__((visibility("default"))) gboolean nvca_gst_register_ele
     for (PartDesc &d : part_descs)
         if (!strcmp(factory, d.factory)) return gst_element_register(plugin, factory, GST_RANK_NONE, nvca_part_type(&d));
     return FALSE;
+}
+
+static gboolean plugin_init(GstPlugin *plugin)
+{
+    gboolean ok = nvca_gst_register_element(plugin, "nubofacedetector") && nvca_gst_register_element(plugin, "nubotracker");
+    for (PartDesc &d : part_descs) ok = ok && nvca_gst_register_element(plugin, d.factory);
+    return ok;
 }
 
 #ifndef PACKAGE

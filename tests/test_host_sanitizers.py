@@ -195,6 +195,35 @@ def test_work_pool_under_thread_sanitizer():
     assert "ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
 
 
+def test_gst_combiner_under_thread_sanitizer():
+    """the GStreamer shim's leader election (gst/combiner.h): 12 threads x 4000 requests through one Combiner under TSan; every
+    request is run exactly once and gets its own status back (the driver checks both), the rounds hold all 48000 requests, and
+    rounds were really shared -- a run that never combined anything must not pass.  With NVCA_GST_NO_COMBINE every request is a
+    round of its own and max_batch is never touched."""
+    if not os.path.exists(CLANG):
+        pytest.skip("no clang++ with sanitizer runtimes")
+    out = os.path.join(SAN, "build", "combiner_driver")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    srcs = [os.path.join(SAN, "combiner_driver.cpp"), os.path.join(ROOT, "nubomedia-vca_amd", "gst", "combiner.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in srcs):
+        r = subprocess.run([CLANG, "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread", srcs[0], "-o", out], capture_output=True, text=True)
+        if r.returncode != 0 and "tsan" in r.stderr.lower():
+            pytest.skip("no TSan runtime")
+        assert r.returncode == 0, r.stderr[-3000:]
+    env = {k: v for k, v in os.environ.items() if k != "NVCA_GST_NO_COMBINE"}
+    for extra, single in (({}, False), ({"NVCA_GST_NO_COMBINE": "1"}, True)):
+        r = subprocess.run([out], capture_output=True, text=True, timeout=600, env=dict(env, **extra))
+        assert r.returncode == 0 and "combiner ok" in r.stdout, (r.stdout[-1000:], r.stderr[-3000:])
+        assert "ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
+        got = {k: int(v) for k, v in (w.split("=") for w in r.stdout.split()[2:])}
+        print(extra, got)
+        assert got["requests"] == 48000, got
+        if single:
+            assert got["rounds"] == 48000 and got["largest"] == 1 and got["max_batch"] == 0, got
+        else:
+            assert 2 <= got["max_batch"] <= 12 and got["largest"] == got["max_batch"], got
+
+
 def test_host_range_bookkeeping_under_sanitizers():
     """which caller memory may reach the runtime as a raw pointer, and which streams nvca_host_unregister drains before the pages go
     (csrc/host_ranges.h): direct copies only inside a range that is registered NOW, released ranges are bounced like any memory,
