@@ -49,10 +49,11 @@ struct BounceRing {
     void release() { for (hipEvent_t &e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } buf.release(); }
 };
 
-// tracker workspace (tracker.cpp): slot table, labels, per-root accumulators, component list, frame staging
+// tracker workspace (tracker.cpp; sizes and parts: trk_layout.h): slot table, labels, per-root accumulators, component list, frame staging,
+// segment flags, root list, live-tile list
 struct TrkWorkspace {
     DevBuf slots, labels, acc, out, staging, flags, roots, tiles; PinnedBuf h_slots, h_out;
-    // the live-tile list's marks are stamped with the launch's tick and never cleared (kernels_tracker.hip, TileList): they are
+    // the live-tile list's marks are stamped with the launch's tick and never cleared (trk_layout.h, TileList): they are
     // zeroed when the buffer's layout changes (frame size, batch) and when the tick would come round
     int tick = 0, tiles_w = 0, tiles_h = 0, tiles_batch = 0;
     void release_all() { slots.release(); labels.release(); acc.release(); out.release(); staging.release(); flags.release(); roots.release(); tiles.release(); h_slots.release(); h_out.release(); tiles_w = tiles_h = tiles_batch = 0; }

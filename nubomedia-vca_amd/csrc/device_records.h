@@ -161,7 +161,7 @@ struct PyrLevelDev {
     ResizeView tab;
 };
 
-// ---- tracker (kernels_tracker.hip) ----
+// ---- tracker (kernels_trk_pixel.hip, kernels_trk_ccl.hip); the layout of its work buffers: trk_layout.h ----
 struct TrkSlot {                // per tracker in the batch
     const uint8_t *src;         // BGRA frame; 4:2:0 trackers (nvca_tracker_set_input): the base `yuv`'s plane offsets count from
     uint8_t *prev;              // previous gray  [h][w]
@@ -172,12 +172,10 @@ struct TrkSlot {                // per tracker in the batch
     int has_prev;               // num_frames > 0
     int sstride;
     int min_area;               // __join_objects drops boxes outside (min_area, max_area) before anything else:
-    long long max_area;         // k_ccl_collect does not even report them
+    long long max_area;         // k_ccl_emit / k_ccl_collect do not even report them (report_component)
     YuvPlanes yuv;              // planes of a 4:2:0 frame (the luma stride is sstride); unused by the packed kernels
 };
 struct CompAcc { int minx, miny, maxx, maxy, seed, pad; };   // per root, stored at the root's pixel index
-inline size_t tracker_count_offset(int w, int h, int batch) { return ((size_t)((w + 255) / 256) * h * batch + 63) & ~(size_t)63; }
-inline size_t tracker_flag_bytes(int w, int h, int batch) { return tracker_count_offset(w, h, batch) + sizeof(int) * (size_t)batch; }   // flag bytes, then a live-segment count per slot
 
 // A candidate's key is scale << key_ss | row << key_sy | column of its window, each field as wide as the plan's own grids need
 // (CascadeArgs / LbpArgs: key_sy = bx, key_ss = bx + by): the widths for grids of at most max_nx x max_ny windows on nscales

@@ -201,21 +201,7 @@ int check_img(nvca_ctx *ctx, const void *p, int w, int h, int stride, int bpp, i
     return NVCA_OK;
 }
 
-// ---- 4:2:0 layouts (nvca_pixel_layout): plane p of a w x h frame has yuv_plane_rows() rows of yuv_plane_row_bytes() bytes
-static int yuv_planes_of(const nvca_pixel_layout &l) { return l.format == NVCA_PIX_NV12 ? 2 : 3; }
-static size_t yuv_plane_rows(int p, int h) { return p == 0 ? (size_t)h : (size_t)h / 2; }
-static size_t yuv_plane_row_bytes(const nvca_pixel_layout &l, int p, int w) { return (p == 0 || l.format == NVCA_PIX_NV12) ? (size_t)w : (size_t)w / 2; }
-static size_t yuv_plane_bytes(const nvca_pixel_layout &l, int p, int w, int h)
-{
-    return (size_t)l.stride[p] * (yuv_plane_rows(p, h) - 1) + yuv_plane_row_bytes(l, p, w);
-}
-// bytes from the frame's base to the end of its last plane
-size_t yuv_extent(const nvca_pixel_layout &l, int w, int h)
-{
-    size_t e = 0;
-    for (int p = 0; p < yuv_planes_of(l); p++) e = std::max(e, l.offset[p] + yuv_plane_bytes(l, p, w, h));
-    return e;
-}
+// ---- 4:2:0 layouts (nvca_pixel_layout); the planes' rows, bytes and the frame's extent: yuv_layout.h
 // what is wrong with a w x h frame in this layout (null: nothing) -- the one set of layout rules, for the streams and for the
 // calls that take a host frame without a context
 const char *yuv_layout_fault(const nvca_pixel_layout &l, int w, int h)

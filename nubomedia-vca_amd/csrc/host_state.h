@@ -1,15 +1,16 @@
 // host_state.h -- host-side state and helpers that the library's host sources share (not part of the ABI): the workspace, the
 // cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect_job.cpp, lbp_job.cpp, pyramid.cpp,
 // detect_rounds.cpp, roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, part_logic.cpp, fb_search.cpp,
-// part_stats.cpp, options.cpp, cascade_xml.cpp, pyr_levels.cpp, lbp_tables.cpp and work_pool.cpp do not include it: the CPU drivers under
-// tests/ build those without it (part_logic.cpp, fb_search.cpp, part_stats.cpp, options.cpp, pyr_levels.cpp and lbp_tables.cpp without any
-// HIP header, the others with host doubles of their own).
+// part_stats.cpp, options.cpp, cascade_xml.cpp, pyr_levels.cpp, lbp_tables.cpp, trk_host.cpp and work_pool.cpp do not include it: the CPU
+// drivers under tests/ build those without it (part_logic.cpp, fb_search.cpp, part_stats.cpp, options.cpp, pyr_levels.cpp, lbp_tables.cpp and
+// trk_host.cpp without any HIP header, the others with host doubles of their own).
 #pragma once
 #include "context.h"
 #include "plan.h"
 #include "fb_search.h"
 #include "host_math.h"
 #include "pyr_levels.h"
+#include "yuv_layout.h"
 
 namespace nvca {
 
@@ -142,11 +143,10 @@ int stage_2d(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t sp
 int unstage_2d(nvca_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width_bytes, size_t height, int mem);
 int finish_device_op(nvca_ctx *ctx);
 int check_img(nvca_ctx *ctx, const void *p, int w, int h, int stride, int bpp, int mem);
-// 4:2:0 frames (nvca_pixel_layout): a w x h frame against its layout (NVCA_ERR_ARG with an error text), the bytes from its base to
-// the end of its last plane, and the layout as the kernels read it (null / BGR: fmt 0)
+// 4:2:0 frames (nvca_pixel_layout): a w x h frame against its layout (NVCA_ERR_ARG with an error text) and the layout as the kernels
+// read it (null / BGR: fmt 0); the bytes from its base to the end of its last plane: yuv_layout.h's yuv_extent
 int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h);      // (ctx may be null: no error text then)
 const char *yuv_layout_fault(const nvca_pixel_layout &l, int w, int h);
-size_t yuv_extent(const nvca_pixel_layout &l, int w, int h);
 YuvPlanes yuv_planes(const nvca_pixel_layout *l);
 // what every nvca_*_set_input and every 4:2:0 stream's frame check share: the caller's layout as a stream keeps it, layouts by value,
 // a frame against its stream's layout, a host frame's planes to the device at the caller's offsets

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include "device_records.h"
+#include "trk_layout.h"
 #include "pixel_rules.h"
 
 namespace nvca {
@@ -64,16 +65,33 @@ bool small_integral_fits(const PreGeom &g);
 void launch_small_integral(hipStream_t st, const uint8_t *gray, const uint8_t *lut, int lut_stride, const PreGeom &g, int *sum,
                            unsigned long long *sqsum, int batch);
 
-// ---- tracker (kernels_tracker.hip)
-// out: [0] = component count, [1] unused, then 6 ints per component: slot, first seed index, x, y, w, h
-// flags: one byte per 256-pixel row segment and slot, set by the pixel pass where the motion history holds anything -- the
-// component kernels leave the other segments alone (a static scene with a few moving objects is mostly such segments)
-// roots: [0] = tile roots listed, [1] = the list overflowed, then one entry (slot * w * h + pixel) per tile root; mode: 0 folded component
-// path, 1 per-pixel component kernels, 2 the latter without the pixel pass (fallback behind an overflow of mode 0's list)
-// fmt: 0 BGRA frames (vec4: every frame takes k_trk_pixel4's 16-byte loads), 1 / 2: NV12 / I420 frames, planes per slot (vec4: every plane
-// and stride takes the wide kernel's loads and w % 4 == 0)
-void launch_tracker(hipStream_t st, const void *d_slots, int batch, int w, int h, int fmt, bool vec4, int *labels, void *acc,
-                    int *out, int cap, bool run_ccl, uint8_t *flags, int order /* Switches::trk_order */, int *roots, int roots_cap, int mode, int *tiles, int tick);
+// ---- tracker (kernels_trk_pixel.hip, kernels_trk_ccl.hip).  One launch set: `batch` slots of one size and format.  Every buffer's
+// layout is trk_layout.h's: flags (a byte per 256-pixel row segment and slot, set by the pixel pass where the motion history holds
+// anything -- the component kernels leave the other segments alone: a static scene with a few moving objects is mostly such segments --
+// and the live-segment counts), tiles (the live-tile list), roots (the folded path's tile roots), out (the component list).
+struct TrkLaunch {
+    const TrkSlot *slots; int batch, w, h;
+    int fmt;                      // 0 BGRA frames, 1 / 2: NV12 / I420 frames, planes per slot
+    bool wide;                    // every slot takes the wide pixel kernel's loads (k_trk_pixel4 / k_trk_pixel_yuv8; trk_host.h, trk_wide_ok)
+    int *labels; CompAcc *acc;    // [batch][h][w] parent words / per-root records
+    int *out; int cap;            // component list and the components it holds
+    uint8_t *flags; int *roots; int roots_cap; int *tiles; int tick;
+    int order;                    // Switches::trk_order
+    int rows, rows_uf;            // rows a block of the per-pixel component kernels walks (NVCA_CCL_ROWS / NVCA_CCL_ROWS_UF; <= kCclRowsMax)
+};
+enum TrkRoute {
+    kTrkPixelOnly,                // the pixel pass alone: no slot has a previous frame
+    kTrkFolded,                   // pixel pass, then tile / border / fold / emit
+    kTrkPerPixel,                 // pixel pass, then tile / border / flatten / reduce / collect (NVCA_TRK_FOLD=0)
+    kTrkPerPixelAlone,            // the latter without the pixel pass, on the history an earlier launch left (kTrkFolded's root list overflowed)
+};
+void launch_trk_pixel(hipStream_t st, const TrkLaunch &L);
+void launch_trk_components(hipStream_t st, const TrkLaunch &L, TrkRoute route);
+inline void launch_tracker(hipStream_t st, const TrkLaunch &L, TrkRoute route)
+{
+    if (route != kTrkPerPixelAlone) launch_trk_pixel(st, L);
+    if (route != kTrkPixelOnly) launch_trk_components(st, L, route);
+}
 
 // One launch per kernel; each is a no-op when the plan has no work for its kernel (no tasks, no tiles / bands / strips, no late stage).
 void launch_stage0(hipStream_t st, const CascadeArgs &a, int batch);        // kernels_cascade_gather.hip

@@ -1,9 +1,11 @@
 // tracker.cpp -- NuboTracker stream objects: replaces gst_nubo_tracker_img_conf +
 // gst_nubo_tracker_process (TRK/gstnubotracker.cpp:202-237, 339-421).  Per stream the
 // device keeps the previous gray frame and the motion-history image; every frame runs
-// k_trk_pixel + the connected-component kernels, then __join_objects on the host.
+// k_trk_pixel + the connected-component kernels, then __join_objects on the host.  The pure parts of a call -- launch sets, the
+// wide-kernel predicate, staged sizes, the component lists -- are trk_host.cpp's; the work buffers' layout is trk_layout.h's.
 #include "host_state.h"
 #include "host_logic.h"
+#include "trk_host.h"
 #include <chrono>
 #include <algorithm>
 #include <cstring>
@@ -18,10 +20,6 @@ struct nvca_tracker {
     nvca_pixel_layout input{};        // format NVCA_PIX_BGR: packed BGRA frames; else the planes of its 4:2:0 frames (nvca_tracker_set_input)
     const nvca_pixel_layout *yuv() const { return input.format != NVCA_PIX_BGR ? &input : nullptr; }
 };
-
-namespace {
-constexpr int kCompCap = 1 << 18;
-}
 
 extern "C" {
 
@@ -72,6 +70,131 @@ try {
 }
 NVCA_API_CATCH((t ? t->ctx : nullptr))
 
+} // extern "C"
+
+namespace {
+
+// the three diagnostic variables of the tracker, read once: rows a block of the per-pixel component kernels walks (NVCA_CCL_ROWS: k_ccl_reduce /
+// _collect; NVCA_CCL_ROWS_UF: k_ccl_flatten, the union-find walk) and the share of the pixels the root list holds (NVCA_TRK_ROOTS_DIV=n: 1 / n)
+struct TrkTuning { int rows, rows_uf, roots_div; };
+const TrkTuning &trk_tuning()
+{
+    static const TrkTuning t = [] {
+        auto rows = [](const char *name, int dflt) { const char *e = getenv(name); const int v = e ? atoi(e) : 0; return v > 0 && v <= kCclRowsMax ? v : dflt; };
+        const char *e = getenv("NVCA_TRK_ROOTS_DIV");
+        const int div = e ? atoi(e) : 8;
+        return TrkTuning{rows("NVCA_CCL_ROWS", kCclRowsDefault), rows("NVCA_CCL_ROWS_UF", kCclRowsUf), div >= 1 ? div : 8};
+    }();
+    return t;
+}
+
+// per-stream state of a launch set's members (gst_nubo_tracker_img_conf: MHI re-created zeroed on a size change)
+int ensure_state(nvca_ctx *ctx, nvca_tracker *const *trackers, const int *idx, int batch, int W, int H)
+{
+    const size_t N = (size_t)W * H;
+    for (int b = 0; b < batch; b++) {
+        nvca_tracker *t = trackers[idx[b]];
+        if (t->w == W && t->h == H) continue;
+        if (t->prev.ensure(N + 64) || t->mhi.ensure(N * sizeof(float) + 64)) { ctx->set_error("tracker state allocation failed"); return NVCA_ERR_NOMEM; }
+        NVCA_HIP_CHECK(ctx, hipMemsetAsync(t->mhi.p, 0, N * sizeof(float), ctx->cs()));
+        NVCA_HIP_CHECK(ctx, hipMemsetAsync(t->prev.p, 0, N, ctx->cs()));
+        t->w = W; t->h = H;
+    }
+    return NVCA_OK;
+}
+
+// the work buffers of a launch set (trk_layout.h) and its tick: the live-tile list's marks are zeroed when they are of another layout
+int ensure_workspace(nvca_ctx *ctx, TrkWorkspace &ws, int W, int H, int batch, int roots_cap, size_t stage_bytes, int *tick)
+{
+    const size_t N = (size_t)W * H, tile_bytes = sizeof(int) * trk_tiles_words(W, H, batch), out_bytes = sizeof(int) * trk_comp_words(kCompCap);
+    const void *tiles_before = ws.tiles.p;
+    if (ws.slots.ensure(sizeof(TrkSlot) * batch) || ws.h_slots.ensure(sizeof(TrkSlot) * batch) ||
+        ws.labels.ensure(sizeof(int) * N * batch) || ws.acc.ensure(sizeof(CompAcc) * N * batch) || ws.flags.ensure(trk_flag_bytes(W, H, batch) + 64) ||
+        ws.out.ensure(out_bytes) || ws.h_out.ensure(out_bytes) ||
+        ws.roots.ensure(sizeof(int) * trk_roots_words(roots_cap)) || ws.tiles.ensure(tile_bytes) ||
+        (stage_bytes && ws.staging.ensure(stage_bytes))) { ctx->set_error("tracker workspace allocation failed"); return NVCA_ERR_NOMEM; }
+    if (ws.tiles.p != tiles_before || ws.tiles_w != W || ws.tiles_h != H || ws.tiles_batch != batch || ws.tick >= 0x7ffffffe) {
+        NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.tiles.p, 0, tile_bytes, ctx->cs()));       // marks of another layout (or of two billion ticks ago) mean nothing
+        ws.tiles_w = W; ws.tiles_h = H; ws.tiles_batch = batch; ws.tick = 0;
+    }
+    *tick = ++ws.tick;
+    return NVCA_OK;
+}
+
+// the slot table of a launch set; host frames go to the staging buffer one behind the other (trk_staged_bytes)
+int fill_slots(nvca_ctx *ctx, TrkWorkspace &ws, nvca_tracker *const *trackers, const nvca_frame *frames, const double *ts, const int *idx, int batch, int W, int H)
+{
+    TrkSlot *hs = ws.h_slots.as<TrkSlot>();
+    size_t off = 0;
+    for (int b = 0; b < batch; b++) {
+        nvca_tracker *t = trackers[idx[b]];
+        const nvca_frame &f = frames[idx[b]];
+        TrkSlot &s = hs[b];
+        memset(&s, 0, sizeof(s));
+        if (f.mem == NVCA_MEM_HOST) {
+            uint8_t *d = ws.staging.as<uint8_t>() + off;
+            if (const nvca_pixel_layout *yuv = t->yuv()) { if (int rc = caller_h2d_planes(ctx, d, f.data, *yuv, W, H, ctx->cs())) return rc; }
+            else if (int rc = caller_h2d(ctx, d, f.data, (size_t)f.stride * (H - 1) + (size_t)W * 4, ctx->cs())) return rc;
+            off += trk_staged_bytes(t->yuv(), f.stride, W, H);
+            s.src = d;
+        } else s.src = (const uint8_t *)f.data;
+        s.yuv = yuv_planes(t->yuv());
+        s.prev = t->prev.as<uint8_t>(); s.mhi = t->mhi.as<float>();
+        const double timestamp = ts[idx[b]];
+        s.ts = (float)timestamp; s.delbound = (float)(timestamp - t->p.mhi_duration);    // cvUpdateMotionHistory
+        s.seg = (float)t->p.seg_thresh; s.threshold = t->p.threshold;
+        s.has_prev = t->num_frames > 0; s.sstride = f.stride;
+        s.min_area = t->p.min_area; s.max_area = (long long)t->p.max_area;
+    }
+    NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ws.slots.p, hs, sizeof(TrkSlot) * batch, hipMemcpyHostToDevice, ctx->cs()));
+    return NVCA_OK;
+}
+
+// the live-segment counts only steer the per-pixel kernels' visiting order: zeroed in front of a launch of those
+int clear_segment_counts(nvca_ctx *ctx, TrkWorkspace &ws, int W, int H, int batch)
+{
+    NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.flags.as<uint8_t>() + trk_count_offset(W, H, batch), 0, sizeof(int) * (size_t)batch, ctx->cs()));
+    return NVCA_OK;
+}
+
+int launch_route(nvca_ctx *ctx, const TrkLaunch &L, TrkRoute route)
+{
+    { TimedLaunch tl(ctx, NVCA_K_TRACKER);
+      launch_tracker(ctx->cs(), L, route); }
+    NVCA_LAUNCH_CHECK(ctx);
+    return NVCA_OK;
+}
+
+// The component list of the launch that was just queued, in ws.h_out: the header with the first kCompFirstRead components, a wait, the
+// rest if there are more.  A label error refuses; with `roots_overflowed` given, a root-list overflow is reported there and nothing
+// else is read (the caller launches again); the count is checked before it sizes the second copy.
+int read_components(nvca_ctx *ctx, TrkWorkspace &ws, int *total, bool *roots_overflowed)
+{
+    int *ho = ws.h_out.as<int>();
+    NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ho, ws.out.p, sizeof(int) * trk_comp_words(kCompFirstRead), hipMemcpyDeviceToHost, ctx->cs()));
+    NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
+    if (ho[kCompFlags] & kCompLabelError) {
+        int dbg[kRootsErrorWords] = {0, 0, 0};
+        (void)hipMemcpy(dbg, ws.roots.as<int>() + kRootsError, sizeof(dbg), hipMemcpyDeviceToHost);
+        ctx->set_error("internal: tracker label walk met an unwritten word (" + std::to_string(dbg[0]) + " times; first at " + std::to_string(dbg[1]) + ", kernel " + std::to_string(dbg[2]) + ")");
+        return NVCA_ERR_INTERNAL;
+    }
+    if (roots_overflowed && (ho[kCompFlags] & kCompRootsOverflowed)) { *roots_overflowed = true; return NVCA_OK; }
+    *total = ho[kCompCount];
+    std::string err;
+    if (int rc = trk_component_count(*total, err)) { ctx->set_error(err); return rc; }
+    if (*total > kCompFirstRead) {
+        const size_t done = trk_comp_words(kCompFirstRead);
+        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ho + done, ws.out.as<int>() + done, sizeof(int) * (trk_comp_words(*total) - done), hipMemcpyDeviceToHost, ctx->cs()));
+        NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
+    }
+    return NVCA_OK;
+}
+
+} // namespace
+
+extern "C" {
+
 int nvca_tracker_batch_process(nvca_ctx *ctx, int n, nvca_tracker *const *trackers, const nvca_frame *frames,
                                const double *ts, nvca_rect *out, int cap, int *n_out)
 try {
@@ -81,6 +204,7 @@ try {
     // the trackers' lane: a stream of its own, so the call neither queues behind a face batch in flight nor waits for it
     struct UseLane { nvca_ctx *c; int old; UseLane(nvca_ctx *x, int l) : c(x), old(x->cur_lane) { c->cur_lane = l; } ~UseLane() { c->cur_lane = old; } } use_lane(ctx, kTrackerLane);
     ctx->timer.tick(1);
+    std::vector<TrkFrameKey> keys(n);
     for (int i = 0; i < n; i++) {
         n_out[i] = 0;
         const nvca_frame &f = frames[i];
@@ -89,148 +213,67 @@ try {
         if (const nvca_pixel_layout *yuv = trackers[i]->yuv()) { if (check_yuv_frame(ctx, *yuv, f)) return NVCA_ERR_ARG; }
         else if (!f.data || f.width <= 0 || f.height <= 0 || f.stride < f.width * 4 || (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
         for (int j = 0; j < i; j++) if (trackers[j] == trackers[i]) { ctx->set_error("a tracker may appear once per batch"); return NVCA_ERR_ARG; }
+        keys[i] = TrkFrameKey{f.width, f.height, trackers[i]->input.format};
     }
     TrkWorkspace &ws = ctx->trk;
-    const bool hostprof = ctx->sw.host_profile;
+    const TrkTuning &tune = trk_tuning();
+    const bool hostprof = ctx->sw.host_profile, fold = ctx->sw.trk_fold;
     auto tp0 = std::chrono::steady_clock::now(), tp1 = tp0, tp2 = tp0;
     int total_comps = 0;
-    std::vector<char> done(n, 0);
-    for (int i0 = 0; i0 < n; i0++) {
-        if (done[i0]) continue;
-        // one launch set per (size, format): the pixel kernels are instances per format, the planes travel per slot
-        const int W = frames[i0].width, H = frames[i0].height, fmt = trackers[i0]->input.format;
-        std::vector<int> idx;
-        for (int j = i0; j < n; j++) if (!done[j] && frames[j].width == W && frames[j].height == H && trackers[j]->input.format == fmt) { idx.push_back(j); done[j] = 1; }
-        const int batch = (int)idx.size();
-        const size_t N = (size_t)W * H;
-        // per-stream state (gst_nubo_tracker_img_conf: MHI re-created zeroed on a size change)
+    TrkLaunchSets sets;
+    trk_launch_sets(keys.data(), n, sets);
+    std::vector<std::vector<nvca_rect>> comps;
+    for (int si = 0; si < sets.count(); si++) {
+        const int *idx = sets.member.data() + sets.begin[si];
+        const int batch = sets.begin[si + 1] - sets.begin[si];
+        const int W = keys[idx[0]].w, H = keys[idx[0]].h, fmt = keys[idx[0]].fmt;
+        // state
+        if (int rc = ensure_state(ctx, trackers, idx, batch, W, H)) return rc;
         size_t stage_bytes = 0;
-        bool any_ccl = false, vec4 = (W % 4) == 0;
+        bool any_ccl = false, wide = true;
         for (int b = 0; b < batch; b++) {
-            nvca_tracker *t = trackers[idx[b]];
-            if (t->w != W || t->h != H) {
-                if (t->prev.ensure(N + 64) || t->mhi.ensure(N * sizeof(float) + 64)) { ctx->set_error("tracker state allocation failed"); return NVCA_ERR_NOMEM; }
-                NVCA_HIP_CHECK(ctx, hipMemsetAsync(t->mhi.p, 0, N * sizeof(float), ctx->cs()));
-                NVCA_HIP_CHECK(ctx, hipMemsetAsync(t->prev.p, 0, N, ctx->cs()));
-                t->w = W; t->h = H;
-            }
+            const nvca_tracker *t = trackers[idx[b]];
             const nvca_frame &f = frames[idx[b]];
-            if (const nvca_pixel_layout *yuv = t->yuv()) {
-                if (f.mem == NVCA_MEM_HOST) stage_bytes += round_up(yuv_extent(*yuv, W, H), 256);
-                // k_trk_pixel_yuv8's loads: 8 bytes of luma and of NV12 chroma, 4 bytes of an I420 chroma plane.  A staged host frame
-                // counts as base 0: ws.staging is 256-byte aligned and every staged frame starts on a multiple of 256 bytes in it
-                const uintptr_t base = f.mem == NVCA_MEM_DEVICE ? (uintptr_t)f.data : 0;
-                const size_t cmask = fmt == NVCA_PIX_NV12 ? 7 : 3;
-                if (((base + yuv->offset[0]) & 7) || (yuv->stride[0] & 7) || ((base + yuv->offset[1]) & cmask) || ((size_t)yuv->stride[1] & cmask) ||
-                    (fmt == NVCA_PIX_I420 && (((base + yuv->offset[2]) & 3) || (yuv->stride[2] & 3)))) vec4 = false;
-            } else {
-                if (f.mem == NVCA_MEM_HOST) stage_bytes += ((size_t)f.stride * H + 255) / 256 * 256;
-                if ((f.stride & 15) || (f.mem == NVCA_MEM_DEVICE && ((uintptr_t)f.data & 15))) vec4 = false;
-            }
+            if (f.mem == NVCA_MEM_HOST) stage_bytes += trk_staged_bytes(t->yuv(), f.stride, W, H);
+            if (!trk_wide_ok(fmt, t->yuv(), f.mem, (uintptr_t)f.data, f.stride, W)) wide = false;
             if (t->num_frames > 0) any_ccl = true;
         }
-        static const int roots_div = [] { const char *e = getenv("NVCA_TRK_ROOTS_DIV"); const int v = e ? atoi(e) : 8; return v >= 1 ? v : 8; }();      // diagnostic: the share of the pixels the root list holds (1 / n)
-        const int roots_cap = (int)std::min<size_t>(N * batch / roots_div, (size_t)1 << 30);
-        const size_t tiles_per_slot = (size_t)((W + 255) / 256) * ((H + 7) / 8), tile_bytes = sizeof(int) * (2 * tiles_per_slot + 2) * (size_t)batch;
-        const void *tiles_before = ws.tiles.p;
-        if (ws.slots.ensure(sizeof(TrkSlot) * batch) || ws.h_slots.ensure(sizeof(TrkSlot) * batch) ||
-            ws.labels.ensure(sizeof(int) * N * batch) || ws.acc.ensure(sizeof(CompAcc) * N * batch) || ws.flags.ensure(tracker_flag_bytes(W, H, batch) + 64) ||
-            ws.out.ensure(sizeof(int) * (2 + 6 * (size_t)kCompCap)) || ws.h_out.ensure(sizeof(int) * (2 + 6 * (size_t)kCompCap)) ||
-            ws.roots.ensure(sizeof(int) * (8 + (size_t)roots_cap + 64)) || ws.tiles.ensure(tile_bytes) ||
-            (stage_bytes && ws.staging.ensure(stage_bytes))) { ctx->set_error("tracker workspace allocation failed"); return NVCA_ERR_NOMEM; }
-        if (ws.tiles.p != tiles_before || ws.tiles_w != W || ws.tiles_h != H || ws.tiles_batch != batch || ws.tick >= 0x7ffffffe) {
-            NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.tiles.p, 0, tile_bytes, ctx->cs()));       // marks of another layout (or of two billion ticks ago) mean nothing
-            ws.tiles_w = W; ws.tiles_h = H; ws.tiles_batch = batch; ws.tick = 0;
-        }
-        const int tick = ++ws.tick;
-        TrkSlot *hs = ws.h_slots.as<TrkSlot>();
-        size_t off = 0;
-        for (int b = 0; b < batch; b++) {
-            nvca_tracker *t = trackers[idx[b]];
-            const nvca_frame &f = frames[idx[b]];
-            TrkSlot &s = hs[b];
-            memset(&s, 0, sizeof(s));
-            if (f.mem == NVCA_MEM_HOST) {
-                uint8_t *d = ws.staging.as<uint8_t>() + off;
-                if (const nvca_pixel_layout *yuv = t->yuv()) {
-                    if (int rc = caller_h2d_planes(ctx, d, f.data, *yuv, W, H, ctx->cs())) return rc;
-                    off += round_up(yuv_extent(*yuv, W, H), 256);
-                } else {
-                    if (int rc = caller_h2d(ctx, d, f.data, (size_t)f.stride * (H - 1) + (size_t)W * 4, ctx->cs())) return rc;
-                    off += ((size_t)f.stride * H + 255) / 256 * 256;
-                }
-                s.src = d;
-            } else s.src = (const uint8_t *)f.data;
-            s.yuv = yuv_planes(t->yuv());
-            s.prev = t->prev.as<uint8_t>(); s.mhi = t->mhi.as<float>();
-            const double timestamp = ts[idx[b]];
-            s.ts = (float)timestamp; s.delbound = (float)(timestamp - t->p.mhi_duration);    // cvUpdateMotionHistory
-            s.seg = (float)t->p.seg_thresh; s.threshold = t->p.threshold;
-            s.has_prev = t->num_frames > 0; s.sstride = f.stride;
-            s.min_area = t->p.min_area; s.max_area = (long long)t->p.max_area;
-        }
-        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ws.slots.p, hs, sizeof(TrkSlot) * batch, hipMemcpyHostToDevice, ctx->cs()));
-        // (the result header and the root list's header are cleared by the pixel kernel; the live-segment counts only steer the per-pixel
-        // kernels' visiting order)
-        if (!ctx->sw.trk_fold) NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.flags.as<uint8_t>() + tracker_count_offset(W, H, batch), 0, sizeof(int) * (size_t)batch, ctx->cs()));
-        const bool fold = ctx->sw.trk_fold;
-        if (fmt != NVCA_PIX_BGR && ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 tracker pass of %d frame(s) %d x %d: %s\n", batch, W, H, vec4 ? "k_trk_pixel_yuv8" : "k_trk_pixel_yuv");
-        { TimedLaunch tl(ctx, NVCA_K_TRACKER);
-          launch_tracker(ctx->cs(), ws.slots.p, batch, W, H, fmt, vec4, ws.labels.as<int>(), ws.acc.p, ws.out.as<int>(), kCompCap, any_ccl, ws.flags.as<uint8_t>(), ctx->sw.trk_order,
-                         ws.roots.as<int>(), roots_cap, fold ? 0 : 1, ws.tiles.as<int>(), tick); }
-        NVCA_LAUNCH_CHECK(ctx);
+        // workspace, slots
+        TrkLaunch L{};
+        L.roots_cap = trk_roots_cap(W, H, batch, tune.roots_div);
+        if (int rc = ensure_workspace(ctx, ws, W, H, batch, L.roots_cap, stage_bytes, &L.tick)) return rc;
+        if (int rc = fill_slots(ctx, ws, trackers, frames, ts, idx, batch, W, H)) return rc;
+        L.slots = ws.slots.as<TrkSlot>(); L.batch = batch; L.w = W; L.h = H; L.fmt = fmt; L.wide = wide;
+        L.labels = ws.labels.as<int>(); L.acc = ws.acc.as<CompAcc>(); L.out = ws.out.as<int>(); L.cap = kCompCap;
+        L.flags = ws.flags.as<uint8_t>(); L.roots = ws.roots.as<int>(); L.tiles = ws.tiles.as<int>();
+        L.order = ctx->sw.trk_order; L.rows = tune.rows; L.rows_uf = tune.rows_uf;
+        // launch (the result header and the root list's header are cleared by the pixel kernel)
+        if (!fold) if (int rc = clear_segment_counts(ctx, ws, W, H, batch)) return rc;
+        if (fmt != NVCA_PIX_BGR && ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 tracker pass of %d frame(s) %d x %d: %s\n", batch, W, H, wide ? "k_trk_pixel_yuv8" : "k_trk_pixel_yuv");
+        if (int rc = launch_route(ctx, L, !any_ccl ? kTrkPixelOnly : fold ? kTrkFolded : kTrkPerPixel)) return rc;
         tp1 = std::chrono::steady_clock::now();
-        int *ho = ws.h_out.as<int>();
+        // read back; fallback
         int total = 0;
         if (any_ccl) {
-            const int first = 1024;
-            NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ho, ws.out.p, sizeof(int) * (2 + 6 * (size_t)first), hipMemcpyDeviceToHost, ctx->cs()));
-            NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
-            auto label_error = [&]() {
-                int dbg[4] = {0, 0, 0, 0};
-                (void)hipMemcpy(dbg, ws.roots.as<int>() + 2, 3 * sizeof(int), hipMemcpyDeviceToHost);
-                ctx->set_error("internal: tracker label walk met an unwritten word (" + std::to_string(dbg[0]) + " times; first at " + std::to_string(dbg[1]) + ", kernel " + std::to_string(dbg[2]) + ")");
-                return NVCA_ERR_INTERNAL;
-            };
-            if (ho[1] & 2) return label_error();
-            if (fold && (ho[1] & 1)) {
+            bool roots_overflowed = false;
+            if (int rc = read_components(ctx, ws, &total, fold ? &roots_overflowed : nullptr)) return rc;
+            if (roots_overflowed) {
                 // more tile roots than the list holds (a frame of single-pixel components): the same motion history through the per-pixel kernels
-                NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.out.p, 0, 2 * sizeof(int), ctx->cs()));
-                NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.flags.as<uint8_t>() + tracker_count_offset(W, H, batch), 0, sizeof(int) * (size_t)batch, ctx->cs()));
-                { TimedLaunch tl(ctx, NVCA_K_TRACKER);
-                  launch_tracker(ctx->cs(), ws.slots.p, batch, W, H, fmt, vec4, ws.labels.as<int>(), ws.acc.p, ws.out.as<int>(), kCompCap, true, ws.flags.as<uint8_t>(), ctx->sw.trk_order,
-                                 ws.roots.as<int>(), roots_cap, 2, ws.tiles.as<int>(), tick); }
-                NVCA_LAUNCH_CHECK(ctx);
-                NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ho, ws.out.p, sizeof(int) * (2 + 6 * (size_t)first), hipMemcpyDeviceToHost, ctx->cs()));
-                NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
-                if (ho[1] & 2) return label_error();
-            }
-            total = ho[0];
-            if (total < 0) { ctx->set_error("internal: negative component count"); return NVCA_ERR_INTERNAL; }
-            if (total > kCompCap) { ctx->set_error("tracker: more motion components than the list holds"); return NVCA_ERR_OVERFLOW; }
-            if (total > first) {
-                NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ho + 2 + 6 * (size_t)first, ws.out.as<int>() + 2 + 6 * (size_t)first,
-                                                   sizeof(int) * 6 * (size_t)(total - first), hipMemcpyDeviceToHost, ctx->cs()));
-                NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
+                NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.out.p, 0, kCompHdr * sizeof(int), ctx->cs()));
+                if (int rc = clear_segment_counts(ctx, ws, W, H, batch)) return rc;
+                if (int rc = launch_route(ctx, L, kTrkPerPixelAlone)) return rc;
+                if (int rc = read_components(ctx, ws, &total, nullptr)) return rc;
             }
         } else
             NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
         tp2 = std::chrono::steady_clock::now(); total_comps += total;
-        // seed order (raster order of each component's first seed pixel) = cvSegmentMotion's output order
-        std::vector<std::vector<std::pair<int, nvca_rect>>> comps(batch);
-        for (int k = 0; k < total; k++) {
-            const int *o = ho + 2 + (size_t)k * 6;
-            if (o[0] < 0 || o[0] >= batch) { ctx->set_error("internal: motion component of an unknown slot (device result rejected)"); return NVCA_ERR_INTERNAL; }
-            comps[o[0]].push_back({o[1], nvca_rect{o[2], o[3], o[4], o[5]}});
-        }
+        // host logic
+        std::string err;
+        if (int rc = trk_component_lists(ws.h_out.as<int>(), total, batch, comps, err)) { ctx->set_error(err); return rc; }
         for (int b = 0; b < batch; b++) {
             nvca_tracker *t = trackers[idx[b]];
             if (t->num_frames > 0) {
-                auto &c = comps[b];
-                std::sort(c.begin(), c.end(), [](const std::pair<int, nvca_rect> &x, const std::pair<int, nvca_rect> &y) { return x.first < y.first; });
-                std::vector<nvca_rect> sb;
-                sb.reserve(c.size());
-                for (auto &e : c) sb.push_back(e.second);
+                std::vector<nvca_rect> &sb = comps[b];
                 join_objects(sb, t->p.min_area, t->p.max_area, t->p.distance);      // __join_objects :380
                 n_out[idx[b]] = (int)sb.size();
                 for (int k = 0; k < std::min<int>(cap, (int)sb.size()); k++) out[(size_t)idx[b] * cap + k] = sb[k];

@@ -1,5 +1,5 @@
 // yuv_device.h -- device-only arithmetic of the 4:2:0 sources, shared by every kernel that reads NV12 / I420 planes
-// (kernels_gray.hip: face streams, the part detectors' working images, nvca_yuv420_to_bgr; kernels_tracker.hip: the pixel pass):
+// (kernels_gray.hip: face streams, the part detectors' working images, nvca_yuv420_to_bgr; kernels_trk_pixel.hip: the tracker's pixel pass):
 // cv::cvtColor(CV_YUV2BGR_NV12 / _I420) as OpenCV 2.4 color.cpp computes it, BT.601 limited range, shift 20 -- pixel
 // (x, y) takes the chroma sample (x >> 1, y >> 1); all int32, the shift arithmetic -- and the BGR2GRAY / BGRA2GRAY that follows it.
 #pragma once

@@ -1,4 +1,4 @@
-"""The tracker's component kernels (csrc/kernels_tracker.hip) on motion histories built by construction (tests/motion_layouts.py; that
+"""The tracker's component kernels (csrc/kernels_trk_ccl.hip behind the pixel pass of csrc/kernels_trk_pixel.hip) on motion histories built by construction (tests/motion_layouts.py; that
 every layout is in the regime it is named for is checked on the host, tests/test_motion_layouts_cpu.py).
 
 Everything goes through the C ABI and is compared with np.array_equal, in order, frame by frame, against the oracle tracker:
