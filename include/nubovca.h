@@ -162,8 +162,8 @@ const char *nvca_kernel_name(int k);
  *  - new format ("opencv-cascade-classifier", what opencv_traincascade writes and OpenCV's lbpcascades/ hold): featureType LBP
  *    with stump weak classifiers.  New-format HAAR and HOG cascades, stage types other than BOOST, trees
  *    (maxDepth > 1) and maxCatCount != 256 are refused with NVCA_ERR_UNSUPPORTED.
- * An LBP cascade goes through nvca_detect_multiscale / nvca_detect_raw on single images; the face and part streams refuse it
- * (NVCA_ERR_UNSUPPORTED).  Its launches are booked under the existing timing slots: the evaluator's kernels under NVCA_K_STRIP
+ * An LBP cascade goes through nvca_detect_multiscale / nvca_detect_raw on single images and through their _batch forms on
+ * several; the face and part streams refuse it (NVCA_ERR_UNSUPPORTED).  Its launches are booked under the existing timing slots: the evaluator's kernels under NVCA_K_STRIP
  * ("window per lane"), the level resize and integral under NVCA_K_RESIZE1 / NVCA_K_INTEGRAL as CV_HAAR_SCALE_IMAGE books them. */
 #define NVCA_CASCADE_HAAR 0
 #define NVCA_CASCADE_LBP  1
@@ -300,6 +300,22 @@ int nvca_detect_multiscale(nvca_ctx *ctx, const nvca_cascade *cascade, const voi
 int nvca_detect_raw(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray, int w, int h,
                     int stride, int mem, double scale_factor, int flags, int min_w, int min_h,
                     int max_w, int max_h, nvca_rect *out, int cap, int *n_out);
+/* nvca_detect_multiscale on n images of ONE geometry (w, h, stride) and one memory kind, behind one wait per round of launch sets:
+ * gray[i] is image i, its objects go to out[(size_t)i * cap + k] (the convention of nvca_face_batch_process), n_out[i] is its
+ * full count and may exceed cap.  Image i's answer is exactly what nvca_detect_multiscale returns for it, for every cascade
+ * format and every flags value that call accepts.  The images share their launch sets in groups of up to 32 (an LBP cascade's
+ * evaluator and the pyramids carry an image axis; a FIND_BIGGEST_OBJECT search runs per image), so the number of launches, and
+ * the waits, are per group and not per image.  Device images at equal distances in one allocation are read where they are,
+ * others are copied first.  n == 0 is NVCA_OK.  NVCA_ERR_ARG: n < 0, gray or one of its entries NULL, cap < 0, cap > 0 without
+ * out, n_out NULL, scale_factor <= 1.  Any failure fails the whole call: out and n_out are then unspecified. */
+int nvca_detect_multiscale_batch(nvca_ctx *ctx, const nvca_cascade *cascade, int n, const void *const *gray,
+                                 int w, int h, int stride, int mem, double scale_factor, int min_neighbors, int flags,
+                                 int min_w, int min_h, int max_w, int max_h, nvca_rect *out, int cap, int *n_out);
+/* nvca_detect_raw on n images, laid out and refused as above; FIND_BIGGEST_OBJECT on a Haar cascade is NVCA_ERR_ARG as for
+ * the single call */
+int nvca_detect_raw_batch(nvca_ctx *ctx, const nvca_cascade *cascade, int n, const void *const *gray,
+                          int w, int h, int stride, int mem, double scale_factor, int flags,
+                          int min_w, int min_h, int max_w, int max_h, nvca_rect *out, int cap, int *n_out);
 /* cv::groupRectangles(rects, groupThreshold, eps) on the device; in place */
 int nvca_group_rectangles(nvca_ctx *ctx, nvca_rect *rects, int n, int group_threshold, double eps,
                           int *n_out);

@@ -205,7 +205,7 @@ int detect_jobs_finish(nvca_ctx *ctx, DetectJob *const *jobs, int n, const int *
 DetectJob *detect_job_new();
 void detect_job_free(DetectJob *j);
 const std::vector<nvca_rect> &detect_job_out(const DetectJob *j, int k);
-constexpr int kJobImages = 32;                                    // images of one geometry that a plain / SCALE_IMAGE job can carry
+constexpr int kJobImages = 32;                                    // images of one geometry that a plain / SCALE_IMAGE / LBP job can carry
 int detect_job_add_image(DetectJob *j, const void *image);       // one more image for the job's launch set; returns its index k (detect_job_out), -1: full / not possible
 
 } // namespace nvca

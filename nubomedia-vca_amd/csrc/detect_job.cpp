@@ -247,7 +247,7 @@ void nvca::detect_job_free(DetectJob *j) { delete j; }
 const std::vector<nvca_rect> &nvca::detect_job_out(const DetectJob *j, int k) { return j->out[k]; }
 int nvca::detect_job_add_image(DetectJob *j, const void *image)
 {
-    if (j->rq.kind == kJobBiggest || j->rq.kind == kJobLbp || j->q.phase != kJobNew || j->rq.nimg >= kJobImages) return -1;
+    if (j->rq.kind == kJobBiggest || j->q.phase != kJobNew || j->rq.nimg >= kJobImages) return -1;
     j->rq.img[j->rq.nimg] = image;
     return j->rq.nimg++;
 }

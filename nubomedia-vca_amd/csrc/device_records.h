@@ -241,20 +241,22 @@ static constexpr int kLbpTileW = 32, kLbpTileH = 16;
 NVCA_HD inline int lbp_tile_pitch(int ow) { return (kLbpTileW - 1) * 2 + ow + 1; }
 NVCA_HD inline int lbp_tile_rows(int oh, int step) { return (kLbpTileH - 1) * step + oh + 1; }
 struct LbpArgs {
-    const int *sum;                 // the levels' sum planes (one image)
+    const int *sum;                 // the levels' sum planes; image b's at sum + b * plane_total
+    int nimg;                       // images of the job: they share every launch and every table
+    size_t plane_total, bit_words;  // elements between two images' planes / u32 words between their pass bits
     int P, TP;                      // pitch of the planes / of the LDS tile (elements)
     int ow, oh;
     const LbpLevelDev *levels; int nlev;
     const LbpStageDev *stages; int nstages;
     const LbpWeakDev *gweak, *tweak;        // offsets at pitch P / at pitch TP
     const LbpTile *tiles; int ntiles;
-    unsigned *bits, *bits2;         // per grid position of every level: passed stage 0 / passed the tile kernel's stages
+    unsigned *bits, *bits2;         // per grid position of every level: passed stage 0 / passed the tile kernel's stages; image b's at + b * bit_words
     int tile_stages;                // stages the tile kernel evaluates (the first min(nstages, 3))
-    int nrows;                      // scan rows of all levels
+    int nrows;                      // scan rows of all levels (of one image)
     int key_sy, key_ss;             // candidate key = level << key_ss | gy << key_sy | gx
     unsigned *cnt;                  // [0]: entries of the list the walk kernel fills, [g]: of the list stage group g leaves
-    unsigned *list[2]; unsigned list_cap;     // survivor keys, ping-pong between stage groups
-    unsigned long long *hits; unsigned hit_cap;       // hits[0] = exact count, hits[1 .. cap] = key (slot 0)
+    unsigned long long *list[2]; unsigned list_cap;   // survivors of ALL images as img << 32 | key, ping-pong between stage groups
+    unsigned long long *hits; unsigned hit_cap;       // hits[0] = exact count, hits[1 .. cap] = img << 32 | key (the job's one list)
 };
 
 // ---- detectMultiScale on a small image in one workgroup (kernels_roi.hip)

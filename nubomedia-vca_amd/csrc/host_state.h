@@ -169,7 +169,7 @@ struct DetectJob {
     struct Request {
         JobKind kind = kJobPlain;
         const nvca_cascade *casc = nullptr;
-        const void *img[kJobImages] = {nullptr}; int nimg = 1;       // plain scan / SCALE_IMAGE: images of one geometry share the launches
+        const void *img[kJobImages] = {nullptr}; int nimg = 1;       // plain scan / SCALE_IMAGE / LBP: images of one geometry share the launches
         int cols = 0, rows = 0, stride = 0, mem = 0;
         double sf = 1.1; int min_neighbors = 0, flags = 0, minw = 0, minh = 0, maxw = 0, maxh = 0;
         bool raw_only = false;

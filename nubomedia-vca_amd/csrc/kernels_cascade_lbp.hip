@@ -5,11 +5,16 @@
 //   k_lbp_stage0   the first stages (LbpArgs::tile_stages, at most 3) at EVERY grid position of every level, 32 x 16 positions per
 //                  workgroup, corners read from a tile of the level's sum plane staged in LDS; leaves two bits per position: passed
 //                  stage 0 (what the skip rule depends on), passed all of the tile's stages
-//   k_lbp_walk     a thread per scan row replays the serial walk's skip rule on the stage-0 bits (a stage-0 reject skips the next grid
+//   k_lbp_walk     a thread per scan row (of every image) replays the serial walk's skip rule on the stage-0 bits (a stage-0 reject skips the next grid
 //                  column: visited[i] = visited[i-1] & pass[i-1] | visited[i-2] & !pass[i-2]) and lists the VISITED survivors of the
 //                  tile's stages -- a skipped column may have been evaluated there, it is never listed and so never emitted
 //   k_lbp_rest     stages [s0, s1) on a list of survivors, corners gathered from the plane; the survivors are compacted into the next
 //                  list (the host launches one per stage group), the last group appends to the candidate list
+//
+// A job's images (LbpArgs::nimg, one geometry) share every launch: stage 0 has the image in grid.y, the walk a lane per (image, scan
+// row), and from there on ONE survivor list holds every image's windows as img << 32 | key -- a stage group runs once on all of them,
+// so its launch count does not depend on the number of images and its late, thin groups see nimg times the windows.  Image b's sum
+// planes lie at sum + b * plane_total, its pass bits at bits + b * bit_words.
 //
 // The subset word of a vote is picked per lane by code >> 5 from eight words held in scalar registers: with seven compares and
 // selects -- indexing scalar registers by a vector value would make the compiler wrap the read in a waterfall loop, and an LDS copy
@@ -59,13 +64,14 @@ __global__ __launch_bounds__(kLbpTileW * kLbpTileH) void k_lbp_stage0(LbpArgs a)
 {
     extern __shared__ int lbp_tile[];
     const LbpTile t = a.tiles[blockIdx.x];
-    if ((unsigned)t.level >= (unsigned)a.nlev) return;
+    const unsigned img = blockIdx.y;          // (the grid is ntiles x nimg; tiles, levels and weak classifiers are every image's)
+    if ((unsigned)t.level >= (unsigned)a.nlev || img >= (unsigned)a.nimg) return;
     const LbpLevelDev L = a.levels[t.level];
     const int tid = threadIdx.x, lx = tid & (kLbpTileW - 1), ly = tid / kLbpTileW;
     const int gx = t.tx * kLbpTileW + lx, gy = t.ty * kLbpTileH + ly;
     const int X0 = t.tx * kLbpTileW * L.step, Y0 = t.ty * kLbpTileH * L.step;
     const bool active = gx < L.nx && gy < L.ny;
-    const int *__restrict__ plane = a.sum + L.plane_off;
+    const int *__restrict__ plane = a.sum + (size_t)img * a.plane_total + L.plane_off;
     const int *p;
     const LbpWeakDev *weak;
     if (LDS) {
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(kLbpTileW * kLbpTileH) void k_lbp_stage0(LbpArgs a)
     // lanes 0 .. 31: row gy of the even lane rows, 32 .. 63: the row below
     const unsigned long long m0 = __ballot(pass0), m1 = __ballot(alive);
     if (lx == 0 && gy < L.ny) {
-        const size_t w = L.bit_off + (size_t)gy * L.wpr + t.tx;
+        const size_t w = (size_t)img * a.bit_words + L.bit_off + (size_t)gy * L.wpr + t.tx;
         a.bits[w] = (unsigned)(m0 >> (tid & 32));
         a.bits2[w] = (unsigned)(m1 >> (tid & 32));
     }
@@ -111,19 +117,26 @@ __global__ __launch_bounds__(64) void k_lbp_walk(LbpArgs a)
         lut[e] = (unsigned short)(vis | (skip ? 256u : 0u));
     }
     __syncthreads();
-    // a lane per row; the lanes of the wave step through their rows' words together, so that the wave appends what its 64 rows
-    // found in a word with ONE atomic (a lane whose row has ended, or that has no row, takes part with nothing)
-    const int row = blockIdx.x * 64 + threadIdx.x, lane = threadIdx.x;
-    int lv = 0, gy = -1, wpr = 0;
+    // a lane per (image, row) -- image-major, so a wave may span two images; the lanes of the wave step through their rows' words
+    // together, so that the wave appends what its 64 rows found in a word with ONE atomic (a lane whose row has ended, or that has
+    // no row, takes part with nothing)
+    const int pair = blockIdx.x * 64 + threadIdx.x, lane = threadIdx.x;
+    int lv = 0, gy = -1, wpr = 0, img = 0;
     const unsigned *rb = nullptr, *rb2 = nullptr;
-    if (row < a.nrows) {
+    if (pair < a.nrows * a.nimg) {
+        img = pair / a.nrows;
+        const int row = pair - img * a.nrows;
         while (lv + 1 < a.nlev && row >= a.levels[lv + 1].row_first) lv++;
         const LbpLevelDev &L = a.levels[lv];
         gy = row - L.row_first;
-        if (gy >= 0 && gy < L.ny) { wpr = L.wpr; rb = a.bits + L.bit_off + (size_t)gy * L.wpr; rb2 = a.bits2 + L.bit_off + (size_t)gy * L.wpr; }
+        if (gy >= 0 && gy < L.ny) {
+            const size_t w = (size_t)img * a.bit_words + L.bit_off + (size_t)gy * L.wpr;
+            wpr = L.wpr; rb = a.bits + w; rb2 = a.bits2 + w;
+        }
     }
+    const unsigned long long slot = (unsigned long long)(unsigned)img << 32;
     const bool final = a.nstages <= a.tile_stages;
-    unsigned state = 0;                  // 256: the next column is jumped over (the one before it was visited and failed stage 0)
+    unsigned state = 0;                  // 256: the next column is jumped over (the one before it was visited and failed stage 0); every row of every image starts at 0
     for (int k = 0; __ballot(k < wpr); k++) {
         unsigned surv = 0;
         if (k < wpr) {
@@ -145,8 +158,8 @@ __global__ __launch_bounds__(64) void k_lbp_walk(LbpArgs a)
         base = __shfl(base, 0) + (unsigned long long)(incl - n);
         for (int i = 0; surv; i++, surv &= surv - 1) {
             const unsigned key = ((unsigned)lv << a.key_ss) | ((unsigned)gy << a.key_sy) | (unsigned)(k * 32 + __ffs(surv) - 1);
-            if (final) { if (base + i < a.hit_cap) a.hits[1 + base + i] = key; }
-            else if (base + i < a.list_cap) a.list[0][base + i] = key;
+            if (final) { if (base + i < a.hit_cap) a.hits[1 + base + i] = slot | key; }
+            else if (base + i < a.list_cap) a.list[0][base + i] = slot | key;
         }
     }
 }
@@ -155,23 +168,24 @@ __global__ __launch_bounds__(256) void k_lbp_rest(LbpArgs a, int s0, int s1, int
 {
     unsigned n = a.cnt[in_cnt];
     if (n > a.list_cap) n = a.list_cap;
-    const unsigned *__restrict__ src = in ? a.list[1] : a.list[0];
-    unsigned *__restrict__ dst = in ? a.list[0] : a.list[1];
+    const unsigned long long *__restrict__ src = in ? a.list[1] : a.list[0];
+    unsigned long long *__restrict__ dst = in ? a.list[0] : a.list[1];
     const bool final = s1 >= a.nstages;
     const int lane = threadIdx.x & 63;
     for (unsigned i0 = blockIdx.x * 256u; i0 < n; i0 += gridDim.x * 256u) {          // (uniform per workgroup: the ballots below see whole waves)
         const unsigned i = i0 + threadIdx.x;
         bool alive = i < n;
-        unsigned key = 0; size_t off = 0;
+        unsigned long long e = 0; size_t off = 0;
         if (alive) {
-            // a key comes from device memory: it is checked against the grids before it indexes the planes
-            key = src[i];
+            // an entry comes from device memory: its image and its key are checked against the job and the grids before they index the planes
+            e = src[i];
+            const unsigned img = (unsigned)(e >> 32), key = (unsigned)e;
             const unsigned lv = key >> a.key_ss, gy = (key >> a.key_sy) & ((1u << (a.key_ss - a.key_sy)) - 1u), gx = key & ((1u << a.key_sy) - 1u);
-            alive = lv < (unsigned)a.nlev;
+            alive = img < (unsigned)a.nimg && lv < (unsigned)a.nlev;
             if (alive) {
                 const LbpLevelDev &L = a.levels[lv];
                 alive = gx < (unsigned)L.nx && gy < (unsigned)L.ny;
-                if (alive) off = (size_t)L.plane_off + (size_t)(gy * L.step) * a.P + gx * L.step;
+                if (alive) off = (size_t)img * a.plane_total + (size_t)L.plane_off + (size_t)(gy * L.step) * a.P + gx * L.step;
             }
         }
         for (int s = s0; s < s1 && s < a.nstages; s++) {
@@ -185,27 +199,28 @@ __global__ __launch_bounds__(256) void k_lbp_rest(LbpArgs a, int s0, int s1, int
             unsigned long long base = 0;
             if (lane == 0) base = atomicAdd(a.hits, (unsigned long long)cntm);
             base = __shfl(base, 0);
-            if (alive && base + rank < a.hit_cap) a.hits[1 + base + rank] = key;
+            if (alive && base + rank < a.hit_cap) a.hits[1 + base + rank] = e;
         } else {
             unsigned base = 0;
             if (lane == 0) base = atomicAdd(a.cnt + in_cnt + 1, (unsigned)cntm);
             base = __shfl(base, 0);
-            if (alive && base + rank < a.list_cap) dst[base + rank] = key;
+            if (alive && base + rank < a.list_cap) dst[base + rank] = e;
         }
     }
 }
 
 void launch_lbp_stage0(hipStream_t st, const LbpArgs &a, int lds)
 {
-    if (a.ntiles <= 0) return;
-    if (lds > 0) NVCA_LAUNCH(k_lbp_stage0<true>, dim3((unsigned)a.ntiles), dim3(kLbpTileW * kLbpTileH), (size_t)lds, st, a);
-    else NVCA_LAUNCH(k_lbp_stage0<false>, dim3((unsigned)a.ntiles), dim3(kLbpTileW * kLbpTileH), 0, st, a);
+    if (a.ntiles <= 0 || a.nimg <= 0) return;
+    const dim3 grid((unsigned)a.ntiles, (unsigned)a.nimg);
+    if (lds > 0) NVCA_LAUNCH(k_lbp_stage0<true>, grid, dim3(kLbpTileW * kLbpTileH), (size_t)lds, st, a);
+    else NVCA_LAUNCH(k_lbp_stage0<false>, grid, dim3(kLbpTileW * kLbpTileH), 0, st, a);
 }
 
 void launch_lbp_walk(hipStream_t st, const LbpArgs &a)
 {
-    if (a.nrows <= 0) return;
-    NVCA_LAUNCH(k_lbp_walk, dim3((unsigned)(a.nrows + 63) / 64), dim3(64), 0, st, a);
+    if (a.nrows <= 0 || a.nimg <= 0) return;
+    NVCA_LAUNCH(k_lbp_walk, dim3((unsigned)(a.nrows * a.nimg + 63) / 64), dim3(64), 0, st, a);
 }
 
 void launch_lbp_rest(hipStream_t st, const LbpArgs &a, int s0, int s1, int in, int in_cnt, unsigned max_items)

@@ -110,6 +110,7 @@ void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, in
 // ---- new-format LBP cascades (kernels_cascade_lbp.hip): stage 0 of every grid position (pass bits), the serial walk's skip rule
 // per row + compaction of the visited survivors, then stages [s0, s1) on the survivors of list `in` (count cnt[in_cnt]) -- into the
 // other list and cnt[in_cnt + 1], or, when s1 is the last stage, into the candidate list.  lds: stage-0 tile bytes (0: gather from global)
+// All three serve the a.nimg images of a job in one launch: grid.y, a lane per (image, row), one survivor list for all images.
 void launch_lbp_stage0(hipStream_t st, const LbpArgs &a, int lds);
 void launch_lbp_walk(hipStream_t st, const LbpArgs &a);
 void launch_lbp_rest(hipStream_t st, const LbpArgs &a, int s0, int s1, int in, int in_cnt, unsigned max_items);

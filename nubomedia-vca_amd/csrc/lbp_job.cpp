@@ -64,26 +64,31 @@ int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
     // (the pyramid launchers write the squared integral with the sum: it is computed and ignored here)
     if ((rc = pyr_build(ctx, j, pp, false))) return rc;
     const LbpPlan &lp = pp->lbp;
-    const int tot = std::max(total, r0 + 1);
+    // The job's images share every launch.  Pass bits per image; the two survivor lists are the whole job's, and either holds every
+    // grid position of every image: a list that could be too short would drop windows, so it is never sized by an estimate.
+    const int nimg = j.rq.nimg;
+    const size_t entries = lp.positions * (size_t)nimg;
+    if (entries > 0xffffffffull) { ctx->set_error("LBP scan: more grid positions in one job than its list counters count"); return NVCA_ERR_ARG; }
+    const int tot = std::max(total, r0 + nimg);
     const size_t hits_stride = (size_t)ctx->hit_cap + 1;
-    constexpr size_t kCnt = 64;                       // list counters in front of the first list
-    if (ws.ln().failbits.ensure(2 * lp.bit_words * sizeof(unsigned) + 8) || ws.ln().deep.ensure((kCnt + lp.positions) * sizeof(unsigned)) ||
-        ws.ln().vnf.ensure(lp.positions * sizeof(unsigned) + 8) ||
+    constexpr size_t kCnt = 64;                       // list counters in front of the first list (kCnt u32 words: the list behind them stays 8-byte aligned)
+    if (ws.ln().failbits.ensure(2 * lp.bit_words * nimg * sizeof(unsigned) + 8) || ws.ln().deep.ensure(kCnt * sizeof(unsigned) + entries * sizeof(unsigned long long)) ||
+        ws.ln().vnf.ensure(entries * sizeof(unsigned long long) + 8) ||
         rb.hits.ensure(hits_stride * tot * sizeof(unsigned long long)) || rb.h_hits.ensure(hits_stride * tot * sizeof(unsigned long long))) {
         ctx->set_error("device allocation failed for the cascade workspace"); return NVCA_ERR_NOMEM;
     }
     CascadeJob &cj = j.q.cj;
-    cj = CascadeJob(); cj.r0 = r0; cj.n = 1; cj.total = total;
-    cj.cap = (unsigned)ctx->hit_cap;
+    cj = CascadeJob(); cj.r0 = r0; cj.n = nimg; cj.total = total;
+    cj.cap = (unsigned)ctx->hit_cap * (unsigned)nimg;         // one list for all the job's slots, as cascade_enqueue's
     cj.d_hits = rb.hits.as<unsigned long long>() + hits_stride * r0;
     cj.h_hits = rb.h_hits.as<unsigned long long>() + hits_stride * r0;
     NVCA_HIP_CHECK(ctx, hipMemsetAsync(cj.d_hits, 0, sizeof(unsigned long long), ctx->cs()));
     NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.ln().deep.p, 0, kCnt * sizeof(unsigned), ctx->cs()));
     LbpArgs a = lp.args;
-    a.sum = ws.ln().sum.as<int>();
-    a.bits = ws.ln().failbits.as<unsigned>(); a.bits2 = a.bits + lp.bit_words;
+    a.sum = ws.ln().sum.as<int>(); a.nimg = nimg; a.plane_total = pp->plane_total; a.bit_words = lp.bit_words;
+    a.bits = ws.ln().failbits.as<unsigned>(); a.bits2 = a.bits + lp.bit_words * nimg;
     a.cnt = ws.ln().deep.as<unsigned>();
-    a.list[0] = ws.ln().deep.as<unsigned>() + kCnt; a.list[1] = ws.ln().vnf.as<unsigned>(); a.list_cap = (unsigned)lp.positions;
+    a.list[0] = (unsigned long long *)(ws.ln().deep.as<unsigned>() + kCnt); a.list[1] = ws.ln().vnf.as<unsigned long long>(); a.list_cap = (unsigned)entries;
     a.hits = cj.d_hits; a.hit_cap = cj.cap;
     {   // the first stages everywhere, the serial walk's skip rule, then the later stages group by group on ever shorter survivor
         // lists (groups of 2, 3, 4 ... stages: survivors thin out by about half per stage).  All booked as "window per lane".
@@ -94,7 +99,7 @@ int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
         for (int s0 = a.tile_stages, len = 2; s0 < a.nstages && g + 1 < (int)kCnt; s0 += len, len++, g++) {
             // (the last group takes every stage that is left: the counters bound the number of groups)
             const int s1 = g + 2 == (int)kCnt ? a.nstages : std::min(a.nstages, s0 + len);
-            launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)lp.positions);
+            launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)entries);
             if (s1 >= a.nstages) break;
         }
     }

@@ -88,6 +88,7 @@ SYMBOLS = [
     "nvca_ctx_kernel_timing", "nvca_kernel_name", "nvca_cascade_load_xml", "nvca_cascade_load_mem",
     "nvca_cascade_free", "nvca_cascade_info", "nvca_cascade_dump", "nvca_bgr2gray", "nvca_resize_linear",
     "nvca_equalize_hist", "nvca_integral", "nvca_detect_multiscale", "nvca_detect_raw", "nvca_group_rectangles",
+    "nvca_detect_multiscale_batch", "nvca_detect_raw_batch",
     "nvca_face_params_default", "nvca_face_stream_create", "nvca_face_stream_destroy",
     "nvca_face_stream_set_params", "nvca_face_stream_motion_event", "nvca_face_stream_process",
     "nvca_face_batch_process", "nvca_tracker_params_default", "nvca_tracker_create", "nvca_tracker_destroy",
@@ -176,6 +177,10 @@ def load():
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
     L.nvca_detect_raw.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
+    L.nvca_detect_multiscale_batch.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
+    L.nvca_detect_raw_batch.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
     L.nvca_group_rectangles.argtypes = [vp, C.POINTER(Rect), C.c_int, C.c_int, C.c_double, ip]
     L.nvca_face_params_default.argtypes = [C.POINTER(FaceParams)]
     L.nvca_face_params_default.restype = None
@@ -409,6 +414,35 @@ class Context:
         self.check(self.L.nvca_detect_raw(self.h, casc.h, gray.ctypes.data, w, h, gray.strides[0], MEM_HOST, scale_factor,
                                           flags, min_size[0], min_size[1], max_size[0], max_size[1], buf, cap, C.byref(n)))
         return _rects(buf, min(n.value, cap))
+
+    def _detect_batch(self, call, grays, cap):
+        """the images of a batch call (host arrays of one shape and row stride) and its answer as a list of (k, 4) arrays"""
+        grays = [np.ascontiguousarray(g, np.uint8) for g in grays]
+        n = len(grays)
+        if n == 0:
+            return []
+        h, w = grays[0].shape
+        if any(g.shape != (h, w) for g in grays):
+            raise ValueError("the images of a batch share one geometry")
+        ptrs = (C.c_void_p * n)(*[g.ctypes.data for g in grays])
+        buf = (Rect * (cap * n))()
+        cnt = (C.c_int * n)()
+        self.check(call(ptrs, w, h, grays[0].strides[0], buf, cnt))
+        flat = np.frombuffer(buf, np.int32).reshape(n, cap, 4)
+        return [flat[i, :min(cnt[i], cap)].copy() for i in range(n)]
+
+    def detect_multiscale_batch(self, casc, grays, scale_factor=1.1, min_neighbors=3, flags=0, min_size=(0, 0),
+                                max_size=(0, 0), cap=4096):
+        """nvca_detect_multiscale_batch on a list of host images of one shape: a list of (k, 4) arrays"""
+        return self._detect_batch(lambda ptrs, w, h, stride, buf, cnt: self.L.nvca_detect_multiscale_batch(
+            self.h, casc.h, len(ptrs), ptrs, w, h, stride, MEM_HOST, scale_factor, min_neighbors, flags, min_size[0], min_size[1],
+            max_size[0], max_size[1], buf, cap, cnt), grays, cap)
+
+    def detect_raw_batch(self, casc, grays, scale_factor=1.1, flags=0, min_size=(0, 0), max_size=(0, 0), cap=1 << 16):
+        """nvca_detect_raw_batch on a list of host images of one shape: a list of (k, 4) arrays"""
+        return self._detect_batch(lambda ptrs, w, h, stride, buf, cnt: self.L.nvca_detect_raw_batch(
+            self.h, casc.h, len(ptrs), ptrs, w, h, stride, MEM_HOST, scale_factor, flags, min_size[0], min_size[1],
+            max_size[0], max_size[1], buf, cap, cnt), grays, cap)
 
     def group_rectangles(self, rects, group_threshold, eps=0.2):
         rects = np.asarray(rects, np.int32).reshape(-1, 4)

@@ -11,6 +11,13 @@ survivors); for Haar by the oracle's statistics (stumps evaluated by the serial 
 --repeats groups of --calls calls; median and spread over the groups.
 
     python scripts/bench_lbp.py [--repeats 7] [--calls 10] > profiles/r07/lbp.txt
+
+--batch N[,N...]: instead of the above, nvca_detect_multiscale_batch on N images -- the same cascade, the same 1080p image and seeded
+siblings of it, equally spaced in one HBM allocation -- beside a loop of N nvca_detect_multiscale calls on the same images in the same
+run.  Per image: host clock around the call (the loop), the evaluator's and the pyramid kernels' times; per call: the timing scopes
+booked.  A library without the batch entry points runs the loops alone (the figure of a parent commit).
+
+    python scripts/bench_lbp.py --batch 1,8,32 > profiles/r08/lbp_batch.txt
 """
 import argparse
 import ctypes as C
@@ -87,11 +94,86 @@ def lbp_work(ref, gray, sf):
     return nlev, positions, visited, pairs, raw
 
 
+PYRAMID = ("resize_gray", "integral_rows", "integral_colsum", "integral_bandscan")
+
+
+def bench_batches(args, sizes):
+    import torch
+    from nubovca import capi, synth
+    torch.cuda.set_device(0)
+    ctx = capi.Context(0)
+    nmax = max(sizes)
+    faces = [(300, 200, 2.0), (1200, 500, 4.0), (800, 100, 1.0)]
+    grays = np.stack([synth.paste_lbp_faces(synth.make_gray(W, H, synth.frame_seed(0, 1 + i), "natural"), faces, 24, 24) for i in range(nmax)])
+    dev = torch.from_numpy(grays).cuda()
+    torch.cuda.synchronize()
+    calib = [synth.make_gray(W // 2, H // 2, synth.frame_seed(7, 9100 + i), "natural") for i in range(4)]
+    lbp = ctx.load_cascade_xml(synth.lbp_cascade_xml(ow=24, oh=24, seed=4, stage_sizes=STAGES, pass_rate=0.5, calibrate_on=calib))
+    have_batch = hasattr(capi.Context, "detect_multiscale_batch")
+    cap = 1 << 12
+    buf, cnt = (capi.Rect * (cap * nmax))(), (C.c_int * nmax)()
+    ptrs = (C.c_void_p * nmax)(*[dev.data_ptr() + i * W * H for i in range(nmax)])
+
+    def batch(n):
+        ctx.check(ctx.L.nvca_detect_multiscale_batch(ctx.h, lbp.h, n, ptrs, W, H, W, capi.MEM_DEVICE, SF, MN, 0, 0, 0, 0, 0, buf, cap, cnt))
+        return [cnt[i] for i in range(n)]
+
+    def loop(n):
+        out = []
+        for i in range(n):
+            ctx.check(ctx.L.nvca_detect_multiscale(ctx.h, lbp.h, ptrs[i], W, H, W, capi.MEM_DEVICE, SF, MN, 0, 0, 0, 0, 0, buf, cap, cnt))
+            out.append(cnt[0])
+        return out
+
+    def measure(fn, n):
+        rounds = max(2, -(-args.calls // n))
+        for _ in range(3):
+            boxes = fn(n)
+        wall, kern = [], []
+        for _ in range(args.repeats):
+            ctx.enable_kernel_timing(1)
+            t0 = time.perf_counter()
+            for _ in range(rounds):
+                fn(n)
+            wall.append((time.perf_counter() - t0) / (rounds * n) * 1e3)
+            kern.append({k: (ms / (rounds * n), c // rounds) for k, (ms, c) in ctx.kernel_timing().items()})
+            ctx.enable_kernel_timing(0)
+        return boxes, wall, kern, rounds
+
+    def report(title, n, boxes, wall, kern, rounds):
+        print("## %s" % title)
+        print("grouped boxes %s; per IMAGE (host clock, timing events on): median %.3f ms, min %.3f, max %.3f over %d groups of %d rounds of %d images"
+              % (boxes if n <= 8 else "%s ..." % boxes[:8], statistics.median(wall), min(wall), max(wall), args.repeats, rounds, n))
+        for k in sorted(kern[0]):
+            v = [g[k][0] for g in kern]
+            print("  %-18s %8.3f ms an image (min %.3f, max %.3f), %d scopes a round" % (k, statistics.median(v), min(v), max(v), kern[0][k][1]))
+        for name, ks in (("evaluator (cascade_strip)", ("cascade_strip",)), ("pyramid (%s)" % " + ".join(PYRAMID), PYRAMID)):
+            v = [sum(g[k][0] for k in ks if k in g) for g in kern]
+            print("  %s: median %.3f ms an image (min %.3f, max %.3f)" % (name, statistics.median(v), min(v), max(v)))
+        return statistics.median(wall), min(wall), max(wall)
+
+    print("# bench_lbp --batch: %d x %d gray images in HBM (one allocation, equally spaced), scale factor %.2f, min_neighbors %d; 24 x 24 LBP cascade, %d stages"
+          % (W, H, SF, MN, len(STAGES)))
+    if not have_batch:
+        print("# this library has no nvca_detect_multiscale_batch: loops of single calls alone")
+    for n in sizes:
+        single = report("loop of %d nvca_detect_multiscale calls" % n, n, *measure(loop, n))
+        if have_batch:
+            b = report("nvca_detect_multiscale_batch, %d images" % n, n, *measure(batch, n))
+            assert batch(n) == loop(n)
+            print("## %d images: batch %.3f ms an image (min %.3f, max %.3f) against %.3f (min %.3f, max %.3f) in single calls: %.2f x"
+                  % ((n,) + b + single + (single[0] / b[0],)))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--batch", default="", help="N[,N...]: time nvca_detect_multiscale_batch on N images beside N single calls, nothing else")
     args = ap.parse_args()
+    if args.batch:
+        return bench_batches(args, [int(v) for v in args.batch.split(",")])
     import torch
     import lbp_reference as R
     import orc
