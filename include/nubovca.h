@@ -37,7 +37,9 @@ extern "C" {
 #define NVCA_ERR_UNSUPPORTED -6  /* tree-structured STAGE graph (parent / next), or a
                                     feature that leaves the image at some scale; a
                                     new-format cascade that is not LBP with stumps; an
-                                    LBP cascade handed to a face or part stream      */
+                                    LBP cascade handed to nvca_face_stream_create or
+                                    to a part stream (nvca_face_stream_create_any
+                                    takes it)                                        */
 #define NVCA_ERR_OVERFLOW   -7   /* more raw candidates than the context's cap     */
 #define NVCA_ERR_NOMEM      -8
 #define NVCA_ERR_INTERNAL   -9   /* an internal check failed (a device result out of range, an exception caught at the
@@ -163,8 +165,10 @@ const char *nvca_kernel_name(int k);
  *    with stump weak classifiers.  New-format HAAR and HOG cascades, stage types other than BOOST, trees
  *    (maxDepth > 1) and maxCatCount != 256 are refused with NVCA_ERR_UNSUPPORTED.
  * An LBP cascade goes through nvca_detect_multiscale / nvca_detect_raw on single images and through their _batch forms on
- * several; the face and part streams refuse it (NVCA_ERR_UNSUPPORTED).  Its launches are booked under the existing timing slots: the evaluator's kernels under NVCA_K_STRIP
- * ("window per lane"), the level resize and integral under NVCA_K_RESIZE1 / NVCA_K_INTEGRAL as CV_HAAR_SCALE_IMAGE books them. */
+ * several, and through the face streams made with nvca_face_stream_create_any; nvca_face_stream_create and the part streams refuse
+ * it (NVCA_ERR_UNSUPPORTED).  Its launches are booked under the existing timing slots: the evaluator's kernels under NVCA_K_STRIP
+ * ("window per lane"), the level resize and integral under NVCA_K_RESIZE1 / NVCA_K_INTEGRAL as CV_HAAR_SCALE_IMAGE books them, a
+ * face stream's grouping under NVCA_K_GROUP. */
 #define NVCA_CASCADE_HAAR 0
 #define NVCA_CASCADE_LBP  1
 int  nvca_cascade_load_xml(nvca_ctx *ctx, const char *path, nvca_cascade **out);
@@ -339,6 +343,16 @@ typedef struct nvca_face_params {
 void nvca_face_params_default(nvca_face_params *p);
 int  nvca_face_stream_create(nvca_ctx *ctx, const nvca_cascade *cascade,
                              const nvca_face_params *params, nvca_face_stream **out);
+/* The same contract on every cascade format nvca_detect_multiscale takes: FACE/kmsfacedetect.cpp:162-177 loads whatever file
+ * cv::CascadeClassifier::load reads, and :805-811 then runs cv::CascadeClassifier::detectMultiScale on it.  On a Haar cascade the
+ * stream is nvca_face_stream_create's.  On a new-format LBP cascade an analysed frame is resize (or the 4:2:0 tap),
+ * BGR2GRAY, equalizeHist, the LBP scan of the equalised working image (scale factor 1 + scale_factor_pct / 100, minSize (cols / 20,
+ * rows / 20), no maximum size, flags ignored), groupRectangles(max(min_neighbors, 1), 0.2) -- the raw list in (level, y, x) order
+ * when min_neighbors is 0 -- and the unchanged gate, track_faces and box scaling.  Everything downstream (process, the batch calls,
+ * submit / collect, set_input, set_params, motion_event, host and device frames) serves both; LBP and Haar streams mix in one
+ * call.  NVCA_ERR_ARG for a cascade of another context. */
+int  nvca_face_stream_create_any(nvca_ctx *ctx, const nvca_cascade *cascade,
+                                 const nvca_face_params *params, nvca_face_stream **out);
 void nvca_face_stream_destroy(nvca_face_stream *s);
 int  nvca_face_stream_set_params(nvca_face_stream *s, const nvca_face_params *params);
 /* The pixel format of the stream's frames from the next frame on: NV12 / I420 frames as a decoder produced them, converted

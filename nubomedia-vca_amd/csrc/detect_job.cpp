@@ -66,7 +66,8 @@ static int si_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
     if ((rc = si_plan(ctx, j, &pp))) return rc;
     j.q.phase = kJobFirstQueued; j.q.dp = nullptr;
     if (pp->lv.empty()) return NVCA_OK;
-    if ((rc = pyr_build(ctx, j, pp, j.rq.casc->c.has_tilted))) return rc;
+    PyrSource src;
+    if ((rc = pyr_job_source(ctx, j, src)) || (rc = pyr_build(ctx, src, j.rq.cols, j.rq.rows, j.rq.nimg, pp, j.rq.casc->c.has_tilted))) return rc;
     j.q.cj = CascadeJob(); j.q.cj.r0 = r0; j.q.cj.n = j.rq.nimg; j.q.cj.total = total;
     if ((rc = cascade_enqueue(ctx, pp->det, pp->plane_total, pp->P, j.q.cj, nullptr, false))) return rc;
     j.q.gp = pp; pp->inflight++; j.q.dp = &pp->det;

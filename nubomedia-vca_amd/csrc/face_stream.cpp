@@ -64,16 +64,30 @@ try {
 }
 NVCA_API_CATCH_VOID
 
-int nvca_face_stream_create(nvca_ctx *ctx, const nvca_cascade *cascade, const nvca_face_params *params, nvca_face_stream **out)
-try {
-    if (!ctx || !cascade || !out) return NVCA_ERR_ARG;
-    if (cascade->format != NVCA_CASCADE_HAAR) { ctx->set_error("face streams do not take an LBP cascade (nvca_detect_multiscale does)"); return NVCA_ERR_UNSUPPORTED; }
+static int face_stream_new(nvca_ctx *ctx, const nvca_cascade *cascade, const nvca_face_params *params, nvca_face_stream **out)
+{
     nvca_face_stream *s = new (std::nothrow) nvca_face_stream();
     if (!s) return NVCA_ERR_NOMEM;
     s->ctx = ctx; s->cascade = cascade;
     if (params) s->p = *params; else nvca_face_params_default(&s->p);
     *out = s;
     return NVCA_OK;
+}
+int nvca_face_stream_create(nvca_ctx *ctx, const nvca_cascade *cascade, const nvca_face_params *params, nvca_face_stream **out)
+try {
+    if (!ctx || !cascade || !out) return NVCA_ERR_ARG;
+    if (cascade->format != NVCA_CASCADE_HAAR) { ctx->set_error("face streams do not take an LBP cascade (nvca_detect_multiscale does)"); return NVCA_ERR_UNSUPPORTED; }
+    return face_stream_new(ctx, cascade, params, out);
+}
+NVCA_API_CATCH(ctx)
+// FACE/kmsfacedetect.cpp:809-811 on whatever cascade file cv::CascadeClassifier::load took: a new-format LBP cascade's frames are
+// scanned by the LBP evaluator on the equalised working image's pyramid (face_submit); a Haar cascade's stream is nvca_face_stream_create's
+int nvca_face_stream_create_any(nvca_ctx *ctx, const nvca_cascade *cascade, const nvca_face_params *params, nvca_face_stream **out)
+try {
+    if (!ctx || !cascade || !out) return NVCA_ERR_ARG;
+    if (cascade->ctx != ctx) { ctx->set_error("the cascade belongs to another context"); return NVCA_ERR_ARG; }      // (its plans and tables are its context's)
+    if (cascade->format != NVCA_CASCADE_HAAR && cascade->format != NVCA_CASCADE_LBP) { ctx->set_error("face streams take a Haar or a new-format LBP cascade"); return NVCA_ERR_UNSUPPORTED; }
+    return face_stream_new(ctx, cascade, params, out);
 }
 NVCA_API_CATCH(ctx)
 void nvca_face_stream_destroy(nvca_face_stream *s) { delete s; }
@@ -111,7 +125,8 @@ struct FaceTicket {
     int n = 0;
     std::vector<nvca_face_stream *> streams;
     std::vector<FrameWork> work;
-    struct Group { GeomPlan *gp; std::vector<int> idx, gthr; std::vector<CascadeJob> jobs; };
+    // gp: the group's pre-processing (and, Haar, scan) plan; scan: the plan whose candidates its jobs leave (gp, or an LBP group's "LBP|" plan)
+    struct Group { GeomPlan *gp = nullptr, *scan = nullptr; std::vector<int> idx, gthr; std::vector<CascadeJob> jobs; };
     std::vector<Group> groups;
     hipEvent_t done = nullptr;
     // Two batches in flight run on two lanes (stream + planes each).  The second one's pre-processing (gray, LUT, integral:
@@ -120,6 +135,21 @@ struct FaceTicket {
     int lane = 0;
     hipEvent_t band_done = nullptr;
 };
+}
+
+// a job whose scan has no level (the working image is no larger than the window): an empty candidate list in its result slots
+static int empty_job(nvca_ctx *ctx, CascadeJob &job)
+{
+    ResultBufs &rb = ctx->ws->res[ctx->ws->cur_res];
+    const size_t hits_stride = (size_t)ctx->hit_cap + 1;
+    const int total = std::max(job.total, job.r0 + job.n);
+    if (rb.hits.ensure(hits_stride * total * sizeof(unsigned long long)) || rb.h_hits.ensure(hits_stride * total * sizeof(unsigned long long))) {
+        ctx->set_error("device allocation failed for the cascade workspace"); return NVCA_ERR_NOMEM;
+    }
+    job.cap = (unsigned)ctx->hit_cap * (unsigned)job.n; job.dev_group = false;
+    job.d_hits = rb.hits.as<unsigned long long>() + hits_stride * job.r0; job.h_hits = rb.h_hits.as<unsigned long long>() + hits_stride * job.r0;
+    NVCA_HIP_CHECK(ctx, hipMemsetAsync(job.d_hits, 0, sizeof(unsigned long long), ctx->cs()));
+    return cascade_fetch(ctx, job);
 }
 
 // first half: gating, then every launch of the batch queued on the context's stream (result set `res`); no waiting
@@ -211,11 +241,22 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
         }
         const int batch = (int)idx.size();
         const int cols = work[i].cols, rows = work[i].rows;
-        GeomPlan *gp = nullptr;
+        GeomPlan *gp = nullptr, *scan = nullptr;
         const double sf = 1 + s0->p.scale_factor_pct * 1.0 / 100;      // MULTI_SCALE_FACTOR :142
-        int rc = get_face_plan(ctx, s0->cascade, f0.width, f0.height, f0.stride, s0->yuv() ? 1 : 3, cols, rows, sf, cols / 20, rows / 20, 0, 0, &gp, s0->yuv());
-        if (rc) return rc;
-        grp.gp = gp; gp->inflight++;
+        const bool lbp = s0->cascade->format == NVCA_CASCADE_LBP;
+        int rc;
+        if (lbp) {
+            // the pre-processing half of the face plan and the LBP scan's own cached plan (no Haar scan tables from the cascade's empty `c`);
+            // detectMultiScale :809-811 with minSize (cols / 20, rows / 20) and no maximum size (the image's: make_detect_job's default)
+            if (!(sf > 1.0)) { ctx->set_error("scaleFactor must be greater than 1 (multi-scale-factor 0)"); return NVCA_ERR_ARG; }
+            if ((rc = get_face_pre_plan(ctx, f0.width, f0.height, f0.stride, s0->yuv() ? 1 : 3, cols, rows, &gp, s0->yuv()))) return rc;
+            grp.gp = gp; gp->inflight++;                               // (held while the second plan is stored: the cache may evict)
+            if ((rc = lbp_plan(ctx, s0->cascade, cols, rows, sf, cols / 20, rows / 20, cols, rows, &scan))) return rc;
+            grp.scan = scan; scan->inflight++;
+        } else {
+            if ((rc = get_face_plan(ctx, s0->cascade, f0.width, f0.height, f0.stride, s0->yuv() ? 1 : 3, cols, rows, sf, cols / 20, rows / 20, 0, 0, &gp, s0->yuv()))) return rc;
+            grp.gp = grp.scan = scan = gp; gp->inflight++;
+        }
         // Host frames: the batch goes through in chunks -- chunk c+1's H2D copies run on the copy stream while the
         // kernels of chunk c execute (with pageable memory the host blocks in the copy, the queued kernels do not).
         // Every chunk reuses planes [0, chunk); only its candidate list / box table are its own (CascadeJob).
@@ -250,7 +291,7 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
             ws.ln().hist_clean = 0;                                             // dirty until the LUT kernel is queued
             CascadeJob job; job.r0 = gbase + s0; job.n = nc; job.total = n;
             unsigned long long *z_hits = nullptr, *z_deep = nullptr;
-            if ((rc = cascade_counters(ctx, gp->det, job, &z_hits, &z_deep))) return rc;
+            if (!lbp && (rc = cascade_counters(ctx, gp->det, job, &z_hits, &z_deep))) return rc;      // (the LBP launch set resets its own counters)
             if (yuv) {
               TimedLaunch t(ctx, NVCA_K_GRAY);                             // cvtColor(YUV2BGR) + cv::resize + cvtColor :805-806 (+ histogram)
               const bool wide = launch_gray_yuv(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, yuv_planes(yuv), gp->view(),
@@ -260,13 +301,21 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
             { TimedLaunch t(ctx, NVCA_K_GRAY);                             // cv::resize + cvtColor :805-806 (+ histogram)
               launch_gray(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, gp->view(),
                           ws.ln().gray.as<uint8_t>(), ws.ln().hist.as<unsigned>(), nc, frames_aligned4(frames, idx.data() + s0, nc)); }
-            { TimedLaunch t(ctx, NVCA_K_LUT);                              // equalizeHist :807 (applied inside the integral pass)
+            { TimedLaunch t(ctx, NVCA_K_LUT);                              // equalizeHist :807 (applied inside the integral pass / where the pyramid reads the image)
               launch_lut(ctx->cs(), ws.ln().hist.as<unsigned>(), cols * rows, ws.ln().lut.as<uint8_t>(), nc, 1, z_hits, z_deep); }
-            job.counters_zeroed = true;
+            job.counters_zeroed = !lbp;
             ws.ln().hist_clean = hist_clean;
+            if (lbp) {
+                // detectMultiScale :809-811 on a new-format cascade: the pyramid of the equalised working image, read from the lane's gray
+                // slots through their LUTs, the LBP evaluator, groupRectangles on the candidate keys (lbp_job.cpp)
+                const PyrSource src{ws.ln().gray.as<uint8_t>(), gp->g.gpitch, gp->g.gray_slot, ws.ln().lut.as<uint8_t>()};
+                if (!scan->lv.empty()) { if ((rc = lbp_launch_set(ctx, scan, src, cols, rows, nc, job, gthr.data() + s0, tk.band_done))) return rc; }
+                else { if ((rc = empty_job(ctx, job))) return rc; NVCA_HIP_CHECK(ctx, hipEventRecord(tk.band_done, ctx->cs())); }
+            } else {
             run_integral(ctx, gp->g, ws.ln().lut.as<uint8_t>(), nc);
             if (streams[idx[0]]->cascade->c.has_tilted && (rc = run_tilted(ctx, gp->g, ws.ln().lut.as<uint8_t>(), nc))) return rc;
             if ((rc = cascade_enqueue(ctx, gp->det, gp->g.sum_slot, gp->g.spitch, job, gthr.data() + s0, true, tk.band_done))) return rc;   // detectMultiScale :809-811
+            }
             band_recorded = true;
             jobs.push_back(job);
         }
@@ -282,7 +331,7 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
 
 static void face_release(FaceTicket &tk)
 {
-    for (FaceTicket::Group &g : tk.groups) if (g.gp) g.gp->inflight--;
+    for (FaceTicket::Group &g : tk.groups) { if (g.gp) g.gp->inflight--; if (g.scan && g.scan != g.gp) g.scan->inflight--; }
     tk.groups.clear(); tk.pending = false;
 }
 
@@ -303,7 +352,7 @@ static int face_collect(nvca_ctx *ctx, int res, FaceTicket &tk, nvca_rect *out, 
         for (const CascadeJob &job : grp.jobs) {
             std::vector<std::vector<nvca_rect>> raw;
             std::vector<char> grouped;
-            if ((rc = cascade_collect(ctx, grp.gp->det, job, raw, &grouped))) { face_release(tk); return rc; }
+            if ((rc = cascade_collect(ctx, grp.scan->det, job, raw, &grouped))) { face_release(tk); return rc; }
             for (int b = 0; b < job.n; b++) {
                 const int gi = job.r0 - gi0 + b;                         // position inside the group
                 if (grp.gthr[gi] != 0 && !grouped[b]) group_rectangles(raw[b], grp.gthr[gi], 0.2);

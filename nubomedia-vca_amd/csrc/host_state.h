@@ -70,6 +70,7 @@ struct LbpPlan {
     DevBuf d_blob; LbpArgs args{};
     size_t bit_words = 0, positions = 0;      // stage-0 pass bits (u32 words) and grid positions of all levels
     int lds = 0;                              // bytes of the stage-0 tile (0: the window is too large, stage 0 gathers from the plane)
+    const ScaleRec *gscales = nullptr; const int *gpos = nullptr;      // device grouping: a record per level, the levels' output coordinates (in d_blob)
     ~LbpPlan() { d_blob.release(); }
 };
 
@@ -127,6 +128,10 @@ int run_tilted(nvca_ctx *ctx, const PreGeom &g, const uint8_t *lut, int batch, c
 int cascade_counters(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, unsigned long long **hits, unsigned long long **deep);
 int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, CascadeJob &job, const int *group_thr, bool want_group,
                     hipEvent_t early_done = nullptr /* recorded behind the band / tile kernels, ahead of the late stages */);
+// the two ends of a job that are no kernel's own (cascade_enqueue and the LBP launch set share them): the box-table region and the
+// thresholds of a job k_group serves (job.dev_group); the copy of the job's results towards the host behind its last kernel
+int group_prepare(nvca_ctx *ctx, CascadeJob &job, const int *group_thr);
+int cascade_fetch(nvca_ctx *ctx, CascadeJob &job);
 int cascade_collect(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, std::vector<std::vector<nvca_rect>> &raw,
                     std::vector<char> *grouped, std::vector<std::vector<int>> *scale_of = nullptr);
 void group_all(std::vector<std::vector<nvca_rect>> &raw, int min_neighbors);
@@ -134,6 +139,7 @@ GeomPlan *find_plan(nvca_ctx *ctx, const std::string &key);
 GeomPlan *store_plan(nvca_ctx *ctx, const std::string &key, std::unique_ptr<GeomPlan> gp);
 int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int stride, int cn, int cols, int rows,
                   double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out, const nvca_pixel_layout *yuv = nullptr);
+int get_face_pre_plan(nvca_ctx *ctx, int W, int H, int stride, int cn, int cols, int rows, GeomPlan **out, const nvca_pixel_layout *yuv = nullptr);   // its pre-processing half alone
 int get_resize_plan(nvca_ctx *ctx, int sw, int sh, int dw, int dh, GeomPlan **out);
 
 // ---- host_copy.cpp
@@ -229,9 +235,19 @@ int pyr_upload_levels(nvca_ctx *ctx, GeomPlan &np);                             
 int pyr_plan_init(nvca_ctx *ctx, GeomPlan &np, int cols, int rows, const std::vector<SiLevel> &levels);      // both, one after the other
 ScaleSpec level_spec(int P, const PyrLevel &L, int ow, int oh, int adaptive);                                // a level's scan grid
 bool job_images_in_place(const DetectJob &j, size_t *slot);
-int pyr_build(nvca_ctx *ctx, DetectJob &j, GeomPlan *pp, bool has_tilted);
+// The images a pyramid is built from: image k at img + k * slot, rows `pitch` bytes apart.  luts: null, or a 256-byte table per image that
+// every sample is read through -- the gray slots and LUTs a face stream's lane holds (the equalised working image is never written out).
+struct PyrSource { const uint8_t *img; int pitch; size_t slot; const uint8_t *luts; };
+int pyr_job_source(nvca_ctx *ctx, const DetectJob &j, PyrSource &src);       // a job's images: in place, or staged into the lane's gray slots
+int pyr_build(nvca_ctx *ctx, const PyrSource &src, int cols, int rows, int nimg, GeomPlan *pp, bool has_tilted);
 
-// ---- lbp_job.cpp
+// ---- lbp_job.cpp: the cached plan and the launch set of a new-format LBP scan, for a detectMultiScale job and for a face stream's chunk
+int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out);
+// pyramid of `nimg` images of `src`, the evaluator, and -- group_thr given ([nimg] groupRectangles thresholds) and device grouping
+// allowed -- k_group on the candidate keys; the job's result slots are cj.r0 .. cj.r0 + nimg of cj.total.  early_done: recorded behind the
+// evaluator's launches.  Collected with cascade_collect(pp->det).
+int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, int rows, int nimg, CascadeJob &cj,
+                   const int *group_thr = nullptr, hipEvent_t early_done = nullptr);
 int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total);              // the launch set of a job on a new-format LBP cascade
 
 // ---- detect_job.cpp

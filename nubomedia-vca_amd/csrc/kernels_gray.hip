@@ -271,13 +271,27 @@ __device__ __forceinline__ int resize1_value(const uint8_t *__restrict__ src, in
     return resize1_sample([&](int r, int c) { return (int)src[(size_t)r * sstride + c]; }, sh, t, x, y);
 }
 
-__global__ __launch_bounds__(256) void k_resize1(
-    const uint8_t *__restrict__ src, int sw, int sh, int sstride, ResizeView t,
-    uint8_t *__restrict__ dst, int dw, int dh, int dstride, unsigned *__restrict__ hist, size_t src_slot, size_t dst_slot)
+// the LDS copy of a frame's LUT in the kernels that read an image through one (none in the instantiations that do not)
+template <bool LUT>
+__device__ __forceinline__ uint8_t *lut_lds()
+{
+    if constexpr (LUT) { __shared__ uint8_t sl[256]; return sl; }
+    else return nullptr;
+}
+
+// LUT: image z's sample is lut[z][byte] (cv::equalizeHist in front of the resize, applied where the image is read: the frame's 256-byte
+// LUT is staged in LDS once a workgroup, as k_work_resize<kWorkGray> does it); otherwise the byte itself, and `luts` is not read
+template <bool LUT>
+__device__ __forceinline__ void resize1_rows(
+    const uint8_t *__restrict__ src, int sh, int sstride, ResizeView t,
+    uint8_t *__restrict__ dst, int dw, int dh, int dstride, unsigned *__restrict__ hist, size_t src_slot, size_t dst_slot,
+    const uint8_t *__restrict__ luts)
 {
     __shared__ unsigned lh[4][256];
+    uint8_t *const sl = lut_lds<LUT>();
     const int tid = threadIdx.x, wave = tid >> 6;
     for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    if (LUT) sl[tid] = luts[(size_t)blockIdx.z * 256 + tid];
     __syncthreads();
     src += (size_t)blockIdx.z * src_slot; dst += (size_t)blockIdx.z * dst_slot;      // several images of one geometry
     if (hist) hist += (size_t)blockIdx.z * 256;
@@ -286,12 +300,26 @@ __global__ __launch_bounds__(256) void k_resize1(
         const int y = blockIdx.y * kGrayRows + ry;
         if (y >= dh) break;
         if (x < dw) {
-            const int v = resize1_value(src, sh, sstride, t, x, y);
+            const int v = LUT ? resize1_sample([&](int r, int c) { return (int)sl[src[(size_t)r * sstride + c]]; }, sh, t, x, y)
+                              : resize1_value(src, sh, sstride, t, x, y);
             dst[(size_t)y * dstride + x] = (uint8_t)v;
             if (hist) atomicAdd(&lh[wave][v], 1u);
         }
     }
     if (hist) hist_flush(lh, hist, tid);
+}
+__global__ __launch_bounds__(256) void k_resize1(
+    const uint8_t *__restrict__ src, int sw, int sh, int sstride, ResizeView t,
+    uint8_t *__restrict__ dst, int dw, int dh, int dstride, unsigned *__restrict__ hist, size_t src_slot, size_t dst_slot)
+{
+    resize1_rows<false>(src, sh, sstride, t, dst, dw, dh, dstride, hist, src_slot, dst_slot, nullptr);
+}
+__global__ __launch_bounds__(256) void k_resize1_lut(
+    const uint8_t *__restrict__ src, int sw, int sh, int sstride, ResizeView t,
+    uint8_t *__restrict__ dst, int dw, int dh, int dstride, unsigned *__restrict__ hist, size_t src_slot, size_t dst_slot,
+    const uint8_t *__restrict__ luts)
+{
+    resize1_rows<true>(src, sh, sstride, t, dst, dw, dh, dstride, hist, src_slot, dst_slot, luts);
 }
 
 // ---- 8UC3 resize (cv::resize on the BGR frame, FACE/kmsfacedetect.cpp:805, as a stand-alone primitive;
@@ -322,10 +350,11 @@ void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstr
 }
 
 void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, const ResizeView &t,
-                    uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch, size_t src_slot, size_t dst_slot)
+                    uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch, size_t src_slot, size_t dst_slot, const uint8_t *luts)
 {
     dim3 grid((dw + 255) / 256, (dh + kGrayRows - 1) / kGrayRows, batch);
-    NVCA_LAUNCH(k_resize1, grid, dim3(256), 0, st, src, sw, sh, sstride, t, dst, dw, dh, dstride, hist, src_slot, dst_slot);
+    if (luts) NVCA_LAUNCH(k_resize1_lut, grid, dim3(256), 0, st, src, sw, sh, sstride, t, dst, dw, dh, dstride, hist, src_slot, dst_slot, luts);
+    else      NVCA_LAUNCH(k_resize1, grid, dim3(256), 0, st, src, sw, sh, sstride, t, dst, dw, dh, dstride, hist, src_slot, dst_slot);
 }
 
 // ---- working images of the part detectors, all frames of a batched call in one launch: image z of the launch is
@@ -379,28 +408,49 @@ void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, 
 #undef NVCA_WORK_RESIZE
 }
 
-// ---- CV_HAAR_SCALE_IMAGE pyramids: every level of every image in one launch (k_pyr_integral, kernels_integral.hip, takes them from here)
-__global__ __launch_bounds__(256) void k_pyr_resize(const uint8_t *__restrict__ src, int sw, int sh, int sstride, size_t src_slot,
-                                                    const PyrLevelDev *__restrict__ levels, int nimg,
-                                                    uint8_t *__restrict__ aux, size_t aux_slot)
+// ---- CV_HAAR_SCALE_IMAGE / LBP pyramids: every level of every image in one launch (k_pyr_integral, kernels_integral.hip, takes them from here).
+// LUT: the pyramid of lut[img][image] -- a face stream's equalised working image, which is never written out: equalizeHist first, cv::resize
+// second, as OpenCV orders them; level 0 (identity) is the equalised image itself
+template <bool LUT>
+__device__ __forceinline__ void pyr_resize_rows(const uint8_t *__restrict__ src, int sh, int sstride, size_t src_slot,
+                                                const PyrLevelDev *__restrict__ levels, int nimg,
+                                                uint8_t *__restrict__ aux, size_t aux_slot, const uint8_t *__restrict__ luts)
 {
+    uint8_t *const sl = lut_lds<LUT>();
     const int lev = blockIdx.z / nimg, img = blockIdx.z - lev * nimg;
     const PyrLevelDev L = levels[lev];
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x * 256 >= L.szw || blockIdx.y * kGrayRows >= L.szh) return;
+    if (LUT) { sl[threadIdx.x] = luts[(size_t)img * 256 + threadIdx.x]; __syncthreads(); }      // (the return above is the whole workgroup's)
     const uint8_t *s = src + (size_t)img * src_slot;
     uint8_t *d = aux + (size_t)img * aux_slot + L.gray_off;
     for (int ry = 0; ry < kGrayRows; ry++) {
         const int y = blockIdx.y * kGrayRows + ry;
         if (y >= L.szh) break;
-        if (x < L.szw) d[(size_t)y * L.gpitch + x] = (uint8_t)resize1_value(s, sh, sstride, L.tab, x, y);
+        if (x < L.szw) {
+            if (LUT) d[(size_t)y * L.gpitch + x] = (uint8_t)resize1_sample([&](int r, int c) { return (int)sl[s[(size_t)r * sstride + c]]; }, sh, L.tab, x, y);
+            else d[(size_t)y * L.gpitch + x] = (uint8_t)resize1_value(s, sh, sstride, L.tab, x, y);
+        }
     }
 }
+__global__ __launch_bounds__(256) void k_pyr_resize(const uint8_t *__restrict__ src, int sw, int sh, int sstride, size_t src_slot,
+                                                    const PyrLevelDev *__restrict__ levels, int nimg,
+                                                    uint8_t *__restrict__ aux, size_t aux_slot)
+{
+    pyr_resize_rows<false>(src, sh, sstride, src_slot, levels, nimg, aux, aux_slot, nullptr);
+}
+__global__ __launch_bounds__(256) void k_pyr_resize_lut(const uint8_t *__restrict__ src, int sw, int sh, int sstride, size_t src_slot,
+                                                        const PyrLevelDev *__restrict__ levels, int nimg,
+                                                        uint8_t *__restrict__ aux, size_t aux_slot, const uint8_t *__restrict__ luts)
+{
+    pyr_resize_rows<true>(src, sh, sstride, src_slot, levels, nimg, aux, aux_slot, luts);
+}
 void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,
-                       int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot)
+                       int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot, const uint8_t *luts)
 {
     dim3 grid((maxw + 255) / 256, (maxh + kGrayRows - 1) / kGrayRows, nlev * nimg);
-    NVCA_LAUNCH(k_pyr_resize, grid, dim3(256), 0, st, src, sw, sh, sstride, src_slot, levels, nimg, aux, aux_slot);
+    if (luts) NVCA_LAUNCH(k_pyr_resize_lut, grid, dim3(256), 0, st, src, sw, sh, sstride, src_slot, levels, nimg, aux, aux_slot, luts);
+    else      NVCA_LAUNCH(k_pyr_resize, grid, dim3(256), 0, st, src, sw, sh, sstride, src_slot, levels, nimg, aux, aux_slot);
 }
 
 } // namespace nvca

@@ -37,11 +37,13 @@ bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom 
                      uint8_t *gray, unsigned *hist, int batch, bool aligned16);
 void launch_yuv420_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int ystride, const YuvPlanes &p, uint8_t *dst, int dstride);
 void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,
-                       int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot);
+                       int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot,
+                       const uint8_t *luts = nullptr /* [nimg][256]: the pyramid of lut[img][image]; null: of the image */);
 void launch_pyr_integral(hipStream_t st, const uint8_t *aux, size_t aux_slot, const PyrLevelDev *levels, int nlev, int nimg,
                          int *sum, unsigned *sq32, size_t sum_slot, int P);
 void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, const ResizeView &t,
-                    uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0);
+                    uint8_t *dst, int dw, int dh, int dstride, unsigned *hist, int batch = 1, size_t src_slot = 0, size_t dst_slot = 0,
+                    const uint8_t *luts = nullptr /* [batch][256]: image z is read through its LUT */);
 void launch_resize3(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, const ResizeView &t,
                     uint8_t *dst, int dw, int dh, int dstride);
 void launch_flip_h(hipStream_t st, const uint8_t *src, int w, int h, int spitch, uint8_t *dst, int dpitch, int batch = 1, size_t src_slot = 0,

@@ -12,18 +12,19 @@ namespace nvca {
 
 // cv::CascadeClassifier::detectMultiScale on a new-format LBP cascade (OpenCV 2.4 cascadedetect.cpp): the pyramid of
 // CV_HAAR_SCALE_IMAGE with its own level rules, scanned by the LBP evaluator (kernels_cascade_lbp.hip).  The plan holds the pyramid
-// (layout, resize tables), one scan grid per level and the cascade's tables at the pitch of the planes and of the stage-0 tile.
-static int lbp_plan(nvca_ctx *ctx, const DetectJob &j, GeomPlan **out)
+// (layout, resize tables), one scan grid per level, the cascade's tables at the pitch of the planes and of the stage-0 tile, and the
+// levels as k_group reads them.  Cached per (cascade, image size, parameters): a detectMultiScale job and a face stream of one
+// geometry share it.
+int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out)
 {
-    const LbpCascade &c = j.rq.casc->lbp;
-    const int cols = j.rq.cols, rows = j.rq.rows;
+    const LbpCascade &c = casc->lbp;
     int rc;
     char key[256];
-    snprintf(key, sizeof(key), "LBP|%llu|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)j.rq.casc->c.uid, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh);
+    snprintf(key, sizeof(key), "LBP|%llu|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)casc->c.uid, cols, rows, sf, minw, minh, maxw, maxh);
     GeomPlan *pp = find_plan(ctx, key);
     if (!pp) {
         std::unique_ptr<GeomPlan> np(new GeomPlan());
-        if ((rc = pyr_plan_init(ctx, *np, cols, rows, lbp_levels(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, 63)))) return rc;
+        if ((rc = pyr_plan_init(ctx, *np, cols, rows, lbp_levels(c.ow, c.oh, cols, rows, sf, minw, minh, maxw, maxh, 63)))) return rc;
         if (!np->lv.empty()) {
             // the scan grids: what hit_valid / hit_rect check and map a candidate key with
             for (const PyrLevel &L : np->lv) np->det.specs.push_back(level_spec(np->P, L, c.ow, c.oh, 1));
@@ -34,7 +35,8 @@ static int lbp_plan(nvca_ctx *ctx, const DetectJob &j, GeomPlan **out)
             TableBlob blob;
             const size_t o_levels = blob.add(t.levels.data(), t.levels.size() * sizeof(LbpLevelDev)), o_tiles = blob.add(t.tiles.data(), t.tiles.size() * sizeof(LbpTile)),
                          o_stages = blob.add(t.stages.data(), t.stages.size() * sizeof(LbpStageDev)), o_gweak = blob.add(t.gweak.data(), t.gweak.size() * sizeof(LbpWeakDev)),
-                         o_tweak = blob.add(t.tweak.data(), t.tweak.size() * sizeof(LbpWeakDev));
+                         o_tweak = blob.add(t.tweak.data(), t.tweak.size() * sizeof(LbpWeakDev)),
+                         o_gscales = blob.add(t.gscales.data(), t.gscales.size() * sizeof(ScaleRec)), o_gpos = blob.add(t.gpos.data(), t.gpos.size() * sizeof(int));
             if ((rc = blob.upload(ctx, lp.d_blob))) return rc;
             LbpArgs &a = lp.args; memset(&a, 0, sizeof(a));
             const unsigned char *base = lp.d_blob.as<unsigned char>();
@@ -45,6 +47,7 @@ static int lbp_plan(nvca_ctx *ctx, const DetectJob &j, GeomPlan **out)
             a.P = np->P; a.TP = t.TP; a.ow = c.ow; a.oh = c.oh; a.nrows = t.nrows;
             a.key_sy = t.key_sy; a.key_ss = t.key_ss; a.tile_stages = t.tile_stages;
             lp.bit_words = t.bit_words; lp.positions = t.positions; lp.lds = t.lds;
+            lp.gscales = (const ScaleRec *)(base + o_gscales); lp.gpos = (const int *)(base + o_gpos);
         }
         pp = store_plan(ctx, key, std::move(np));
     }
@@ -52,24 +55,23 @@ static int lbp_plan(nvca_ctx *ctx, const DetectJob &j, GeomPlan **out)
     return NVCA_OK;
 }
 
-int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
+// The launch set of an LBP scan, stated once: the pyramid of `nimg` images of `src` (the caller's images, or a lane's gray slots read
+// through their LUTs), the evaluator on all of them, and -- group_thr given -- groupRectangles on the device; results into slots
+// cj.r0 .. cj.r0 + nimg of cj.total.  Work buffers are the current lane's.
+int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, int rows, int nimg, CascadeJob &cj, const int *group_thr,
+                   hipEvent_t early_done)
 {
     Workspace &ws = *ctx->ws;
     ResultBufs &rb = ws.res[ws.cur_res];
-    GeomPlan *pp = nullptr;
     int rc;
-    if ((rc = lbp_plan(ctx, j, &pp))) return rc;
-    j.q.phase = kJobFirstQueued; j.q.dp = nullptr;
-    if (pp->lv.empty()) return NVCA_OK;
     // (the pyramid launchers write the squared integral with the sum: it is computed and ignored here)
-    if ((rc = pyr_build(ctx, j, pp, false))) return rc;
+    if ((rc = pyr_build(ctx, src, cols, rows, nimg, pp, false))) return rc;
     const LbpPlan &lp = pp->lbp;
     // The job's images share every launch.  Pass bits per image; the two survivor lists are the whole job's, and either holds every
     // grid position of every image: a list that could be too short would drop windows, so it is never sized by an estimate.
-    const int nimg = j.rq.nimg;
     const size_t entries = lp.positions * (size_t)nimg;
     if (entries > 0xffffffffull) { ctx->set_error("LBP scan: more grid positions in one job than its list counters count"); return NVCA_ERR_ARG; }
-    const int tot = std::max(total, r0 + nimg);
+    const int r0 = cj.r0, tot = std::max(cj.total, r0 + nimg);
     const size_t hits_stride = (size_t)ctx->hit_cap + 1;
     constexpr size_t kCnt = 64;                       // list counters in front of the first list (kCnt u32 words: the list behind them stays 8-byte aligned)
     if (ws.ln().failbits.ensure(2 * lp.bit_words * nimg * sizeof(unsigned) + 8) || ws.ln().deep.ensure(kCnt * sizeof(unsigned) + entries * sizeof(unsigned long long)) ||
@@ -77,11 +79,12 @@ int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
         rb.hits.ensure(hits_stride * tot * sizeof(unsigned long long)) || rb.h_hits.ensure(hits_stride * tot * sizeof(unsigned long long))) {
         ctx->set_error("device allocation failed for the cascade workspace"); return NVCA_ERR_NOMEM;
     }
-    CascadeJob &cj = j.q.cj;
-    cj = CascadeJob(); cj.r0 = r0; cj.n = nimg; cj.total = total;
+    cj.n = nimg;
     cj.cap = (unsigned)ctx->hit_cap * (unsigned)nimg;         // one list for all the job's slots, as cascade_enqueue's
     cj.d_hits = rb.hits.as<unsigned long long>() + hits_stride * r0;
     cj.h_hits = rb.h_hits.as<unsigned long long>() + hits_stride * r0;
+    cj.dev_group = group_thr && !ctx->sw.host_group;
+    if (cj.dev_group && (rc = group_prepare(ctx, cj, group_thr))) return rc;
     NVCA_HIP_CHECK(ctx, hipMemsetAsync(cj.d_hits, 0, sizeof(unsigned long long), ctx->cs()));
     NVCA_HIP_CHECK(ctx, hipMemsetAsync(ws.ln().deep.p, 0, kCnt * sizeof(unsigned), ctx->cs()));
     LbpArgs a = lp.args;
@@ -103,9 +106,32 @@ int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
             if (s1 >= a.nstages) break;
         }
     }
+    if (early_done) NVCA_HIP_CHECK(ctx, hipEventRecord(early_done, ctx->cs()));
+    if (cj.dev_group) {
+        // k_group as the Haar stream path launches it, on the fields it reads: the candidate list, the key layout, a ScaleRec per level
+        // and the levels' output coordinates (lbp_tables.cpp)
+        CascadeArgs ga; memset(&ga, 0, sizeof(ga));
+        ga.hits = cj.d_hits; ga.hit_cap = cj.cap; ga.key_sy = a.key_sy; ga.key_ss = a.key_ss; ga.scales = lp.gscales; ga.pos = lp.gpos;
+        ga.nscales = a.nlev; ga.batch = nimg;
+        TimedLaunch t(ctx, NVCA_K_GROUP);
+        launch_group(ctx->cs(), ga, rb.gthr.as<int>() + r0, ctx->sw.group_zero_copy ? cj.h_grp : cj.d_grp, kGroupOutCap, nimg);
+    }
     NVCA_LAUNCH_CHECK(ctx);
-    cj.first = std::min<size_t>(cj.cap, 2048);
-    NVCA_HIP_CHECK(ctx, hipMemcpyAsync(cj.h_hits, cj.d_hits, (cj.first + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->cs()));
+    return cascade_fetch(ctx, cj);
+}
+
+int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
+{
+    GeomPlan *pp = nullptr;
+    int rc;
+    if ((rc = lbp_plan(ctx, j.rq.casc, j.rq.cols, j.rq.rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, &pp))) return rc;
+    j.q.phase = kJobFirstQueued; j.q.dp = nullptr;
+    if (pp->lv.empty()) return NVCA_OK;
+    PyrSource src;
+    if ((rc = pyr_job_source(ctx, j, src))) return rc;
+    CascadeJob &cj = j.q.cj;
+    cj = CascadeJob(); cj.r0 = r0; cj.total = total;
+    if ((rc = lbp_launch_set(ctx, pp, src, j.rq.cols, j.rq.rows, j.rq.nimg, cj))) return rc;      // (grouped on the host: detect_job_advance)
     j.q.gp = pp; pp->inflight++; j.q.dp = &pp->det;
     return NVCA_OK;
 }

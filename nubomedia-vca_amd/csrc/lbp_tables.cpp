@@ -1,5 +1,6 @@
 // lbp_tables.cpp -- the device tables of a new-format LBP scan (lbp_tables.h): pure host code.
 #include "lbp_tables.h"
+#include "host_math.h"
 #include <algorithm>
 #include <cstring>
 
@@ -18,6 +19,15 @@ int build_lbp_tables(const LbpCascade &c, const std::vector<PyrLevel> &lv, int P
         out.bit_words += (size_t)d.wpr * d.ny; out.nrows += d.ny; out.positions += (size_t)d.nx * d.ny;
         mx = std::max(mx, (size_t)d.nx); my = std::max(my, (size_t)d.ny);
         out.levels.push_back(d);
+        // the level as k_group reads it: a candidate (level, gy, gx) is Rect(cvRound(gx * step * f), cvRound(gy * step * f), winw, winh)
+        // (DetectPlan::hit_rect's arithmetic on the level's scan grid), the rounded coordinates in the position table
+        ScaleRec g; memset(&g, 0, sizeof(g));
+        g.winw = L.winw; g.winh = L.winh; g.plane_off = L.plane_off; g.pitch = P; g.endX = d.nx; g.endY = d.ny; g.factor = L.f;
+        g.xpos_off = (int)out.gpos.size();
+        for (int gx = 0; gx < d.nx; gx++) out.gpos.push_back(cv_round(gx * d.step * L.f));
+        g.ypos_off = (int)out.gpos.size();
+        for (int gy = 0; gy < d.ny; gy++) out.gpos.push_back(cv_round(gy * d.step * L.f));
+        out.gscales.push_back(g);
     }
     int bx, by, bs;
     candidate_key_bits(mx, my, lv.size(), &bx, &by, &bs);

@@ -11,6 +11,9 @@ namespace nvca {
 
 struct LbpTables {
     std::vector<LbpLevelDev> levels; std::vector<LbpTile> tiles; std::vector<LbpStageDev> stages;
+    // device grouping (k_group, kernels_group.hip): a ScaleRec per level -- window size, grid extents, where its columns' and rows' OUTPUT
+    // coordinates lie in gpos -- and those coordinates, cvRound(origin * factor), rounded here
+    std::vector<ScaleRec> gscales; std::vector<int> gpos;
     std::vector<LbpWeakDev> gweak, tweak;     // corner offsets at the planes' pitch P / at the stage-0 tile's pitch TP
     int TP = 0, nrows = 0;                    // scan rows of all levels
     int key_sy = 0, key_ss = 0;               // candidate key = level << key_ss | gy << key_sy | gx

@@ -200,6 +200,45 @@ int cascade_counters(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, unsig
     return NVCA_OK;
 }
 
+// A job whose candidates k_group turns into boxes (job.dev_group): its box-table region -- per result slot a table, a job's tables
+// followed by the 64-bit raw count -- and its slots' groupRectangles thresholds on the device
+int group_prepare(nvca_ctx *ctx, CascadeJob &job, const int *group_thr)
+{
+    ResultBufs &rb = ctx->ws->res[ctx->ws->cur_res];
+    const int batch = job.n, total = std::max(job.total, job.r0 + job.n);
+    const size_t grp_stride = 2 + 4 * kGroupOutCap + 2;
+    const void *old_gthr = rb.gthr.p;
+    if (rb.grp.ensure((size_t)total * grp_stride * sizeof(int)) || rb.h_grp.ensure((size_t)total * grp_stride * sizeof(int)) ||
+        rb.gthr.ensure((size_t)total * sizeof(int)) || rb.h_gthr.ensure((size_t)total * sizeof(int))) {
+        ctx->set_error("device allocation failed for the grouping workspace"); return NVCA_ERR_NOMEM;
+    }
+    if (rb.gthr.p != old_gthr) rb.gthr_last.clear();          // a new buffer holds no thresholds yet
+    job.d_grp = rb.grp.as<int>() + grp_stride * job.r0; job.h_grp = rb.h_grp.as<int>() + grp_stride * job.r0;
+    if (rb.gthr_last.size() < (size_t)total) rb.gthr_last.resize(total, -1);
+    if (memcmp(rb.gthr_last.data() + job.r0, group_thr, batch * sizeof(int)) != 0) {
+        NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));             // h_gthr may still feed an earlier copy
+        memcpy(rb.h_gthr.as<int>() + job.r0, group_thr, batch * sizeof(int));
+        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(rb.gthr.as<int>() + job.r0, rb.h_gthr.as<int>() + job.r0, batch * sizeof(int), hipMemcpyHostToDevice, ctx->cs()));
+        std::copy(group_thr, group_thr + batch, rb.gthr_last.begin() + job.r0);
+    }
+    return NVCA_OK;
+}
+
+// behind a job's last kernel: what the host reads once the stream has drained, on its way
+int cascade_fetch(nvca_ctx *ctx, CascadeJob &job)
+{
+    const size_t rec = 2 + 4 * kGroupOutCap;
+    if (job.dev_group && ctx->sw.group_zero_copy) {
+        // nothing to copy: k_group wrote the host buffer
+    } else if (job.dev_group) {      // the device hands back final boxes; the raw list is only fetched for frames it declined
+        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(job.h_grp, job.d_grp, (rec * job.n + 2) * sizeof(int), hipMemcpyDeviceToHost, ctx->cs()));
+    } else {              // one D2H covers the count and (almost always) every candidate
+        job.first = std::min<size_t>(job.cap, 2048);
+        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(job.h_hits, job.d_hits, (job.first + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->cs()));
+    }
+    return NVCA_OK;
+}
+
 int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, CascadeJob &job, const int *group_thr, bool want_group,
                     hipEvent_t early_done)
 {
@@ -207,6 +246,7 @@ int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, 
     ResultBufs &rb = ws.res[ws.cur_res];
     const bool grp_zero_copy = ctx->sw.group_zero_copy;
     const int batch = job.n, total = std::max(job.total, job.r0 + job.n);
+    int rc;
     const size_t hits_stride = (size_t)ctx->hit_cap + 1;                 // u64 words per result slot
     const unsigned cap = (unsigned)ctx->hit_cap * (unsigned)batch;
     const unsigned deep_cap = (unsigned)std::min<size_t>((size_t)dp.tasks.size() * 64 * batch + 64, 1u << 28);   // every window may survive
@@ -227,24 +267,7 @@ int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, 
     const bool host_group = ctx->sw.host_group;
     const bool dev_group = group_thr && want_group && dp.device_group_ok && !host_group && !dp.tasks.empty() && !skip_cascade;
     job.dev_group = dev_group;
-    const size_t rec = 2 + 4 * kGroupOutCap;
-    const size_t grp_stride = rec + 2;                                       // per result slot: a job's table is followed by the 64-bit raw count
-    if (dev_group) {
-        const void *old_gthr = rb.gthr.p;
-        if (rb.grp.ensure((size_t)total * grp_stride * sizeof(int)) || rb.h_grp.ensure((size_t)total * grp_stride * sizeof(int)) ||
-            rb.gthr.ensure((size_t)total * sizeof(int)) || rb.h_gthr.ensure((size_t)total * sizeof(int))) {
-            ctx->set_error("device allocation failed for the grouping workspace"); return NVCA_ERR_NOMEM;
-        }
-        if (rb.gthr.p != old_gthr) rb.gthr_last.clear();          // a new buffer holds no thresholds yet
-        job.d_grp = rb.grp.as<int>() + grp_stride * job.r0; job.h_grp = rb.h_grp.as<int>() + grp_stride * job.r0;
-        if (rb.gthr_last.size() < (size_t)total) rb.gthr_last.resize(total, -1);
-        if (memcmp(rb.gthr_last.data() + job.r0, group_thr, batch * sizeof(int)) != 0) {
-            NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));             // h_gthr may still feed an earlier copy
-            memcpy(rb.h_gthr.as<int>() + job.r0, group_thr, batch * sizeof(int));
-            NVCA_HIP_CHECK(ctx, hipMemcpyAsync(rb.gthr.as<int>() + job.r0, rb.h_gthr.as<int>() + job.r0, batch * sizeof(int), hipMemcpyHostToDevice, ctx->cs()));
-            std::copy(group_thr, group_thr + batch, rb.gthr_last.begin() + job.r0);
-        }
-    }
+    if (dev_group && (rc = group_prepare(ctx, job, group_thr))) return rc;
     if (!dp.tasks.empty() && !skip_cascade) {
         CascadeArgs a;
         a.sum = ws.ln().sum.as<int>(); a.sqsum = ws.ln().sqsum.as<unsigned long long>();
@@ -305,15 +328,7 @@ int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, 
         if (dev_group) { TimedLaunch t(ctx, NVCA_K_GROUP); launch_group(ctx->cs(), a, rb.gthr.as<int>() + job.r0, grp_zero_copy ? job.h_grp : job.d_grp, kGroupOutCap, batch); }
     }
     NVCA_LAUNCH_CHECK(ctx);
-    if (dev_group && grp_zero_copy) {
-        // nothing to copy: k_group wrote the host buffer
-    } else if (dev_group) {      // the device hands back final boxes; the raw list is only fetched for frames it declined
-        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(job.h_grp, job.d_grp, (rec * batch + 2) * sizeof(int), hipMemcpyDeviceToHost, ctx->cs()));
-    } else {              // one D2H covers the count and (almost always) every candidate
-        job.first = std::min<size_t>(cap, 2048);
-        NVCA_HIP_CHECK(ctx, hipMemcpyAsync(job.h_hits, job.d_hits, (job.first + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->cs()));
-    }
-    return NVCA_OK;
+    return cascade_fetch(ctx, job);
 }
 
 // after the stream has been synchronised: raw[b] / grouped[b] for the job's n frames
@@ -417,6 +432,20 @@ GeomPlan *store_plan(nvca_ctx *ctx, const std::string &key, std::unique_ptr<Geom
     return p;
 }
 
+// the pre-processing half of a face plan: working-image geometry, resize table, row copy of host frames
+static int face_plan_pre(nvca_ctx *ctx, GeomPlan &gp, int W, int H, int stride, int cn, int cols, int rows)
+{
+    make_geom(gp.g, W, H, stride, cn, cols, rows);
+    build_resize_tab(W, H, cols, rows, gp.tab);
+    gp.rowcopy = make_rowcopy(gp.tab);
+    return upload_tab(ctx, gp);
+}
+static void yuv_key(char *key, size_t room, const nvca_pixel_layout *yuv)
+{
+    if (yuv) snprintf(key, room, "|Y%d|%zu|%zu|%zu|%d|%d|%d", yuv->format, yuv->offset[0], yuv->offset[1], yuv->offset[2],
+                      yuv->stride[0], yuv->stride[1], yuv->stride[2]);
+}
+
 // plan for "BGR frame -> working image -> scale-cascade scan"
 // (yuv: the frames are 4:2:0 buffers of this layout; stride is their luma stride, cn 1)
 int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int stride, int cn, int cols, int rows,
@@ -428,14 +457,10 @@ int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int str
     char key[384];
     int kl = snprintf(key, sizeof(key), "F|%llu|%d|%d|%d|%d|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)casc->c.uid, W, H, stride,
                       cn, cols, rows, sf, minw, minh, maxw, maxh);
-    if (yuv) snprintf(key + kl, sizeof(key) - kl, "|Y%d|%zu|%zu|%zu|%d|%d|%d", yuv->format, yuv->offset[0], yuv->offset[1], yuv->offset[2],
-                      yuv->stride[0], yuv->stride[1], yuv->stride[2]);
+    yuv_key(key + kl, sizeof(key) - kl, yuv);
     if (GeomPlan *gp = find_plan(ctx, key)) { *out = gp; return NVCA_OK; }
     std::unique_ptr<GeomPlan> gp(new GeomPlan());
-    make_geom(gp->g, W, H, stride, cn, cols, rows);
-    build_resize_tab(W, H, cols, rows, gp->tab);
-    gp->rowcopy = make_rowcopy(gp->tab);
-    int rc = upload_tab(ctx, *gp);
+    int rc = face_plan_pre(ctx, *gp, W, H, stride, cn, cols, rows);
     if (rc) return rc;
     std::string err;
     rc = gp->det.build_scale_cascade(ctx, casc->c, cols, rows, gp->g.spitch, sf, minw, minh, maxw, maxh, err);
@@ -443,6 +468,21 @@ int get_face_plan(nvca_ctx *ctx, const nvca_cascade *casc, int W, int H, int str
     rc = gp->det.upload(ctx);
     if (rc) return rc;
     gp->has_det = true;
+    *out = store_plan(ctx, key, std::move(gp));
+    return NVCA_OK;
+}
+
+// that plan's pre-processing half alone, whatever scans the working image (a face stream on a new-format LBP cascade: its scan is
+// the cached "LBP|" plan, lbp_job.cpp)
+int get_face_pre_plan(nvca_ctx *ctx, int W, int H, int stride, int cn, int cols, int rows, GeomPlan **out, const nvca_pixel_layout *yuv)
+{
+    char key[256];
+    int kl = snprintf(key, sizeof(key), "FP|%d|%d|%d|%d|%d|%d", W, H, stride, cn, cols, rows);
+    yuv_key(key + kl, sizeof(key) - kl, yuv);
+    if (GeomPlan *gp = find_plan(ctx, key)) { *out = gp; return NVCA_OK; }
+    std::unique_ptr<GeomPlan> gp(new GeomPlan());
+    int rc = face_plan_pre(ctx, *gp, W, H, stride, cn, cols, rows);
+    if (rc) return rc;
     *out = store_plan(ctx, key, std::move(gp));
     return NVCA_OK;
 }

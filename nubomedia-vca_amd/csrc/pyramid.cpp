@@ -76,31 +76,40 @@ bool job_images_in_place(const DetectJob &j, size_t *slot)
     return true;
 }
 
-// the job's images resized to every level of the plan's pyramid and integrated (the squared integral with them; the tilted one when asked)
-int pyr_build(nvca_ctx *ctx, DetectJob &j, GeomPlan *pp, bool has_tilted)
+// where a job's images are read from: in place when they allow it, otherwise copied into the lane's gray slots first
+int pyr_job_source(nvca_ctx *ctx, const DetectJob &j, PyrSource &src)
 {
     Workspace &ws = *ctx->ws;
     const int cols = j.rq.cols, rows = j.rq.rows, nimg = j.rq.nimg;
     int rc;
-    const int P = pp->P;
-    const size_t gray_total = pp->gray_total, plane_total = pp->plane_total;
     PreGeom g0; make_geom(g0, cols, rows, j.rq.stride, 1, cols, rows);
     if ((rc = ensure_ws(ctx, g0, nimg))) return rc;
+    src = PyrSource{ws.ln().gray.as<uint8_t>(), g0.gpitch, g0.gray_slot, nullptr};
+    size_t in_place_slot = 0;
+    if (job_images_in_place(j, &in_place_slot)) src = PyrSource{(const uint8_t *)j.rq.img[0], j.rq.stride, in_place_slot, nullptr};
+    else
+        for (int k = 0; k < nimg; k++)
+            if ((rc = stage_2d(ctx, ws.ln().gray.as<uint8_t>() + g0.gray_slot * k, g0.gpitch, j.rq.img[k], j.rq.stride, cols, rows, j.rq.mem))) return rc;
+    return NVCA_OK;
+}
+
+// `nimg` cols x rows images of `src` resized to every level of the plan's pyramid and integrated (the squared integral with them; the
+// tilted one when asked).  The caller has sized the lane's pre-processing buffers for the images (ensure_ws).
+int pyr_build(nvca_ctx *ctx, const PyrSource &src, int cols, int rows, int nimg, GeomPlan *pp, bool has_tilted)
+{
+    Workspace &ws = *ctx->ws;
+    int rc;
+    const int P = pp->P;
+    const size_t gray_total = pp->gray_total, plane_total = pp->plane_total;
     if (ws.ln().aux.ensure(gray_total * nimg + 64) || ws.ln().sum.ensure((plane_total * nimg + 4 * (size_t)P) * sizeof(int)) || ws.ln().sqsum.ensure(plane_total * nimg * sizeof(unsigned long long)) ||
         (has_tilted && ws.ln().tilted.ensure((plane_total * nimg + 4 * (size_t)P) * sizeof(int)))) {
         ctx->set_error("allocation failed (pyramid)"); return NVCA_ERR_NOMEM;
     }
     if (has_tilted && (size_t)2 * (pp->pyr_maxw + pp->pyr_maxh + 2) * sizeof(int) > 64 * 1024) { ctx->set_error("image too large for the tilted integral"); return NVCA_ERR_ARG; }
-    const uint8_t *src0 = ws.ln().gray.as<uint8_t>(); int spitch0 = g0.gpitch; size_t sslot0 = g0.gray_slot;
-    size_t in_place_slot = 0;
-    if (job_images_in_place(j, &in_place_slot)) { src0 = (const uint8_t *)j.rq.img[0]; spitch0 = j.rq.stride; sslot0 = in_place_slot; }
-    else
-        for (int k = 0; k < nimg; k++)
-            if ((rc = stage_2d(ctx, ws.ln().gray.as<uint8_t>() + g0.gray_slot * k, g0.gpitch, j.rq.img[k], j.rq.stride, cols, rows, j.rq.mem))) return rc;
     if (pp->pyr_ok) {            // all levels of all images: one resize launch, one integral launch
         { TimedLaunch t(ctx, NVCA_K_RESIZE1);
-          launch_pyr_resize(ctx->cs(), src0, cols, rows, spitch0, sslot0, pp->d_pyr.as<PyrLevelDev>(),
-                            (int)pp->lv.size(), nimg, pp->pyr_maxw, pp->pyr_maxh, ws.ln().aux.as<uint8_t>(), gray_total); }
+          launch_pyr_resize(ctx->cs(), src.img, cols, rows, src.pitch, src.slot, pp->d_pyr.as<PyrLevelDev>(),
+                            (int)pp->lv.size(), nimg, pp->pyr_maxw, pp->pyr_maxh, ws.ln().aux.as<uint8_t>(), gray_total, src.luts); }
         { TimedLaunch t(ctx, NVCA_K_INTEGRAL);
           launch_pyr_integral(ctx->cs(), ws.ln().aux.as<uint8_t>(), gray_total, pp->d_pyr.as<PyrLevelDev>(), (int)pp->lv.size(), nimg,
                               ws.ln().sum.as<int>(), ws.ln().sqsum.as<unsigned>(), plane_total, P); }
@@ -115,7 +124,7 @@ int pyr_build(nvca_ctx *ctx, DetectJob &j, GeomPlan *pp, bool has_tilted)
         GeomPlan *gp = pp->level_tabs[li].get();
         uint8_t *lg = ws.ln().aux.as<uint8_t>() + L.gray_off;
         { TimedLaunch t(ctx, NVCA_K_RESIZE1);               // cvResize(img, &img1, CV_INTER_LINEAR)
-          launch_resize1(ctx->cs(), src0, cols, rows, spitch0, gp->view(), lg, L.szw, L.szh, L.gpitch, nullptr, nimg, sslot0, gray_total); }
+          launch_resize1(ctx->cs(), src.img, cols, rows, src.pitch, gp->view(), lg, L.szw, L.szh, L.gpitch, nullptr, nimg, src.slot, gray_total, src.luts); }
         PreGeom g; make_geom(g, L.szw, L.szh, L.gpitch, 1, L.szw, L.szh);
         g.gpitch = L.gpitch; g.spitch = P; g.sum_slot = plane_total; g.gray_slot = gray_total;
         run_integral(ctx, g, nullptr, nimg, lg, ws.ln().sum.as<int>() + L.plane_off,

@@ -381,7 +381,7 @@ static void face_lazy_init(NvcaFace *f)
     nvca_ctx *ctx = f->slot->ctx;
     if (!ctx) return;
     if (!need_cascade(f->slot, "haarcascade_frontalface_alt.xml", &f->cascade)) return;
-    if (nvca_face_stream_create(ctx, f->cascade, &f->p, &f->stream) != NVCA_OK) f->stream = nullptr;
+    if (nvca_face_stream_create_any(ctx, f->cascade, &f->p, &f->stream) != NVCA_OK) f->stream = nullptr;
 }
 
 static GstFlowReturn nvca_face_transform_frame_ip(GstVideoFilter *filter, GstVideoFrame *frame)

@@ -89,7 +89,7 @@ SYMBOLS = [
     "nvca_cascade_free", "nvca_cascade_info", "nvca_cascade_dump", "nvca_bgr2gray", "nvca_resize_linear",
     "nvca_equalize_hist", "nvca_integral", "nvca_detect_multiscale", "nvca_detect_raw", "nvca_group_rectangles",
     "nvca_detect_multiscale_batch", "nvca_detect_raw_batch",
-    "nvca_face_params_default", "nvca_face_stream_create", "nvca_face_stream_destroy",
+    "nvca_face_params_default", "nvca_face_stream_create", "nvca_face_stream_create_any", "nvca_face_stream_destroy",
     "nvca_face_stream_set_params", "nvca_face_stream_motion_event", "nvca_face_stream_process",
     "nvca_face_batch_process", "nvca_tracker_params_default", "nvca_tracker_create", "nvca_tracker_destroy",
     "nvca_tracker_set_params", "nvca_tracker_process", "nvca_tracker_batch_process", "nvca_flip_horizontal",
@@ -185,6 +185,7 @@ def load():
     L.nvca_face_params_default.argtypes = [C.POINTER(FaceParams)]
     L.nvca_face_params_default.restype = None
     L.nvca_face_stream_create.argtypes = [vp, vp, C.POINTER(FaceParams), C.POINTER(vp)]
+    L.nvca_face_stream_create_any.argtypes = [vp, vp, C.POINTER(FaceParams), C.POINTER(vp)]
     L.nvca_face_stream_destroy.argtypes = [vp]
     L.nvca_face_stream_destroy.restype = None
     L.nvca_face_stream_set_params.argtypes = [vp, C.POINTER(FaceParams)]
@@ -667,14 +668,16 @@ class FaceStream:
              "euclidean_distance": "euclidean_threshold", "area_threshold": "area_threshold",
              "min_neighbors": "min_neighbors", "detect_event": "detect_event"}
 
-    def __init__(self, ctx, cascade, **props):
+    def __init__(self, ctx, cascade, any_format=False, **props):
+        """any_format: made by nvca_face_stream_create_any, which takes a new-format LBP cascade as well"""
         self.ctx, self.cascade = ctx, cascade
         self.p = FaceParams()
         ctx.L.nvca_face_params_default(C.byref(self.p))
         for k, v in props.items():
             setattr(self.p, self.PROPS[k], int(v))
         h = C.c_void_p()
-        ctx.check(ctx.L.nvca_face_stream_create(ctx.h, cascade.h, C.byref(self.p), C.byref(h)))
+        create = ctx.L.nvca_face_stream_create_any if any_format else ctx.L.nvca_face_stream_create
+        ctx.check(create(ctx.h, cascade.h, C.byref(self.p), C.byref(h)))
         self.h = h
 
     def set_property(self, name, value):
