@@ -38,8 +38,8 @@ extern "C" {
                                     feature that leaves the image at some scale; a
                                     new-format cascade that is not LBP with stumps; an
                                     LBP cascade handed to nvca_face_stream_create or
-                                    to a part stream (nvca_face_stream_create_any
-                                    takes it)                                        */
+                                    nvca_part_stream_create (their _create_any forms
+                                    take it)                                         */
 #define NVCA_ERR_OVERFLOW   -7   /* more raw candidates than the context's cap     */
 #define NVCA_ERR_NOMEM      -8
 #define NVCA_ERR_INTERNAL   -9   /* an internal check failed (a device result out of range, an exception caught at the
@@ -165,10 +165,13 @@ const char *nvca_kernel_name(int k);
  *    with stump weak classifiers.  New-format HAAR and HOG cascades, stage types other than BOOST, trees
  *    (maxDepth > 1) and maxCatCount != 256 are refused with NVCA_ERR_UNSUPPORTED.
  * An LBP cascade goes through nvca_detect_multiscale / nvca_detect_raw on single images and through their _batch forms on
- * several, and through the face streams made with nvca_face_stream_create_any; nvca_face_stream_create and the part streams refuse
- * it (NVCA_ERR_UNSUPPORTED).  Its launches are booked under the existing timing slots: the evaluator's kernels under NVCA_K_STRIP
- * ("window per lane"), the level resize and integral under NVCA_K_RESIZE1 / NVCA_K_INTEGRAL as CV_HAAR_SCALE_IMAGE books them, a
- * face stream's grouping under NVCA_K_GROUP. */
+ * several, through the face streams made with nvca_face_stream_create_any and through the part streams made with
+ * nvca_part_stream_create_any, in any role; nvca_face_stream_create and nvca_part_stream_create refuse it (NVCA_ERR_UNSUPPORTED).
+ * Its launches are booked under the existing timing slots.  A single small image -- a part detector's face region, the 160-px
+ * face-pass image: whatever fits one workgroup's LDS -- is scanned by the round's one small-image launch, under NVCA_K_ROI
+ * (option "roi", as for old-format cascades).  Larger images and jobs of several images: the evaluator's kernels under NVCA_K_STRIP ("window per
+ * lane"), the level resize and integral under NVCA_K_RESIZE1 / NVCA_K_INTEGRAL as CV_HAAR_SCALE_IMAGE books them, a face stream's
+ * grouping under NVCA_K_GROUP. */
 #define NVCA_CASCADE_HAAR 0
 #define NVCA_CASCADE_LBP  1
 int  nvca_cascade_load_xml(nvca_ctx *ctx, const char *path, nvca_cascade **out);
@@ -408,6 +411,16 @@ void nvca_part_params_default(nvca_part_params *p, int kind);
  *   NOSE / MOUTH  a only (b may be NULL) */
 int  nvca_part_stream_create(nvca_ctx *ctx, const nvca_part_params *params, const nvca_cascade *face,
                              const nvca_cascade *a, const nvca_cascade *b, nvca_part_stream **out);
+/* The same stream on cascades of either format: each of face, a and b may be an old-format cascade or a new-format LBP cascade, in
+ * any mixture (opencv_traincascade -featureType LBP files, OpenCV's lbpcascade_profileface.xml).  Same arguments, same refusals; on
+ * three old-format cascades the stream is nvca_part_stream_create's.  A search on an LBP cascade is what
+ * cv::CascadeClassifier::detectMultiScale does with a new-format file behind it: the element's flags are ignored
+ * (CV_HAAR_FIND_BIGGEST_OBJECT and CV_HAAR_SCALE_IMAGE make no difference), the call's own scale factor, minNeighbors, minSize and
+ * maxSize apply, and the raw list is grouped with groupRectangles(max(minNeighbors, 1), 0.2).  Everything downstream (process, the
+ * batched call, submit / collect, set_input, set_params, push_faces, frames shared between streams) serves both; streams of either
+ * kind mix in one call, and their small searches share one launch per round. */
+int  nvca_part_stream_create_any(nvca_ctx *ctx, const nvca_part_params *params, const nvca_cascade *face,
+                                 const nvca_cascade *a, const nvca_cascade *b, nvca_part_stream **out);
 void nvca_part_stream_destroy(nvca_part_stream *s);
 int  nvca_part_stream_set_params(nvca_part_stream *s, const nvca_part_params *params);
 /* The pixel format of the stream's frames, as nvca_face_stream_set_input: NV12 / I420 frames are converted where the working-image

@@ -71,6 +71,7 @@ static int detect_gray_batch(nvca_ctx *ctx, const nvca_cascade *casc, int n, con
             jobs.emplace_back(new DetectJob());
             const int rc = make_detect_job(ctx, *jobs.back(), casc, gray[i], w, h, stride, mem, sf, min_neighbors, flags, minw, minh, maxw, maxh, raw_only);
             if (rc) return rc;
+            jobs.back()->rq.image_axis = true;             // (a batch's launch set does not depend on how many images its last job holds)
             jp.push_back(jobs.back().get());
         }
     }

@@ -282,4 +282,25 @@ struct RoiJobDev {
 };
 static constexpr int kRoiMaxWin = 2048;           // windows of one ladder step / pyramid level of a small-image job
 
+// ---- detectMultiScale of a new-format LBP cascade on a small image in one workgroup (kernels_roi_lbp.hip).  A job is a RoiJobDev
+// (scale_image == 2; `stages` points at the cascade's RoiLbp table: nstages LbpStageDev, then -- at roi_lbp_weak_off(nstages) bytes --
+// its weak classifiers), a level or a band of a level's rows a RoiStep as CV_HAAR_SCALE_IMAGE's (trecs, the variance rectangle and
+// adaptive unused).  The level's plane lives in LDS at its own pitch, so a weak classifier keeps its feature rectangle and the kernel
+// forms the sixteen corner offsets: (y + r h) * pitch + x + c w.
+struct RoiLbpWeak { int x, y, w, h; int subset[8]; float leaf[2]; int pad[2]; };
+static_assert(sizeof(RoiLbpWeak) == 64, "RoiLbpWeak is fetched with one wide scalar load");
+NVCA_HD inline size_t roi_lbp_weak_off(int nstages) { return ((size_t)nstages * sizeof(LbpStageDev) + 63) & ~(size_t)63; }
+// A stage on a short queue: at most kRoiLbpShortWin windows and at most kRoiLbpVoteWords votes (weak classifiers x windows padded to
+// whole waves) run a wave per (weak classifier, 64 windows), every vote stored to LDS, and one lane per window adds the stage's votes in
+// file order -- the same f32 additions as a window per lane.  0 switches the form off.
+#ifndef NVCA_ROI_LBP_SHORT_WIN
+#define NVCA_ROI_LBP_SHORT_WIN 256
+#endif
+static constexpr int kRoiLbpShortWin = NVCA_ROI_LBP_SHORT_WIN;
+static constexpr int kRoiLbpVoteWords = 4096;
+// k_roi_lbp's dynamic LDS (host sizing and kernel carve-up agree through this): sum plane | two queues | counters | votes | level image,
+// every part a multiple of 16 bytes
+NVCA_HD constexpr int roi_lbp_fixed_bytes() { return 2 * kRoiMaxWin * 2 + 16 + kRoiLbpVoteWords * 4; }
+NVCA_HD constexpr int roi_lbp_lds_bytes(int plane_words, int lev_bytes) { return ((plane_words + 3) & ~3) * 4 + roi_lbp_fixed_bytes() + ((lev_bytes + 15) & ~15); }
+
 } // namespace nvca

@@ -168,7 +168,7 @@ bool frames_aligned4(const nvca_frame *frames, const int *idx, int n);
 bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l);
 
 // ---- detectMultiScale jobs (detect_job.cpp, detect_rounds.cpp) and their small-image batches (roi_batch.cpp)
-enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2, kJobLbp = 3 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT, a new-format LBP cascade (whatever the flags)
+enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2, kJobLbp = 3, kJobKinds = 4 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT, a new-format LBP cascade (whatever the flags)
 enum JobPhase { kJobNew = 0, kJobFirstQueued = 1, kJobNarrowedQueued = 2, kJobDone = 3 };      // (narrowed: the second set of a FIND_BIGGEST search)
 
 struct DetectJob {
@@ -179,6 +179,7 @@ struct DetectJob {
         int cols = 0, rows = 0, stride = 0, mem = 0;
         double sf = 1.1; int min_neighbors = 0, flags = 0, minw = 0, minh = 0, maxw = 0, maxh = 0;
         bool raw_only = false;
+        bool image_axis = false;                             // a job of the _batch entry points on an LBP cascade: its images, however many, share the large-image evaluator's launches
     } rq;
     std::vector<nvca_rect> out[kJobImages];          // the result, per image
     // progress of the queued launch set
@@ -209,16 +210,17 @@ struct DetectJob {
 };
 
 struct RoiBatch {
-    std::vector<RoiJobDev> jobs; std::vector<RoiStep> steps; std::vector<unsigned char> tabs; std::vector<DetectJob *> owners; std::vector<int> owner_img;
+    std::vector<RoiJobDev> jobs; std::vector<RoiStep> steps, lbp_steps /* k_roi_lbp's: the LBP jobs' */; std::vector<unsigned char> tabs; std::vector<DetectJob *> owners; std::vector<int> owner_img;
     std::vector<ScaleTable *> held;                 // stump tables of the launch: kept from eviction until it has been collected
     int plane_words = 0, lev_bytes = 0, lane = 0; unsigned cap = 0; size_t first = 0;
+    int lbp_plane_words = 0, lbp_lev_bytes = 0;     // k_roi_lbp's LDS: the largest level's sum plane (words, a multiple of 4) and resized level (bytes)
     size_t rej_words = 0;                           // stage-0 reject bitmaps of the launch's dense steps (u64 words)
     void release() { for (ScaleTable *t : held) if (t->refs > 0) t->refs--; held.clear(); }
     ~RoiBatch() { release(); }
     RoiBatch() = default;
     RoiBatch(const RoiBatch &) = delete; RoiBatch &operator=(const RoiBatch &) = delete;
     // (a round object is reused from round to round: what the previous round held is released first)
-    void reset() { release(); jobs.clear(); steps.clear(); tabs.clear(); owners.clear(); owner_img.clear(); plane_words = 0; lev_bytes = 0; lane = 0; cap = 0; first = 0; rej_words = 0; }
+    void reset() { release(); jobs.clear(); steps.clear(); lbp_steps.clear(); tabs.clear(); owners.clear(); owner_img.clear(); plane_words = 0; lev_bytes = 0; lbp_plane_words = 0; lbp_lev_bytes = 0; lane = 0; cap = 0; first = 0; rej_words = 0; }
 };
 
 // ---- roi_batch.cpp

@@ -140,5 +140,9 @@ void launch_roi(hipStream_t st, const RoiJobDev *jobs, int nsteps, const RoiStep
 void roi_stamps_dump(const char *path);     // diagnostic build: k_roi's phase sums as text
 #endif
 int roi_grant_lds(int bytes);     // dynamic LDS above 64 KiB is granted per function and device (monotonic, process-wide); returns a hipError_t as int
+// ---- ... of a new-format LBP cascade (kernels_roi_lbp.hip): the same job table, candidate list and key as k_roi, its own step records
+void launch_roi_lbp(hipStream_t st, const RoiJobDev *jobs, int nsteps, const RoiStep *steps, const unsigned char *tabs, unsigned long long *hits,
+                    unsigned hit_cap, int plane_words, int lds_bytes);
+int roi_lbp_grant_lds(int bytes);
 
 } // namespace nvca

@@ -16,11 +16,11 @@ void PartStats::report()
     clear_rounds();
 }
 
-void PartStats::report_round(size_t images, const int kinds[3], int narrowed, size_t workgroups, double waited_s)
+void PartStats::report_round(size_t images, const int kinds[4], int narrowed, size_t workgroups, double waited_s)
 {
     if (++rounds <= 200 || rounds > 212) return;
-    fprintf(stderr, "[nvca jobs] small-image round: %zu images (plain %d, scale-image %d, biggest-object %d of which narrowed %d), %zu workgroups, waited %.0f us\n",
-            images, kinds[0], kinds[1], kinds[2], narrowed, workgroups, waited_s * 1e6);
+    fprintf(stderr, "[nvca jobs] small-image round: %zu images (plain %d, scale-image %d, biggest-object %d of which narrowed %d, LBP %d), %zu workgroups, waited %.0f us\n",
+            images, kinds[0], kinds[1], kinds[2], narrowed, kinds[3], workgroups, waited_s * 1e6);
 }
 
 } // namespace nvca

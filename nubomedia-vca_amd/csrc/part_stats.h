@@ -27,7 +27,7 @@ struct PartStats {
     void clear_rounds() { enqueue = wait = advance = add_jobs = small_jobs = launch = collect = advance_helpers = advance_serial = 0; }
     void report();                                   // a part batch was timed: every 8th prints the two report lines and starts over
     // a small-image round was waited for: rounds 201 .. 212 (a dozen of the steady state) print what the round held
-    void report_round(size_t images, const int kinds[3], int narrowed, size_t workgroups, double waited_s);
+    void report_round(size_t images, const int kinds[4] /* by JobKind */, int narrowed, size_t workgroups, double waited_s);
 };
 
 } // namespace nvca

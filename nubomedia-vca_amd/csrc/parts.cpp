@@ -32,6 +32,24 @@ int part_call_slot(nvca_ctx *ctx)
 }
 } // namespace
 
+namespace {
+// what both create calls check and make; any_format: a role may be a new-format LBP cascade
+int part_stream_make(nvca_ctx *ctx, const nvca_part_params *params, const nvca_cascade *face, const nvca_cascade *a, const nvca_cascade *b,
+                     bool any_format, nvca_part_stream **out)
+{
+    if (!ctx || !params || !face || !a || !out || params->kind < NVCA_PART_EYE || params->kind > NVCA_PART_EAR) return NVCA_ERR_ARG;
+    if ((params->kind == NVCA_PART_EYE || params->kind == NVCA_PART_EAR) && !b) return NVCA_ERR_ARG;
+    if (!any_format && (face->format != NVCA_CASCADE_HAAR || a->format != NVCA_CASCADE_HAAR || (b && b->format != NVCA_CASCADE_HAAR))) {
+        ctx->set_error("nvca_part_stream_create does not take an LBP cascade in any role (nvca_part_stream_create_any does)"); return NVCA_ERR_UNSUPPORTED;
+    }
+    nvca_part_stream *s = new (std::nothrow) nvca_part_stream();
+    if (!s) return NVCA_ERR_NOMEM;
+    s->ctx = ctx; s->p = *params; s->face = face; s->a = a; s->b = b;
+    *out = s;
+    return NVCA_OK;
+}
+} // namespace
+
 extern "C" {
 
 void nvca_part_params_default(nvca_part_params *p, int kind)
@@ -44,16 +62,13 @@ NVCA_API_CATCH_VOID
 int nvca_part_stream_create(nvca_ctx *ctx, const nvca_part_params *params, const nvca_cascade *face, const nvca_cascade *a,
                             const nvca_cascade *b, nvca_part_stream **out)
 try {
-    if (!ctx || !params || !face || !a || !out || params->kind < NVCA_PART_EYE || params->kind > NVCA_PART_EAR) return NVCA_ERR_ARG;
-    if ((params->kind == NVCA_PART_EYE || params->kind == NVCA_PART_EAR) && !b) return NVCA_ERR_ARG;
-    if (face->format != NVCA_CASCADE_HAAR || a->format != NVCA_CASCADE_HAAR || (b && b->format != NVCA_CASCADE_HAAR)) {
-        ctx->set_error("part streams do not take an LBP cascade in any role (nvca_detect_multiscale does)"); return NVCA_ERR_UNSUPPORTED;
-    }
-    nvca_part_stream *s = new (std::nothrow) nvca_part_stream();
-    if (!s) return NVCA_ERR_NOMEM;
-    s->ctx = ctx; s->p = *params; s->face = face; s->a = a; s->b = b;
-    *out = s;
-    return NVCA_OK;
+    return part_stream_make(ctx, params, face, a, b, false, out);
+}
+NVCA_API_CATCH(ctx)
+int nvca_part_stream_create_any(nvca_ctx *ctx, const nvca_part_params *params, const nvca_cascade *face, const nvca_cascade *a,
+                                const nvca_cascade *b, nvca_part_stream **out)
+try {
+    return part_stream_make(ctx, params, face, a, b, true, out);
 }
 NVCA_API_CATCH(ctx)
 void nvca_part_stream_destroy(nvca_part_stream *s)

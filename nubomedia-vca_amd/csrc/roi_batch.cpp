@@ -1,6 +1,8 @@
-// roi_batch.cpp -- the small-image path of detectMultiScale: every small job of a round in one k_roi launch (kernels_roi.hip),
-// and its candidates handed back to the jobs.
+// roi_batch.cpp -- the small-image path of detectMultiScale: every small job of a round in one k_roi launch (kernels_roi.hip) --
+// the jobs on new-format LBP cascades in one k_roi_lbp launch beside it (kernels_roi_lbp.hip) --, and their candidates handed
+// back to the jobs.
 #include "host_state.h"
+#include "lbp_roi_tables.h"
 #include <cstring>
 #include <algorithm>
 
@@ -16,8 +18,15 @@ namespace nvca {
 static constexpr int kRoiMaxWords = 14848;          // (cols + 1) * (rows + 2) words per plane: the part detectors' 160 x 90 face-pass image still fits (two planes + queues + a level image = 157 KB of the 160 KB of LDS)
 bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round)
 {
+    if (!ctx->sw.roi) return false;
+    if (j.rq.kind == kJobLbp) {
+        // a new-format LBP cascade (its Haar model is empty): ONE image whose working set fits k_roi_lbp's LDS (kRoiLbpMaxBytes,
+        // lbp_roi_tables.h); a job of several images, and every job of the _batch entry points, keeps the image axis of the
+        // large-image evaluator
+        if (j.rq.nimg != 1 || j.rq.image_axis || !lbp_roi_fits_lds(j.rq.cols, j.rq.rows)) return false;
+        return j.rq.mem == NVCA_MEM_DEVICE || njobs_in_round == 1;              // a host image is staged in the lane's one gray buffer
+    }
     const Cascade &c = j.rq.casc->c;
-    if (!ctx->sw.roi || j.rq.kind == kJobLbp) return false;
     if (!c.stump_based || c.has_tilted || (j.rq.nimg != 1 && j.rq.mem != NVCA_MEM_DEVICE)) return false;
     if ((long long)(j.rq.cols + 1) * (j.rq.rows + 2) > kRoiMaxWords || j.rq.cols < 1 || j.rq.rows < 1) return false;
     if (j.rq.mem != NVCA_MEM_DEVICE && njobs_in_round != 1) return false;       // a host image is staged in the lane's one gray buffer
@@ -34,6 +43,20 @@ static const StageRec *roi_stage_recs(nvca_ctx *ctx, const Cascade &c)
     }
     const StageRec *p = d->as<StageRec>();
     ctx->roi_stage_recs[c.uid] = d.release();
+    return p;
+}
+// the cascade's table for k_roi_lbp (lbp_roi_tables.cpp), cached per context and cascade beside the Haar cascades' stage records
+static const StageRec *roi_lbp_recs(nvca_ctx *ctx, const nvca_cascade *casc)
+{
+    auto it = ctx->roi_stage_recs.find(casc->c.uid);
+    if (it != ctx->roi_stage_recs.end()) return it->second->as<StageRec>();
+    std::vector<unsigned char> blob; build_lbp_roi_table(casc->lbp, blob);
+    std::unique_ptr<DevBuf> d(new DevBuf());
+    if (d->ensure(blob.size()) || hipMemcpy(d->p, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        d->release(); ctx->set_error("allocation failed (LBP cascade records)"); return nullptr;
+    }
+    const StageRec *p = d->as<StageRec>();
+    ctx->roi_stage_recs[casc->c.uid] = d.release();
     return p;
 }
 static ScaleTable *roi_table(nvca_ctx *ctx, RoiBatch &rb, const Cascade &c, double factor)
@@ -54,15 +77,26 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
     const Cascade &c = j.rq.casc->c;
     const int cols = j.rq.cols, rows = j.rq.rows;
     j.sm.fused = false;
-    const StageRec *d_stages = roi_stage_recs(ctx, c);
+    const bool lbp = j.rq.kind == kJobLbp;
+    const StageRec *d_stages = lbp ? roi_lbp_recs(ctx, j.rq.casc) : roi_stage_recs(ctx, c);
     if (!d_stages) return NVCA_ERR_NOMEM;
     std::vector<RoiStep> steps; std::vector<DetectJob::RoiStepInfo> info; std::vector<unsigned char> tabs;
     const size_t tab0 = rb.tabs.size();
-    int lev_bytes = 0;
+    int lev_bytes = 0, lbp_plane_words = 0;
+    bool fits = true;
     const bool dense = j.rq.kind == kJobBiggest && j.q.phase == kJobNew && ctx->sw.fb_dense && j.rq.nimg == 1;
     std::vector<DetectJob::RejInfo> rej; size_t rej_local = 0;
     if (j.q.phase == kJobNew) for (int k = 0; k < kJobImages; k++) j.out[k].clear();
-    if (j.rq.kind == kJobScaleImage) {
+    if (lbp) {
+        // the levels of detectMultiScale on a new-format cascade, each with its cv::resize tables (lbp_roi_tables.cpp); a candidate maps
+        // to its rectangle as a CV_HAAR_SCALE_IMAGE level's does: (cvRound(x f), cvRound(y f), cvRound(ow f), cvRound(oh f))
+        LbpRoiSteps ls;
+        build_lbp_roi_steps(j.rq.casc->lbp, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, tab0, ls);
+        fits = ls.fits;
+        steps.swap(ls.steps); tabs.swap(ls.tabs); lev_bytes = ls.lev_bytes; lbp_plane_words = ls.plane_words;
+        for (const LbpRoiLevel &l : ls.info) info.push_back(DetectJob::RoiStepInfo{0., l.factor, l.winw, l.winh, -1});
+        j.q.phase = kJobFirstQueued;
+    } else if (j.rq.kind == kJobScaleImage) {
         // the pyramid levels of si_plan, each with its cv::resize tables.  (No cap on their number here: with more of them than the key
         // holds the job takes the large-image path, below)
         ScaleTable *t1 = nullptr;
@@ -118,30 +152,11 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
             steps.push_back(st); info.push_back(DetectJob::RoiStepInfo{fs.ystep, 0., fs.winw, fs.winh, li});
         }
     }
-    bool fits = steps.size() <= 63;                                  // the key holds 6 bits of step
-    {
-        // A step's rows are independent of one another (the adaptive x step works row by row, a pyramid level's grid is fixed):
-        // a step with more windows than the queues hold goes out as several records, a band of whole rows each -- one workgroup
-        // per band instead of one per step walking its bands one after the other (the largest pyramid level of a 160 x 90 face
-        // pass is 10 k windows: alone it set the length of the whole launch).  Every band builds the integral pair for itself.
-        std::vector<RoiStep> bands;
-        for (size_t li = 0; li < steps.size(); li++) {
-            RoiStep st = steps[li];
-            const int nx = (st.endX - st.startX + st.step - 1) / st.step, ny = (st.endY - st.startY + st.step - 1) / st.step;
-            if (nx > kRoiMaxWin) fits = false;                       // (a grid row longer than the queues: not with images this small)
-            st.key_step = (int)li;
-            st.key_x0 = st.startX; st.key_dx = st.step; st.key_dy = st.step;
-            const int rows_per = nx > 0 && nx < kRoiMaxWin ? kRoiMaxWin / nx : 1;
-            for (int gy0 = 0; gy0 < std::max(ny, 1); gy0 += rows_per) {
-                RoiStep b = st;
-                b.startY = st.startY + gy0 * st.step;
-                b.endY = std::min(st.endY, st.startY + (gy0 + rows_per) * st.step);
-                b.key_y0 = b.startY;
-                bands.push_back(b);
-            }
-        }
-        steps.swap(bands);
-    }
+    // the key holds 6 bits of step; a step with more windows than the queues hold goes out as bands of whole rows, one workgroup per
+    // band instead of one per step walking its bands one after the other (the largest pyramid level of a 160 x 90 face pass is 10 k
+    // windows: alone it set the length of the whole launch).  Every band builds the integral planes for itself.
+    fits = fits && steps.size() <= 63;
+    if (!roi_split_bands(steps)) fits = false;
     if (!fits && j.sm.roi_prev_phase == kJobNarrowedQueued) { ctx->set_error("internal: a narrowed search outgrew the small-image path"); return NVCA_ERR_INTERNAL; }   // (its full grids fitted)
     if (!fits) { j.q.phase = (JobPhase)j.sm.roi_prev_phase; return NVCA_OK; }       // this one takes the large-image path
     j.sm.fused = true; j.sm.rinfo.swap(info); j.q.dp = nullptr;
@@ -160,22 +175,24 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
             if ((rc = stage_2d(ctx, ctx->ws->ln().gray.p, g.gpitch, j.rq.img[0], j.rq.stride, cols, rows, j.rq.mem))) return rc;
             d.img = ctx->ws->ln().gray.as<uint8_t>(); d.stride = g.gpitch;
         }
-        d.first_step = (int)rb.steps.size(); d.nsteps = (int)steps.size(); d.scale_image = j.rq.kind == kJobScaleImage;
-        d.stages = d_stages; d.nstages = (int)c.stages.size(); d.pair_policy = ctx->policy == NVCA_SUM_F32PAIR; d.slot = (int)rb.jobs.size();
+        std::vector<RoiStep> &all = lbp ? rb.lbp_steps : rb.steps;        // (k_roi_lbp's records apart: each kernel is launched on its own)
+        d.first_step = (int)all.size(); d.nsteps = (int)steps.size(); d.scale_image = lbp ? 2 : j.rq.kind == kJobScaleImage;
+        d.stages = d_stages; d.nstages = lbp ? (int)j.rq.casc->lbp.stages.size() : (int)c.stages.size(); d.pair_policy = ctx->policy == NVCA_SUM_F32PAIR; d.slot = (int)rb.jobs.size();
         for (RoiStep &st : steps) st.job = d.slot;
-        rb.steps.insert(rb.steps.end(), steps.begin(), steps.end());
+        all.insert(all.end(), steps.begin(), steps.end());
         rb.jobs.push_back(d); rb.owners.push_back(&j); rb.owner_img.push_back(k);
     }
-    rb.plane_words = std::max(rb.plane_words, (cols + 1) * (rows + 2));
-    rb.lev_bytes = std::max(rb.lev_bytes, lev_bytes);
+    if (lbp) { rb.lbp_plane_words = std::max(rb.lbp_plane_words, (lbp_plane_words + 3) & ~3); rb.lbp_lev_bytes = std::max(rb.lbp_lev_bytes, lev_bytes); }
+    else { rb.plane_words = std::max(rb.plane_words, (cols + 1) * (rows + 2)); rb.lev_bytes = std::max(rb.lev_bytes, lev_bytes); }
     return NVCA_OK;
 }
-// upload the round's tables and launch k_roi on the current lane
+// upload the round's tables and launch k_roi (the Haar jobs' steps) and k_roi_lbp (the LBP jobs') on the current lane
 int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap)
 {
     const int nj = (int)rb.jobs.size();
-    const size_t jb = (size_t)nj * sizeof(RoiJobDev), sb = rb.steps.size() * sizeof(RoiStep);
-    const size_t o_steps = (jb + 255) & ~(size_t)255, o_tabs = (o_steps + sb + 255) & ~(size_t)255, total = o_tabs + rb.tabs.size() + 64;
+    const size_t jb = (size_t)nj * sizeof(RoiJobDev), sb = rb.steps.size() * sizeof(RoiStep), lb = rb.lbp_steps.size() * sizeof(RoiStep);
+    const size_t o_steps = (jb + 255) & ~(size_t)255, o_lsteps = (o_steps + sb + 255) & ~(size_t)255, o_tabs = (o_lsteps + lb + 255) & ~(size_t)255,
+                 total = o_tabs + rb.tabs.size() + 64;
     // the list starts at a quarter of a million candidates for the whole launch however many jobs share it; a launch that
     // overflows it is queued again with the exact size (run_detect_jobs raises hit_cap for the rest of the call)
     const long long want = (long long)ctx->hit_cap * nj;
@@ -187,16 +204,23 @@ int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap)
         ctx->set_error("allocation failed (small-image detector)"); return NVCA_ERR_NOMEM;
     }
     unsigned char *h = ctx->rbuf().h_tables.as<unsigned char>();
-    memcpy(h, rb.jobs.data(), jb); memcpy(h + o_steps, rb.steps.data(), sb);
+    memcpy(h, rb.jobs.data(), jb);
+    if (sb) memcpy(h + o_steps, rb.steps.data(), sb);
+    if (lb) memcpy(h + o_lsteps, rb.lbp_steps.data(), lb);
     if (!rb.tabs.empty()) memcpy(h + o_tabs, rb.tabs.data(), rb.tabs.size());
     NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().tables.p, h, total - 64, hipMemcpyHostToDevice, ctx->cs()));
     NVCA_HIP_CHECK(ctx, hipMemsetAsync(ctx->rbuf().hits.p, 0, sizeof(unsigned long long), ctx->cs()));
     const int lds = rb.plane_words * 8 + kRoiMaxWin * (8 + 2 + 2) + 16 + ((rb.lev_bytes + 15) & ~15) + 64;      // k_roi's carve-up
-    if (const int e = roi_grant_lds(lds)) { ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e)); return NVCA_ERR_HIP; }
+    const int lbp_lds = roi_lbp_lds_bytes(rb.lbp_plane_words, rb.lbp_lev_bytes);                                 // k_roi_lbp's
+    if (const int e = sb ? roi_grant_lds(lds) : 0) { ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e)); return NVCA_ERR_HIP; }
+    if (const int e = lb ? roi_lbp_grant_lds(lbp_lds) : 0) { ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e)); return NVCA_ERR_HIP; }
     const unsigned char *d = ctx->rbuf().tables.as<unsigned char>();
+    // the Haar jobs' steps and the LBP jobs' steps: two kernels on one lane, one job table, one candidate list, one wait
     { TimedLaunch t(ctx, NVCA_K_ROI);
-      launch_roi(ctx->cs(), (const RoiJobDev *)d, (int)rb.steps.size(), (const RoiStep *)(d + o_steps), d + o_tabs, ctx->rbuf().hits.as<unsigned long long>(), rb.cap, rb.plane_words, lds,
-                 ctx->rbuf().rej.as<unsigned long long>()); }
+      if (sb) launch_roi(ctx->cs(), (const RoiJobDev *)d, (int)rb.steps.size(), (const RoiStep *)(d + o_steps), d + o_tabs, ctx->rbuf().hits.as<unsigned long long>(), rb.cap, rb.plane_words, lds,
+                 ctx->rbuf().rej.as<unsigned long long>());
+      if (lb) launch_roi_lbp(ctx->cs(), (const RoiJobDev *)d, (int)rb.lbp_steps.size(), (const RoiStep *)(d + o_lsteps), d + o_tabs, ctx->rbuf().hits.as<unsigned long long>(), rb.cap,
+                             rb.lbp_plane_words, lbp_lds); }
     if (rb.rej_words) NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().h_rej.p, ctx->rbuf().rej.p, rb.rej_words * 8, hipMemcpyDeviceToHost, ctx->cs()));
     NVCA_LAUNCH_CHECK(ctx);
     NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().h_hits.p, ctx->rbuf().hits.p, (first + 1) * 8, hipMemcpyDeviceToHost, ctx->cs()));

@@ -27,7 +27,7 @@ struct Switches {
     int  trk_order = -1;             // NVCA_TRK_ORDER: visiting order of k_ccl_reduce (default -1: decided per frame on the device)
     int  host_threads = -1;          // NVCA_HOST_THREADS=n: helper threads for per-job host work, 0: none (default -1: min(8, cores / 2) - 1)
     bool fb_dense = true;            // NVCA_FB_DENSE=0: a FIND_BIGGEST search on the small-image path re-scans its narrowed grids in a second launch instead of replaying them on the host from the first launch's dense candidates + stage-0 reject bits (default 1)
-    bool roi = true;                 // NVCA_ROI=0: small images take the large-image path too (plan + four launches per job) (default 1)
+    bool roi = true;                 // NVCA_ROI=0: small images take the large-image path too (plan + four launches per job; on a new-format LBP cascade plan, pyramid and a dozen launches) (default 1)
     bool stage_order = false;        // NVCA_STAGE_ORDER=1: the tile kernels walk the early stages 1 .. 5 in the order the previous tile of the band found cheapest (cost per window killed) instead of the cascade's own; the set of survivors is the same (default 0)
     int  pair_max = 32;              // NVCA_PAIR_MAX=n (<= 32): windows up to which a round of the tile kernels runs lane = (window, stump) instead of a window per lane (default 32)
     int  spec_pairs = 1536;          // NVCA_SPEC_PAIRS=n: with at most 32 windows left a round takes as many stages as stay within n (window, stump) pairs, 512 being one step of the workgroup (default 1536)

@@ -630,7 +630,7 @@ static void part_lazy_init(NvcaPart *f)
     if (!ctx) return;
     const PartDesc *d = f->desc;
     if (!need_cascade(f->slot, d->face_file, &f->cf) || !need_cascade(f->slot, d->a_file, &f->ca) || !need_cascade(f->slot, d->b_file, &f->cb)) return;
-    if (nvca_part_stream_create(ctx, &f->p, f->cf, f->ca, f->cb, &f->stream) != NVCA_OK) f->stream = nullptr;
+    if (nvca_part_stream_create_any(ctx, &f->p, f->cf, f->ca, f->cb, &f->stream) != NVCA_OK) f->stream = nullptr;
 }
 
 // faces handed over by an upstream element (message_faces)

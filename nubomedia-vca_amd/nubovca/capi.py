@@ -93,7 +93,7 @@ SYMBOLS = [
     "nvca_face_stream_set_params", "nvca_face_stream_motion_event", "nvca_face_stream_process",
     "nvca_face_batch_process", "nvca_tracker_params_default", "nvca_tracker_create", "nvca_tracker_destroy",
     "nvca_tracker_set_params", "nvca_tracker_process", "nvca_tracker_batch_process", "nvca_flip_horizontal",
-    "nvca_part_params_default", "nvca_part_stream_create", "nvca_part_stream_destroy", "nvca_part_stream_set_params",
+    "nvca_part_params_default", "nvca_part_stream_create", "nvca_part_stream_create_any", "nvca_part_stream_destroy", "nvca_part_stream_set_params",
     "nvca_part_stream_push_faces", "nvca_part_stream_process", "nvca_part_stream_faces",
     "nvca_host_register", "nvca_host_unregister", "nvca_face_batch_submit", "nvca_face_batch_collect",
     "nvca_integral_tilted", "nvca_cascade_kind", "nvca_part_batch_process", "nvca_device_count", "nvca_draw_shapes",
@@ -214,6 +214,8 @@ def load():
     L.nvca_part_params_default.argtypes = [C.POINTER(PartParams), C.c_int]
     L.nvca_part_params_default.restype = None
     L.nvca_part_stream_create.argtypes = [vp, C.POINTER(PartParams), vp, vp, vp, C.POINTER(vp)]
+    if hasattr(L, "nvca_part_stream_create_any"):      # (NVCA_LIB may name an older library: A/B runs against a parent commit)
+        L.nvca_part_stream_create_any.argtypes = [vp, C.POINTER(PartParams), vp, vp, vp, C.POINTER(vp)]
     L.nvca_part_stream_destroy.argtypes = [vp]
     L.nvca_part_stream_destroy.restype = None
     L.nvca_part_stream_set_params.argtypes = [vp, C.POINTER(PartParams)]
@@ -851,14 +853,16 @@ class PartStream:
     PROPS = {"width_to_process": "width_to_process", "process_x_every_4_frames": "process_x_every_4",
              "multi_scale_factor": "scale_factor_pct", "detect_event": "detect_event"}
 
-    def __init__(self, ctx, kind, face, a, b=None, **props):
+    def __init__(self, ctx, kind, face, a, b=None, any_format=False, **props):
+        """any_format: made by nvca_part_stream_create_any, which takes a new-format LBP cascade in any role"""
         self.ctx = ctx
         self.p = PartParams()
         ctx.L.nvca_part_params_default(C.byref(self.p), kind)
         for k, v in props.items():
             setattr(self.p, self.PROPS[k], int(v))
         h = C.c_void_p()
-        ctx.check(ctx.L.nvca_part_stream_create(ctx.h, C.byref(self.p), face.h, a.h, b.h if b is not None else None, C.byref(h)))
+        create = ctx.L.nvca_part_stream_create_any if any_format else ctx.L.nvca_part_stream_create
+        ctx.check(create(ctx.h, C.byref(self.p), face.h, a.h, b.h if b is not None else None, C.byref(h)))
         self.h = h
         self._keep = (face, a, b)
 
