@@ -161,19 +161,24 @@ const char *nvca_kernel_name(int k);
  * of <opencv_storage>:
  *  - old format ("opencv-haar-classifier"): stump or tree-structured weak classifiers, upright or tilted features (cascades
  *    with trees / tilted features run through the general evaluator);
- *  - new format ("opencv-cascade-classifier", what opencv_traincascade writes and OpenCV's lbpcascades/ hold): featureType LBP
- *    with stump weak classifiers.  New-format HAAR and HOG cascades, stage types other than BOOST, trees
- *    (maxDepth > 1) and maxCatCount != 256 are refused with NVCA_ERR_UNSUPPORTED.
- * An LBP cascade goes through nvca_detect_multiscale / nvca_detect_raw on single images and through their _batch forms on
- * several, through the face streams made with nvca_face_stream_create_any and through the part streams made with
- * nvca_part_stream_create_any, in any role; nvca_face_stream_create and nvca_part_stream_create refuse it (NVCA_ERR_UNSUPPORTED).
- * Its launches are booked under the existing timing slots.  A single small image -- a part detector's face region, the 160-px
- * face-pass image: whatever fits one workgroup's LDS -- is scanned by the round's one small-image launch, under NVCA_K_ROI
- * (option "roi", as for old-format cascades).  Larger images and jobs of several images: the evaluator's kernels under NVCA_K_STRIP ("window per
+ *  - new format ("opencv-cascade-classifier", what opencv_traincascade writes and what OpenCV 3 / 4 install as haarcascades/ and
+ *    lbpcascades/): featureType LBP or HAAR (cascadedetect.cpp's HaarEvaluator, which is NOT the
+ *    old format's arithmetic), stump weak classifiers.  Refused with NVCA_ERR_UNSUPPORTED: featureType HOG, stage types other than
+ *    BOOST, trees (maxDepth > 1 or more than one internal node), tilted HAAR features, and a maxCatCount that does not fit the
+ *    feature type (256 for LBP, 0 for HAAR).
+ * A new-format cascade of either feature type goes through nvca_detect_multiscale / nvca_detect_raw on single images and through
+ * their _batch forms on several, through the face streams made with nvca_face_stream_create_any and through the part streams made
+ * with nvca_part_stream_create_any, in any role and any mixture; nvca_face_stream_create and nvca_part_stream_create refuse it
+ * (NVCA_ERR_UNSUPPORTED).  Its scan ignores `flags`.
+ * Its launches are booked under the existing timing slots.  An LBP cascade's single small image -- a part detector's face region,
+ * the 160-px face-pass image: whatever fits one workgroup's LDS -- is scanned by the round's one small-image launch, under
+ * NVCA_K_ROI (option "roi", as for old-format cascades); a new-format HAAR cascade has no small-image kernel and always takes the
+ * large-image route.  Larger images and jobs of several images: the evaluator's kernels under NVCA_K_STRIP ("window per
  * lane"), the level resize and integral under NVCA_K_RESIZE1 / NVCA_K_INTEGRAL as CV_HAAR_SCALE_IMAGE books them, a face stream's
  * grouping under NVCA_K_GROUP. */
 #define NVCA_CASCADE_HAAR 0
 #define NVCA_CASCADE_LBP  1
+#define NVCA_CASCADE_HAAR_NEW 2     /* new format, featureType HAAR */
 int  nvca_cascade_load_xml(nvca_ctx *ctx, const char *path, nvca_cascade **out);
 int  nvca_cascade_load_mem(nvca_ctx *ctx, const char *xml, int64_t len, nvca_cascade **out);
 void nvca_cascade_free(nvca_cascade *c);
@@ -195,8 +200,8 @@ int  nvca_cascade_kind(const nvca_cascade *c, int *has_tilted, int *has_trees);
  * stage_sizes/stage_thr[n_stages] (stump cascades only) */
 int  nvca_cascade_dump(const nvca_cascade *c, int *rects, float *weights, float *thr,
                        float *left_val, float *right_val, int *stage_sizes, float *stage_thr);
-/* which branch of cv::CascadeClassifier::load (cascadedetect.cpp) took the file: NVCA_CASCADE_HAAR / NVCA_CASCADE_LBP, and the
- * length of an LBP cascade's feature list (0 for an old-format cascade); either pointer may be NULL */
+/* which branch of cv::CascadeClassifier::load (cascadedetect.cpp) took the file: NVCA_CASCADE_HAAR / NVCA_CASCADE_LBP /
+ * NVCA_CASCADE_HAAR_NEW, and the length of a new-format cascade's feature list (0 for an old-format cascade); either pointer may be NULL */
 int  nvca_cascade_format(const nvca_cascade *c, int *format, int *n_features);
 /* flat dump of an LBP cascade as cascadedetect.cpp's Data::read / LBPEvaluator::read keep it, for cross-checking the loader
  * (any pointer may be NULL): rects[n_features*4] (x, y, w, h of the top-left cell), feature_idx[n_weak], subsets[n_weak*8],
@@ -204,6 +209,13 @@ int  nvca_cascade_format(const nvca_cascade *c, int *format, int *n_features);
  * old-format cascade (as nvca_cascade_dump answers for an LBP cascade; nvca_cascade_kind reports (0, 0) for one). */
 int  nvca_cascade_dump_lbp(const nvca_cascade *c, int *rects, int *feature_idx, int32_t *subsets, float *leaves,
                            int *stage_sizes, float *stage_thr);
+/* flat dump of a new-format HAAR cascade as Data::read / HaarEvaluator::read keep it (any pointer may be NULL):
+ * rects[n_features*12] (3 rects x, y, w, h; a missing one all zero), weights[n_features*3] (a missing rect's is 0),
+ * rect_counts[n_features], feature_idx[n_weak], thr[n_weak], leaves[n_weak*2], stage_sizes / stage_thr[n_stages] -- thresholds as
+ * evaluated, after the 1e-5f.  NVCA_ERR_ARG for any other cascade (as nvca_cascade_dump and nvca_cascade_dump_lbp answer for this
+ * one; nvca_cascade_kind reports (0, 0)). */
+int  nvca_cascade_dump_haar_new(const nvca_cascade *c, int *rects, float *weights, int *rect_counts, int *feature_idx, float *thr,
+                                float *leaves, int *stage_sizes, float *stage_thr);
 
 /* ---- imgproc primitives (each = one cv:: call of the reference) -------- */
 /* cv::cvtColor(CV_BGR2GRAY) FACE/kmsfacedetect.cpp:806, TRK/gstnubotracker.cpp:356 (channels 4) */

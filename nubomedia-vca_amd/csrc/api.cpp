@@ -234,7 +234,7 @@ try {
     CascadeFile f;
     int rc = parse_cascade_file(xml, (size_t)len, f, err);
     if (rc) { ctx->set_error("cascade XML: " + err); return rc; }
-    c->c = std::move(f.haar); c->lbp = std::move(f.lbp); c->format = f.format;
+    c->c = std::move(f.haar); c->lbp = std::move(f.lbp); c->hnew = std::move(f.hnew); c->format = f.format;
     c->ctx = ctx;
     c->c.uid = ctx->next_uid++;
     *out = c.release();
@@ -252,11 +252,11 @@ try {
     std::string msg;
     const int rc = parse_cascade_file(xml, (size_t)len, f, msg);
     if (rc) { if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", msg.c_str()); return rc; }
-    const bool lbp = f.format == NVCA_CASCADE_LBP;
+    const bool lbp = f.format == NVCA_CASCADE_LBP, hnew = f.format == NVCA_CASCADE_HAAR_NEW;
     if (win_w) *win_w = f.haar.ow;
     if (win_h) *win_h = f.haar.oh;
-    if (n_stages) *n_stages = lbp ? (int)f.lbp.stages.size() : (int)f.haar.stages.size();
-    if (n_weak) *n_weak = lbp ? (int)f.lbp.weak.size() : (int)f.haar.cls.size();
+    if (n_stages) *n_stages = lbp ? (int)f.lbp.stages.size() : hnew ? (int)f.hnew.stages.size() : (int)f.haar.stages.size();
+    if (n_weak) *n_weak = lbp ? (int)f.lbp.weak.size() : hnew ? (int)f.hnew.weak.size() : (int)f.haar.cls.size();
     return NVCA_OK;
 }
 NVCA_API_CATCH(nullptr)
@@ -320,9 +320,9 @@ try {
     if (!c) return NVCA_ERR_ARG;
     if (win_w) *win_w = c->c.ow;
     if (win_h) *win_h = c->c.oh;
-    const bool lbp = c->format == NVCA_CASCADE_LBP;
-    if (n_stages) *n_stages = lbp ? (int)c->lbp.stages.size() : (int)c->c.stages.size();
-    if (n_weak) *n_weak = lbp ? (int)c->lbp.weak.size() : (int)c->c.cls.size();
+    const bool lbp = c->format == NVCA_CASCADE_LBP, hnew = c->format == NVCA_CASCADE_HAAR_NEW;
+    if (n_stages) *n_stages = lbp ? (int)c->lbp.stages.size() : hnew ? (int)c->hnew.stages.size() : (int)c->c.stages.size();
+    if (n_weak) *n_weak = lbp ? (int)c->lbp.weak.size() : hnew ? (int)c->hnew.weak.size() : (int)c->c.cls.size();
     return NVCA_OK;
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))
@@ -332,7 +332,7 @@ int nvca_cascade_format(const nvca_cascade *c, int *format, int *n_features)
 try {
     if (!c) return NVCA_ERR_ARG;
     if (format) *format = c->format;
-    if (n_features) *n_features = c->format == NVCA_CASCADE_LBP ? (int)c->lbp.features.size() : 0;
+    if (n_features) *n_features = c->format == NVCA_CASCADE_LBP ? (int)c->lbp.features.size() : c->format == NVCA_CASCADE_HAAR_NEW ? (int)c->hnew.features.size() : 0;
     return NVCA_OK;
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))
@@ -351,6 +351,30 @@ try {
     for (size_t s = 0; s < l.stages.size(); s++) {
         if (stage_sizes) stage_sizes[s] = l.stages[s].count;
         if (stage_thr) stage_thr[s] = l.stages[s].threshold;
+    }
+    return NVCA_OK;
+}
+NVCA_API_CATCH((c ? c->ctx : nullptr))
+
+// what Data::read / HaarEvaluator::read keep of a new-format HAAR cascade, flat
+int nvca_cascade_dump_haar_new(const nvca_cascade *c, int *rects, float *weights, int *rect_counts, int *feature_idx, float *thr, float *leaves,
+                               int *stage_sizes, float *stage_thr)
+try {
+    if (!c || c->format != NVCA_CASCADE_HAAR_NEW) return NVCA_ERR_ARG;
+    const HnewCascade &h = c->hnew;
+    for (size_t i = 0; i < h.features.size(); i++) {
+        if (rects) memcpy(rects + i * 12, h.features[i].rect, sizeof(int) * 12);
+        if (weights) memcpy(weights + i * 3, h.features[i].weight, sizeof(float) * 3);
+        if (rect_counts) rect_counts[i] = h.features[i].nrect;
+    }
+    for (size_t i = 0; i < h.weak.size(); i++) {
+        if (feature_idx) feature_idx[i] = h.weak[i].feature;
+        if (thr) thr[i] = h.weak[i].threshold;
+        if (leaves) { leaves[i * 2] = h.weak[i].leaf[0]; leaves[i * 2 + 1] = h.weak[i].leaf[1]; }
+    }
+    for (size_t s = 0; s < h.stages.size(); s++) {
+        if (stage_sizes) stage_sizes[s] = h.stages[s].count;
+        if (stage_thr) stage_thr[s] = h.stages[s].threshold;
     }
     return NVCA_OK;
 }

@@ -49,8 +49,21 @@ struct LbpCascade {
     std::vector<LbpStage> stages;
 };
 
+// --------------------------------------------------------------------------
+// The same envelope with featureType HAAR: what Data::read and HaarEvaluator::read keep of a cascade of stumps on upright features.
+// SURVEY.md A.16.  A feature has one to three rects; a missing one is all zero with weight 0 (its sum is 0, the third is not added).
+// --------------------------------------------------------------------------
+struct HnewFeature { int rect[3][4]; float weight[3]; int nrect; };      // x, y, w, h, window-relative
+struct HnewWeak { int feature; float threshold; float leaf[2]; };        // vote = value < threshold ? leaf[0] : leaf[1]
+struct HnewCascade {
+    int ow = 0, oh = 0;
+    std::vector<HnewFeature> features;
+    std::vector<HnewWeak> weak;
+    std::vector<LbpStage> stages;          // (threshold as evaluated: (float)value - 1e-5f, as an LBP cascade's)
+};
+
 // a cascade file of either format: `format` says which model the loader filled (haar.ow / haar.oh hold the window either way)
-struct CascadeFile { int format = NVCA_CASCADE_HAAR; Cascade haar; LbpCascade lbp; };
+struct CascadeFile { int format = NVCA_CASCADE_HAAR; Cascade haar; LbpCascade lbp; HnewCascade hnew; };
 
 // returns NVCA_OK or NVCA_ERR_PARSE / NVCA_ERR_UNSUPPORTED; err gets a message
 int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err);      // old-format files only

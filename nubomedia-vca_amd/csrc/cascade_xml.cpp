@@ -1,6 +1,5 @@
-// cascade_xml.cpp -- reader of OpenCV's old-format Haar cascade XML
-// (type_id="opencv-haar-classifier"), the format of every cascade file the
-// reference loads: FACE/kmsfacedetect.cpp:40,162-177, EYE/kmseyedetect.cpp:27-29,
+// cascade_xml.cpp -- reader of OpenCV's cascade XML: old-format Haar files and new-format LBP / HAAR files (further down).  The old
+// format (type_id="opencv-haar-classifier") is the format of every cascade file the reference loads: FACE/kmsfacedetect.cpp:40,162-177, EYE/kmseyedetect.cpp:27-29,
 // NOSE/kmsnosedetect.cpp:31-32, MOUTH/kmsmouthdetect.cpp:37-38, EAR/kmseardetect.cpp:29-31.
 // Mirrors what OpenCV 2.4's icvReadHaarClassifier stores: numbers are parsed as
 // double and kept as float; a *_val leaf becomes alpha[last++] with child index -last.
@@ -245,31 +244,44 @@ std::string word(const XNode *n)
     return s.substr(b);
 }
 
-// the new-format branch (type_id="opencv-cascade-classifier"): what OpenCV 2.4 cascadedetect.cpp's CascadeClassifier::Data::read
-// and LBPEvaluator::read keep of an LBP cascade of stumps -- numbers parsed as double and kept as float, the stage threshold
-// less 1e-5f (subtracted in float), a stump's subset as eight int32 words
-int parse_lbp(const XNode &cn, LbpCascade &out, std::string &err)
+// the envelope of a new-format file (type_id="opencv-cascade-classifier"), as OpenCV 2.4 cascadedetect.cpp's CascadeClassifier::Data::read
+// takes it, for either feature type: everything in front of the stages and the features.  maxCatCount is checked against the feature
+// type here, before any feature or node is read: Data::read takes a stump's nodes for categorical ones whenever it is not 0.
+struct NewEnvelope { const XNode *stages = nullptr, *features = nullptr; int ow = 0, oh = 0, nstages = 0; bool haar = false; };
+int read_envelope(const XNode &cn, NewEnvelope &e, std::string &err)
 {
     const XNode *stype = cn.child("stageType"), *ftype = cn.child("featureType"), *hn = cn.child("height"), *wn = cn.child("width");
     const XNode *sparams = cn.child("stageParams"), *fparams = cn.child("featureParams"), *snum = cn.child("stageNum");
-    const XNode *stages = cn.child("stages"), *features = cn.child("features");
-    if (!stype || !ftype || !hn || !wn || !sparams || !fparams || !snum || !stages || !features) {
+    e.stages = cn.child("stages"); e.features = cn.child("features");
+    if (!stype || !ftype || !hn || !wn || !sparams || !fparams || !snum || !e.stages || !e.features) {
         err = "new-format cascade without stageType/featureType/height/width/stageParams/featureParams/stageNum/stages/features"; return NVCA_ERR_PARSE;
     }
     if (word(stype) != "BOOST") { err = "stageType '" + word(stype) + "' is not supported (BOOST only)"; return NVCA_ERR_UNSUPPORTED; }
     const std::string ft = word(ftype);
-    if (ft == "HAAR" || ft == "HOG") { err = "new-format " + ft + " cascades are not supported (LBP only)"; return NVCA_ERR_UNSUPPORTED; }
-    if (ft != "LBP") { err = "unknown featureType"; return NVCA_ERR_PARSE; }
-    if (!one_int(wn, out.ow) || !one_int(hn, out.oh) || out.ow <= 2 || out.oh <= 2 || out.ow > 1024 || out.oh > 1024) { err = "bad <width> / <height>"; return NVCA_ERR_PARSE; }
-    int v = 0, nstages = 0;
+    if (ft == "HOG") { err = "new-format HOG cascades are not supported (LBP and HAAR only)"; return NVCA_ERR_UNSUPPORTED; }
+    if (ft != "LBP" && ft != "HAAR") { err = "unknown featureType"; return NVCA_ERR_PARSE; }
+    e.haar = ft == "HAAR";
+    if (!one_int(wn, e.ow) || !one_int(hn, e.oh) || e.ow <= 2 || e.oh <= 2 || e.ow > 1024 || e.oh > 1024) { err = "bad <width> / <height>"; return NVCA_ERR_PARSE; }
+    int v = 0;
     if (!one_int(sparams->child("maxWeakCount"), v)) { err = "stageParams without maxWeakCount"; return NVCA_ERR_PARSE; }
     if (const XNode *md = sparams->child("maxDepth")) {
         if (!one_int(md, v)) { err = "bad <maxDepth>"; return NVCA_ERR_PARSE; }
         if (v > 1) { err = "weak classifiers with maxDepth > 1 (trees) are not supported"; return NVCA_ERR_UNSUPPORTED; }
     }
     if (!one_int(fparams->child("maxCatCount"), v)) { err = "featureParams without maxCatCount"; return NVCA_ERR_PARSE; }
-    if (v != 256) { err = "maxCatCount is not 256 (LBP codes are 8 bits)"; return NVCA_ERR_UNSUPPORTED; }
-    if (!one_int(snum, nstages)) { err = "bad <stageNum>"; return NVCA_ERR_PARSE; }
+    if (!e.haar && v != 256) { err = "maxCatCount is not 256 (LBP codes are 8 bits)"; return NVCA_ERR_UNSUPPORTED; }
+    if (e.haar && v != 0) { err = "featureType HAAR with maxCatCount other than 0 (categorical nodes on Haar features) is not supported"; return NVCA_ERR_UNSUPPORTED; }
+    if (!one_int(snum, e.nstages)) { err = "bad <stageNum>"; return NVCA_ERR_PARSE; }
+    return NVCA_OK;
+}
+
+// featureType LBP: what Data::read and LBPEvaluator::read keep of an LBP cascade of stumps -- numbers parsed as double and kept as
+// float, the stage threshold less 1e-5f (subtracted in float), a stump's subset as eight int32 words
+int parse_lbp(const NewEnvelope &e, LbpCascade &out, std::string &err)
+{
+    const XNode *stages = e.stages, *features = e.features;
+    const int nstages = e.nstages;
+    out.ow = e.ow; out.oh = e.oh;
 
     out.features.clear(); out.weak.clear(); out.stages.clear();
     std::vector<int> iv; std::vector<double> dv;
@@ -307,6 +319,61 @@ int parse_lbp(const XNode &cn, LbpCascade &out, std::string &err)
     return NVCA_OK;
 }
 
+// featureType HAAR: what Data::read and HaarEvaluator::Feature::read keep of a cascade of stumps on upright features.
+// A stump's internalNodes is "0 -1 featureIdx threshold" (the threshold a real), a feature one to three rects "x y w h weight".
+int parse_hnew(const NewEnvelope &e, HnewCascade &out, std::string &err)
+{
+    out.ow = e.ow; out.oh = e.oh;
+    out.features.clear(); out.weak.clear(); out.stages.clear();
+    std::vector<double> dv, lv;
+    for (auto &f : e.features->kids) {
+        const XNode *rects = f->child("rects"), *tilted = f->child("tilted");
+        if (!rects) { err = "feature without <rects>"; return NVCA_ERR_PARSE; }
+        int tl = 0;
+        if (tilted && !one_int(tilted, tl)) { err = "bad <tilted>"; return NVCA_ERR_PARSE; }
+        if (tl != 0) { err = "tilted features are not supported in a new-format HAAR cascade"; return NVCA_ERR_UNSUPPORTED; }
+        if (rects->kids.empty() || rects->kids.size() > 3) { err = "feature must have 1 to 3 rects"; return NVCA_ERR_PARSE; }
+        HnewFeature hf; memset(&hf, 0, sizeof(hf));
+        hf.nrect = (int)rects->kids.size();
+        for (int k = 0; k < hf.nrect; k++) {
+            if (!to_doubles(rects->kids[(size_t)k]->text, dv) || dv.size() != 5) { err = "rect is not 'x y w h weight'"; return NVCA_ERR_PARSE; }
+            for (int q = 0; q < 4; q++) {
+                if (!(dv[(size_t)q] >= -4096. && dv[(size_t)q] <= 4096.) || dv[(size_t)q] != floor(dv[(size_t)q])) { err = "rect coordinate is not a small integer"; return NVCA_ERR_PARSE; }
+                hf.rect[k][q] = (int)dv[(size_t)q];
+            }
+            const int *r = hf.rect[k];
+            // every corner the evaluator reads exists at every window position
+            if (r[0] < 0 || r[1] < 0 || r[2] <= 0 || r[3] <= 0 || r[0] + r[2] > e.ow || r[1] + r[3] > e.oh) { err = "rect outside the window"; return NVCA_ERR_PARSE; }
+            if (!std::isfinite(dv[4])) { err = "rect weight is not a finite number"; return NVCA_ERR_PARSE; }
+            hf.weight[k] = (float)dv[4];
+        }
+        out.features.push_back(hf);
+    }
+    for (auto &st : e.stages->kids) {
+        const XNode *sthr = st->child("stageThreshold"), *wk = st->child("weakClassifiers");
+        int mwc = 0; double d;
+        if (!sthr || !wk || !one_int(st->child("maxWeakCount"), mwc) || !to_double(sthr->text, d)) { err = "stage without maxWeakCount/stageThreshold/weakClassifiers"; return NVCA_ERR_PARSE; }
+        LbpStage ls; ls.first = (int)out.weak.size(); ls.count = (int)wk->kids.size();
+        ls.threshold = (float)d - 1e-5f;                  // THRESHOLD_EPS, subtracted in float
+        if (ls.count <= 0) { err = "empty stage"; return NVCA_ERR_PARSE; }
+        if (ls.count != mwc) { err = "stage's maxWeakCount disagrees with its weak classifiers"; return NVCA_ERR_PARSE; }
+        for (auto &w : wk->kids) {
+            const XNode *in = w->child("internalNodes"), *lf = w->child("leafValues");
+            if (!in || !lf || !to_doubles(in->text, dv) || !to_doubles(lf->text, lv)) { err = "weak classifier without internalNodes/leafValues"; return NVCA_ERR_PARSE; }
+            if (dv.size() > 4 && dv.size() % 4 == 0 && lv.size() == dv.size() / 4 + 1) { err = "weak classifiers with more than one internal node (trees) are not supported"; return NVCA_ERR_UNSUPPORTED; }
+            if (dv.size() != 4 || dv[0] != 0. || dv[1] != -1. || lv.size() != 2) { err = "internalNodes is not '0 -1 featureIdx threshold' with two leaf values"; return NVCA_ERR_PARSE; }
+            if (!(dv[2] >= 0. && dv[2] < (double)out.features.size()) || dv[2] != floor(dv[2])) { err = "featureIdx outside the feature list"; return NVCA_ERR_PARSE; }
+            if (!std::isfinite(dv[3]) || !std::isfinite(lv[0]) || !std::isfinite(lv[1])) { err = "threshold or leaf value is not a finite number"; return NVCA_ERR_PARSE; }
+            HnewWeak hw; hw.feature = (int)dv[2]; hw.threshold = (float)dv[3]; hw.leaf[0] = (float)lv[0]; hw.leaf[1] = (float)lv[1];
+            out.weak.push_back(hw);
+        }
+        out.stages.push_back(ls);
+    }
+    if (out.stages.empty()) { err = "cascade has no stages"; return NVCA_ERR_PARSE; }
+    if ((int)out.stages.size() != e.nstages) { err = "stageNum disagrees with the stages"; return NVCA_ERR_PARSE; }
+    return NVCA_OK;
+}
+
 } // namespace
 
 int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err)
@@ -323,9 +390,12 @@ int parse_cascade_file(const char *text, size_t len, CascadeFile &out, std::stri
     XNode root;
     if (int rc = parse_root(text, len, root, err)) return rc;
     if (!root.kids.empty() && root.kids[0]->type_id == "opencv-cascade-classifier") {
+        NewEnvelope e;
         out.format = NVCA_CASCADE_LBP;
-        const int rc = parse_lbp(*root.kids[0], out.lbp, err);
-        if (rc == NVCA_OK) { out.haar.ow = out.lbp.ow; out.haar.oh = out.lbp.oh; }
+        if (int rc = read_envelope(*root.kids[0], e, err)) return rc;
+        out.format = e.haar ? NVCA_CASCADE_HAAR_NEW : NVCA_CASCADE_LBP;
+        const int rc = e.haar ? parse_hnew(e, out.hnew, err) : parse_lbp(e, out.lbp, err);
+        if (rc == NVCA_OK) { out.haar.ow = e.ow; out.haar.oh = e.oh; }
         return rc;
     }
     out.format = NVCA_CASCADE_HAAR;

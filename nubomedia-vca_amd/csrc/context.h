@@ -93,7 +93,11 @@ struct KernelTimer {
 
 } // namespace nvca
 
-struct nvca_cascade { nvca::Cascade c; nvca_ctx *ctx; nvca::LbpCascade lbp; int format = NVCA_CASCADE_HAAR; };      // format LBP: `lbp` is the model, c holds the window size and the uid
+struct nvca_cascade {       // format LBP / HAAR_NEW: `lbp` / `hnew` is the model, c holds the window size and the uid
+    nvca::Cascade c; nvca_ctx *ctx; nvca::LbpCascade lbp; int format = NVCA_CASCADE_HAAR; nvca::HnewCascade hnew;
+    // a new-format file, whatever its features: the new-format scan (its own pyramid levels, step and skip rule; `flags` ignored)
+    bool new_format() const { return format != NVCA_CASCADE_HAAR; }
+};
 
 namespace nvca {
 static constexpr int kLanes = 10;         // lane 0: the context's stream; 1 .. 7: the batched part detectors; 8: the face detector's second batch in flight; 9: the trackers

@@ -43,7 +43,7 @@ int nvca_detect_raw(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray
                     int cap, int *n_out)
 try {
     if (!n_out || cap < 0 || (cap > 0 && !out)) return NVCA_ERR_ARG;
-    if ((flags & NVCA_HAAR_FIND_BIGGEST_OBJECT) && !(cascade && cascade->format == NVCA_CASCADE_LBP)) return NVCA_ERR_ARG;       // (an LBP cascade's scan ignores flags)
+    if ((flags & NVCA_HAAR_FIND_BIGGEST_OBJECT) && !(cascade && cascade->new_format())) return NVCA_ERR_ARG;       // (a new-format cascade's scan ignores flags)
     std::vector<nvca_rect> r;
     int rc = detect_gray(ctx, cascade, gray, w, h, stride, mem, scale_factor, 0, flags, min_w, min_h, max_w, max_h, true, r);
     if (rc) return rc;
@@ -100,7 +100,7 @@ int nvca_detect_raw_batch(nvca_ctx *ctx, const nvca_cascade *cascade, int n, con
                           double scale_factor, int flags, int min_w, int min_h, int max_w, int max_h, nvca_rect *out, int cap,
                           int *n_out)
 try {
-    if ((flags & NVCA_HAAR_FIND_BIGGEST_OBJECT) && !(cascade && cascade->format == NVCA_CASCADE_LBP)) return NVCA_ERR_ARG;       // (as nvca_detect_raw)
+    if ((flags & NVCA_HAAR_FIND_BIGGEST_OBJECT) && !(cascade && cascade->new_format())) return NVCA_ERR_ARG;       // (as nvca_detect_raw)
     return detect_gray_batch(ctx, cascade, n, gray, w, h, stride, mem, scale_factor, 0, flags, min_w, min_h, max_w, max_h, true, out,
                              cap, n_out);
 }

@@ -262,7 +262,7 @@ int nvca::make_detect_job(nvca_ctx *ctx, DetectJob &j, const nvca_cascade *casc,
     j = DetectJob();
     j.rq.casc = casc; j.rq.img[0] = gray; j.rq.nimg = 1; j.rq.cols = w; j.rq.rows = h; j.rq.stride = stride; j.rq.mem = mem;
     j.rq.sf = sf; j.rq.min_neighbors = min_neighbors; j.rq.minw = minw; j.rq.minh = minh; j.rq.maxw = maxw; j.rq.maxh = maxh; j.rq.raw_only = raw_only;
-    if (casc->format == NVCA_CASCADE_LBP) j.rq.kind = kJobLbp;           // the new-format scan ignores flags (cascadedetect.cpp)
+    if (casc->new_format()) j.rq.kind = kJobLbp;           // the new-format scan ignores flags (cascadedetect.cpp)
     else if (flags & NVCA_HAAR_FIND_BIGGEST_OBJECT) {
         flags &= ~(NVCA_HAAR_SCALE_IMAGE | NVCA_HAAR_DO_CANNY_PRUNING);
         if (raw_only) return NVCA_ERR_ARG;

@@ -259,6 +259,28 @@ struct LbpArgs {
     unsigned long long *hits; unsigned hit_cap;       // hits[0] = exact count, hits[1 .. cap] = img << 32 | key (the job's one list)
 };
 
+// ---- new-format HAAR cascades (kernels_cascade_hnew.hip): the scan, its levels, tiles, stages, bit planes, lists and
+// keys are the LBP evaluator's (LbpArgs, `l` below; k_lbp_walk runs on it as it is); the weak classifier is a stump on a Haar feature
+// at window scale 1 and every window has a variance normaliser.
+// A weak classifier, wave-uniform (scalar loads, five dwordx4): per rect the corners (x, y), (x + w, y), (x, y + h), (x + w, y + h) as
+// element offsets from the window's origin at ONE pitch (rect r at off[4 r ..]; a missing rect: four zeros, weight 0), the weights, the
+// stump's threshold and leaves.  A plan holds the table at the planes' pitch and at the stage-0 tile's.
+struct alignas(16) HnewWeakDev { int off[12]; float w[3]; float thr; float leaf[2]; int pad[2]; };
+static_assert(sizeof(HnewWeakDev) == 80, "HnewWeakDev is fetched with wide scalar loads");
+struct HnewArgs {
+    LbpArgs l;                      // (gweak / tweak unused)
+    const HnewWeakDev *gweak, *tweak;       // offsets at pitch P / at pitch TP
+    // the squared integral of the levels as the pyramid launchers leave it: image b's u32 low-word planes at sq + b * 2 * plane_total,
+    // its u8 high-byte planes in the plane_total words behind them.  A level's low words lie at + plane_off elements; its high bytes at
+    // + hi_mul * plane_off BYTES of the high-byte region: 1 where one launch integrates every level (k_pyr_integral), 4 where the levels
+    // are integrated one by one (a plan with a level wider than 1023: each launch is handed the level's low-word plane and puts the
+    // high bytes plane_total words behind THAT)
+    const unsigned *sq;
+    int hi_mul, pad;
+    int nr[4], nrt[4];              // normrect (1, 1, ow - 2, oh - 2): its four corners in off[]'s order at pitch P / at pitch TP
+    double area;                    // (ow - 2) * (oh - 2)
+};
+
 // ---- detectMultiScale on a small image in one workgroup (kernels_roi.hip)
 struct RoiStep {                  // one ladder step (scale-cascade scan) or one pyramid level (CV_HAAR_SCALE_IMAGE) of a job
     const TStumpRec *trecs;       // the cascade's stumps at this step's factor (levels: factor 1)

@@ -86,7 +86,7 @@ int nvca_face_stream_create_any(nvca_ctx *ctx, const nvca_cascade *cascade, cons
 try {
     if (!ctx || !cascade || !out) return NVCA_ERR_ARG;
     if (cascade->ctx != ctx) { ctx->set_error("the cascade belongs to another context"); return NVCA_ERR_ARG; }      // (its plans and tables are its context's)
-    if (cascade->format != NVCA_CASCADE_HAAR && cascade->format != NVCA_CASCADE_LBP) { ctx->set_error("face streams take a Haar or a new-format LBP cascade"); return NVCA_ERR_UNSUPPORTED; }
+    if (cascade->format != NVCA_CASCADE_HAAR && cascade->format != NVCA_CASCADE_LBP && cascade->format != NVCA_CASCADE_HAAR_NEW) { ctx->set_error("face streams take an old-format Haar or a new-format LBP / HAAR cascade"); return NVCA_ERR_UNSUPPORTED; }
     return face_stream_new(ctx, cascade, params, out);
 }
 NVCA_API_CATCH(ctx)
@@ -243,7 +243,7 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
         const int cols = work[i].cols, rows = work[i].rows;
         GeomPlan *gp = nullptr, *scan = nullptr;
         const double sf = 1 + s0->p.scale_factor_pct * 1.0 / 100;      // MULTI_SCALE_FACTOR :142
-        const bool lbp = s0->cascade->format == NVCA_CASCADE_LBP;
+        const bool lbp = s0->cascade->new_format();          // (a new-format scan, LBP or HAAR: lbp_job.cpp)
         int rc;
         if (lbp) {
             // the pre-processing half of the face plan and the LBP scan's own cached plan (no Haar scan tables from the cascade's empty `c`);

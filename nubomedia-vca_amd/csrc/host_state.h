@@ -64,10 +64,12 @@ struct RowCopy {
     int first = 0, period = 0, run = 0, count = 0;
 };
 
-// new-format LBP cascades (lbp_job.cpp, lbp_plan; the tables: lbp_tables.cpp): the evaluator's tables on the device and its arguments but for the
-// per-call buffers; the pyramid and the scan grids (hit_valid / hit_rect) are the GeomPlan's lv / det.specs
+// new-format cascades (lbp_job.cpp, lbp_plan; the tables: lbp_tables.cpp, hnew_tables.cpp): the evaluator's tables on the device and its arguments
+// but for the per-call buffers; the pyramid and the scan grids (hit_valid / hit_rect) are the GeomPlan's lv / det.specs.  `format` says which
+// evaluator scans: NVCA_CASCADE_LBP (args alone) or NVCA_CASCADE_HAAR_NEW (hnew, whose `l` is filled from args at every launch set)
 struct LbpPlan {
     DevBuf d_blob; LbpArgs args{};
+    int format = NVCA_CASCADE_LBP; HnewArgs hnew{};
     size_t bit_words = 0, positions = 0;      // stage-0 pass bits (u32 words) and grid positions of all levels
     int lds = 0;                              // bytes of the stage-0 tile (0: the window is too large, stage 0 gathers from the plane)
     const ScaleRec *gscales = nullptr; const int *gpos = nullptr;      // device grouping: a record per level, the levels' output coordinates (in d_blob)
@@ -168,7 +170,7 @@ bool frames_aligned4(const nvca_frame *frames, const int *idx, int n);
 bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l);
 
 // ---- detectMultiScale jobs (detect_job.cpp, detect_rounds.cpp) and their small-image batches (roi_batch.cpp)
-enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2, kJobLbp = 3, kJobKinds = 4 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT, a new-format LBP cascade (whatever the flags)
+enum JobKind { kJobPlain = 0, kJobScaleImage = 1, kJobBiggest = 2, kJobLbp = 3, kJobKinds = 4 };       // scale-cascade scan, CV_HAAR_SCALE_IMAGE, CV_HAAR_FIND_BIGGEST_OBJECT, a new-format cascade, LBP or HAAR (whatever the flags)
 enum JobPhase { kJobNew = 0, kJobFirstQueued = 1, kJobNarrowedQueued = 2, kJobDone = 3 };      // (narrowed: the second set of a FIND_BIGGEST search)
 
 struct DetectJob {
@@ -243,7 +245,8 @@ struct PyrSource { const uint8_t *img; int pitch; size_t slot; const uint8_t *lu
 int pyr_job_source(nvca_ctx *ctx, const DetectJob &j, PyrSource &src);       // a job's images: in place, or staged into the lane's gray slots
 int pyr_build(nvca_ctx *ctx, const PyrSource &src, int cols, int rows, int nimg, GeomPlan *pp, bool has_tilted);
 
-// ---- lbp_job.cpp: the cached plan and the launch set of a new-format LBP scan, for a detectMultiScale job and for a face stream's chunk
+// ---- lbp_job.cpp: the cached plan and the launch set of a new-format scan (the evaluator by the cascade's format: LBP or HAAR), for a
+// detectMultiScale job and for a face stream's chunk
 int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out);
 // pyramid of `nimg` images of `src`, the evaluator, and -- group_thr given ([nimg] groupRectangles thresholds) and device grouping
 // allowed -- k_group on the candidate keys; the job's result slots are cj.r0 .. cj.r0 + nimg of cj.total.  early_done: recorded behind the

@@ -116,6 +116,10 @@ void launch_group(hipStream_t st, const CascadeArgs &a, const int *group_thr, in
 void launch_lbp_stage0(hipStream_t st, const LbpArgs &a, int lds);
 void launch_lbp_walk(hipStream_t st, const LbpArgs &a);
 void launch_lbp_rest(hipStream_t st, const LbpArgs &a, int s0, int s1, int in, int in_cnt, unsigned max_items);
+// ---- new-format HAAR cascades (kernels_cascade_hnew.hip): the same scan with the Haar evaluator -- its stage 0 and its stage groups
+// around launch_lbp_walk(a.l), which reads the pass bits alone
+void launch_hnew_stage0(hipStream_t st, const HnewArgs &a, int lds);
+void launch_hnew_rest(hipStream_t st, const HnewArgs &a, int s0, int s1, int in, int in_cnt, unsigned max_items);
 // ---- image-to-overlay and view-* outlines on a device frame (kernels_draw.hip)
 void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const OverlayImage &o);
 void launch_draw_shapes(hipStream_t st, uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *d_shapes, int n,

@@ -1,7 +1,8 @@
-// lbp_job.cpp -- the launch set of a detectMultiScale job on a new-format LBP cascade: its cached plan (pyramid: pyramid.cpp; tables:
-// lbp_tables.cpp) and the evaluator's launches (kernels_cascade_lbp.hip).
+// lbp_job.cpp -- the launch set of a detectMultiScale job on a new-format cascade: its cached plan (pyramid: pyramid.cpp; tables:
+// lbp_tables.cpp, hnew_tables.cpp) and the evaluator's launches (featureType LBP: kernels_cascade_lbp.hip; HAAR: kernels_cascade_hnew.hip
+// around the LBP file's walk kernel).
 #include "host_state.h"
-#include "lbp_tables.h"
+#include "hnew_tables.h"
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
@@ -10,29 +11,33 @@ using namespace nvca;
 
 namespace nvca {
 
-// cv::CascadeClassifier::detectMultiScale on a new-format LBP cascade (OpenCV 2.4 cascadedetect.cpp): the pyramid of
-// CV_HAAR_SCALE_IMAGE with its own level rules, scanned by the LBP evaluator (kernels_cascade_lbp.hip).  The plan holds the pyramid
+// cv::CascadeClassifier::detectMultiScale on a new-format cascade (OpenCV 2.4 cascadedetect.cpp): the pyramid of
+// CV_HAAR_SCALE_IMAGE with its own level rules, scanned by the cascade's evaluator (the plan key carries the format).  The plan holds the pyramid
 // (layout, resize tables), one scan grid per level, the cascade's tables at the pitch of the planes and of the stage-0 tile, and the
 // levels as k_group reads them.  Cached per (cascade, image size, parameters): a detectMultiScale job and a face stream of one
 // geometry share it.
 int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out)
 {
-    const LbpCascade &c = casc->lbp;
+    const bool hnew = casc->format == NVCA_CASCADE_HAAR_NEW;
+    const int ow = casc->c.ow, oh = casc->c.oh;          // (the window, whichever model holds the cascade)
     int rc;
     char key[256];
-    snprintf(key, sizeof(key), "LBP|%llu|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)casc->c.uid, cols, rows, sf, minw, minh, maxw, maxh);
+    snprintf(key, sizeof(key), hnew ? "HNEW|%llu|%d|%d|%.17g|%d|%d|%d|%d" : "LBP|%llu|%d|%d|%.17g|%d|%d|%d|%d", (unsigned long long)casc->c.uid, cols, rows, sf, minw, minh, maxw, maxh);
     GeomPlan *pp = find_plan(ctx, key);
     if (!pp) {
         std::unique_ptr<GeomPlan> np(new GeomPlan());
-        if ((rc = pyr_plan_init(ctx, *np, cols, rows, lbp_levels(c.ow, c.oh, cols, rows, sf, minw, minh, maxw, maxh, 63)))) return rc;
+        if ((rc = pyr_plan_init(ctx, *np, cols, rows, lbp_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, 63)))) return rc;
         if (!np->lv.empty()) {
             // the scan grids: what hit_valid / hit_rect check and map a candidate key with
-            for (const PyrLevel &L : np->lv) np->det.specs.push_back(level_spec(np->P, L, c.ow, c.oh, 1));
-            LbpTables t; std::string err;
-            if ((rc = build_lbp_tables(c, np->lv, np->P, t, err))) { ctx->set_error(err); return rc; }
+            for (const PyrLevel &L : np->lv) np->det.specs.push_back(level_spec(np->P, L, ow, oh, 1));
+            HnewTables ht; std::string err;
+            if ((rc = hnew ? build_hnew_tables(casc->hnew, np->lv, np->P, ht, err) : build_lbp_tables(casc->lbp, np->lv, np->P, ht.scan, err))) { ctx->set_error(err); return rc; }
+            const LbpTables &t = ht.scan;
             np->det.key_sy = t.key_sy; np->det.key_ss = t.key_ss;
             LbpPlan &lp = np->lbp;
+            lp.format = casc->format;
             TableBlob blob;
+            const size_t o_hg = hnew ? blob.add(ht.gweak.data(), ht.gweak.size() * sizeof(HnewWeakDev)) : 0, o_ht = hnew ? blob.add(ht.tweak.data(), ht.tweak.size() * sizeof(HnewWeakDev)) : 0;
             const size_t o_levels = blob.add(t.levels.data(), t.levels.size() * sizeof(LbpLevelDev)), o_tiles = blob.add(t.tiles.data(), t.tiles.size() * sizeof(LbpTile)),
                          o_stages = blob.add(t.stages.data(), t.stages.size() * sizeof(LbpStageDev)), o_gweak = blob.add(t.gweak.data(), t.gweak.size() * sizeof(LbpWeakDev)),
                          o_tweak = blob.add(t.tweak.data(), t.tweak.size() * sizeof(LbpWeakDev)),
@@ -44,10 +49,16 @@ int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double
             a.tiles = (const LbpTile *)(base + o_tiles); a.ntiles = (int)t.tiles.size();
             a.stages = (const LbpStageDev *)(base + o_stages); a.nstages = (int)t.stages.size();
             a.gweak = (const LbpWeakDev *)(base + o_gweak); a.tweak = (const LbpWeakDev *)(base + o_tweak);
-            a.P = np->P; a.TP = t.TP; a.ow = c.ow; a.oh = c.oh; a.nrows = t.nrows;
+            a.P = np->P; a.TP = t.TP; a.ow = ow; a.oh = oh; a.nrows = t.nrows;
             a.key_sy = t.key_sy; a.key_ss = t.key_ss; a.tile_stages = t.tile_stages;
             lp.bit_words = t.bit_words; lp.positions = t.positions; lp.lds = t.lds;
             lp.gscales = (const ScaleRec *)(base + o_gscales); lp.gpos = (const int *)(base + o_gpos);
+            if (hnew) {
+                HnewArgs &h = lp.hnew; memset(&h, 0, sizeof(h));
+                a.gweak = a.tweak = nullptr;
+                h.gweak = (const HnewWeakDev *)(base + o_hg); h.tweak = (const HnewWeakDev *)(base + o_ht);
+                memcpy(h.nr, ht.nr, sizeof(h.nr)); memcpy(h.nrt, ht.nrt, sizeof(h.nrt)); h.area = ht.area;
+            }
         }
         pp = store_plan(ctx, key, std::move(np));
     }
@@ -55,7 +66,7 @@ int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double
     return NVCA_OK;
 }
 
-// The launch set of an LBP scan, stated once: the pyramid of `nimg` images of `src` (the caller's images, or a lane's gray slots read
+// The launch set of a new-format scan, stated once: the pyramid of `nimg` images of `src` (the caller's images, or a lane's gray slots read
 // through their LUTs), the evaluator on all of them, and -- group_thr given -- groupRectangles on the device; results into slots
 // cj.r0 .. cj.r0 + nimg of cj.total.  Work buffers are the current lane's.
 int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, int rows, int nimg, CascadeJob &cj, const int *group_thr,
@@ -64,7 +75,7 @@ int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, 
     Workspace &ws = *ctx->ws;
     ResultBufs &rb = ws.res[ws.cur_res];
     int rc;
-    // (the pyramid launchers write the squared integral with the sum: it is computed and ignored here)
+    // (the pyramid launchers write the squared integral with the sum: the HAAR evaluator reads it, the LBP one ignores it)
     if ((rc = pyr_build(ctx, src, cols, rows, nimg, pp, false))) return rc;
     const LbpPlan &lp = pp->lbp;
     // The job's images share every launch.  Pass bits per image; the two survivor lists are the whole job's, and either holds every
@@ -96,13 +107,16 @@ int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, 
     {   // the first stages everywhere, the serial walk's skip rule, then the later stages group by group on ever shorter survivor
         // lists (groups of 2, 3, 4 ... stages: survivors thin out by about half per stage).  All booked as "window per lane".
         TimedLaunch t(ctx, NVCA_K_STRIP);
-        launch_lbp_stage0(ctx->cs(), a, lp.lds);
+        const bool hnew = lp.format == NVCA_CASCADE_HAAR_NEW;
+        HnewArgs h = lp.hnew;
+        h.l = a; h.sq = ws.ln().sqsum.as<unsigned>(); h.hi_mul = pp->pyr_ok ? 1 : 4;          // (where pyr_build left the levels' high-byte planes)
+        if (hnew) launch_hnew_stage0(ctx->cs(), h, lp.lds); else launch_lbp_stage0(ctx->cs(), a, lp.lds);
         launch_lbp_walk(ctx->cs(), a);
         int g = 0;
         for (int s0 = a.tile_stages, len = 2; s0 < a.nstages && g + 1 < (int)kCnt; s0 += len, len++, g++) {
             // (the last group takes every stage that is left: the counters bound the number of groups)
             const int s1 = g + 2 == (int)kCnt ? a.nstages : std::min(a.nstages, s0 + len);
-            launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)entries);
+            if (hnew) launch_hnew_rest(ctx->cs(), h, s0, s1, g & 1, g, (unsigned)entries); else launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)entries);
             if (s1 >= a.nstages) break;
         }
     }

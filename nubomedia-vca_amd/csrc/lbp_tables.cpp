@@ -6,7 +6,8 @@
 
 namespace nvca {
 
-int build_lbp_tables(const LbpCascade &c, const std::vector<PyrLevel> &lv, int P, LbpTables &out, std::string &err)
+// what depends on the window, the stages' shape and the levels alone
+int build_scan_tables(int ow, int oh, const std::vector<LbpStage> &stages, const std::vector<PyrLevel> &lv, int P, LbpTables &out, std::string &err)
 {
     out = LbpTables();
     // the evaluator's level records: each level's grid, and where its pass bits and scan rows lie among all levels'
@@ -14,7 +15,7 @@ int build_lbp_tables(const LbpCascade &c, const std::vector<PyrLevel> &lv, int P
     for (const PyrLevel &L : lv) {
         LbpLevelDev d; memset(&d, 0, sizeof(d));
         d.plane_off = L.plane_off; d.szw = L.szw; d.szh = L.szh; d.step = level_step(L.f);
-        d.nx = level_positions(L.szw, c.ow, d.step); d.ny = level_positions(L.szh, c.oh, d.step);
+        d.nx = level_positions(L.szw, ow, d.step); d.ny = level_positions(L.szh, oh, d.step);
         d.wpr = (d.nx + kLbpTileW - 1) / kLbpTileW; d.bit_off = (int)out.bit_words; d.row_first = out.nrows;
         out.bit_words += (size_t)d.wpr * d.ny; out.nrows += d.ny; out.positions += (size_t)d.nx * d.ny;
         mx = std::max(mx, (size_t)d.nx); my = std::max(my, (size_t)d.ny);
@@ -36,7 +37,18 @@ int build_lbp_tables(const LbpCascade &c, const std::vector<PyrLevel> &lv, int P
     for (size_t li = 0; li < out.levels.size(); li++)
         for (int ty = 0; ty * kLbpTileH < out.levels[li].ny; ty++)
             for (int tx = 0; tx < out.levels[li].wpr; tx++) out.tiles.push_back(LbpTile{(int)li, tx, ty, 0});
-    out.TP = lbp_tile_pitch(c.ow);
+    out.TP = lbp_tile_pitch(ow);
+    for (const LbpStage &st : stages) out.stages.push_back(LbpStageDev{st.first, st.count, st.threshold, 0});
+    out.tile_stages = std::min((int)out.stages.size(), 3);          // at LDS speed while most windows are alive; later stages see scattered survivors
+    // the stage-0 tile at step 2 (the larger one); a window too large for 64 KiB of LDS gathers from the plane instead
+    const size_t lds = (size_t)out.TP * lbp_tile_rows(oh, 2) * sizeof(int);
+    out.lds = lds <= 64 * 1024 ? (int)lds : 0;
+    return NVCA_OK;
+}
+
+int build_lbp_tables(const LbpCascade &c, const std::vector<PyrLevel> &lv, int P, LbpTables &out, std::string &err)
+{
+    if (int rc = build_scan_tables(c.ow, c.oh, c.stages, lv, P, out, err)) return rc;
     out.gweak.resize(c.weak.size()); out.tweak.resize(c.weak.size());
     for (size_t i = 0; i < c.weak.size(); i++) {
         const LbpWeak &w = c.weak[i]; const LbpFeature &f = c.features[(size_t)w.feature];
@@ -48,11 +60,6 @@ int build_lbp_tables(const LbpCascade &c, const std::vector<PyrLevel> &lv, int P
             memcpy(d.subset, w.subset, sizeof(d.subset)); d.leaf[0] = w.leaf[0]; d.leaf[1] = w.leaf[1];
         }
     }
-    for (const LbpStage &st : c.stages) out.stages.push_back(LbpStageDev{st.first, st.count, st.threshold, 0});
-    out.tile_stages = std::min((int)out.stages.size(), 3);          // at LDS speed while most windows are alive; later stages see scattered survivors
-    // the stage-0 tile at step 2 (the larger one); a window too large for 64 KiB of LDS gathers from the plane instead
-    const size_t lds = (size_t)out.TP * lbp_tile_rows(c.oh, 2) * sizeof(int);
-    out.lds = lds <= 64 * 1024 ? (int)lds : 0;
     return NVCA_OK;
 }
 

@@ -21,6 +21,9 @@ struct LbpTables {
     int lds = 0;                              // bytes of the stage-0 tile (0: the window is too large, stage 0 gathers from the plane)
     size_t bit_words = 0, positions = 0;      // stage-0 pass bits (u32 words) and grid positions of all levels
 };
+// the part every new-format scan shares, whatever its evaluator (gweak / tweak stay empty): levels, tiles, stages, key layout, k_group's
+// records, the stage-0 tile's pitch and LDS bytes -- from the window, the stages' shape and the levels alone
+int build_scan_tables(int ow, int oh, const std::vector<LbpStage> &stages, const std::vector<PyrLevel> &lv, int P, LbpTables &out, std::string &err);
 // the tables of cascade `c` on levels `lv` whose planes have pitch P; NVCA_ERR_ARG (with err) when the scan outgrows the candidate key
 int build_lbp_tables(const LbpCascade &c, const std::vector<PyrLevel> &lv, int P, LbpTables &out, std::string &err);
 

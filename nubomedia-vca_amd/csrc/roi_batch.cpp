@@ -19,6 +19,7 @@ static constexpr int kRoiMaxWords = 14848;          // (cols + 1) * (rows + 2) w
 bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round)
 {
     if (!ctx->sw.roi) return false;
+    if (j.rq.kind == kJobLbp && j.rq.casc->format != NVCA_CASCADE_LBP) return false;      // a new-format HAAR cascade: neither k_roi nor k_roi_lbp evaluates it
     if (j.rq.kind == kJobLbp) {
         // a new-format LBP cascade (its Haar model is empty): ONE image whose working set fits k_roi_lbp's LDS (kRoiLbpMaxBytes,
         // lbp_roi_tables.h); a job of several images, and every job of the _batch entry points, keeps the image axis of the

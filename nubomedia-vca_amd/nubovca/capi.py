@@ -19,7 +19,7 @@ HAAR_DO_CANNY_PRUNING, HAAR_SCALE_IMAGE, HAAR_FIND_BIGGEST_OBJECT, HAAR_DO_ROUGH
 SUM_F32PAIR, SUM_F64 = 0, 1
 K_COUNT = 14
 PIX_BGR, PIX_NV12, PIX_I420 = 0, 1, 2
-CASCADE_HAAR, CASCADE_LBP = 0, 1
+CASCADE_HAAR, CASCADE_LBP, CASCADE_HAAR_NEW = 0, 1, 2
 
 
 class NvcaError(RuntimeError):
@@ -100,7 +100,7 @@ SYMBOLS = [
     "nvca_cascade_validate_mem", "nvca_abi_selftest", "nvca_ctx_set_option", "nvca_ctx_get_option", "nvca_overlay_blend",
     "nvca_part_batch_submit", "nvca_part_batch_collect", "nvca_face_stream_set_input", "nvca_yuv420_to_bgr",
     "nvca_part_stream_set_input", "nvca_tracker_set_input", "nvca_bgr_to_yuv420", "nvca_draw_shapes_yuv420",
-    "nvca_overlay_blend_yuv420", "nvca_cascade_format", "nvca_cascade_dump_lbp",
+    "nvca_overlay_blend_yuv420", "nvca_cascade_format", "nvca_cascade_dump_lbp", "nvca_cascade_dump_haar_new",
 ]
 
 _lib = None
@@ -173,6 +173,7 @@ def load():
     L.nvca_cascade_kind.argtypes = [vp, ip, ip]
     L.nvca_cascade_format.argtypes = [vp, ip, ip]
     L.nvca_cascade_dump_lbp.argtypes = [vp, ip, ip, C.POINTER(C.c_int32), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
+    L.nvca_cascade_dump_haar_new.argtypes = [vp, ip, C.POINTER(C.c_float), ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
     L.nvca_detect_multiscale.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
     L.nvca_detect_raw.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
@@ -551,7 +552,7 @@ class Cascade:
         return dict(size=(ow, oh), rects=rects, weights=wts, thr=thr, left=lv, right=rv, stage_sizes=ss, stage_thr=st)
 
     def format(self):
-        """(CASCADE_HAAR or CASCADE_LBP, length of an LBP cascade's feature list)"""
+        """(CASCADE_HAAR, CASCADE_LBP or CASCADE_HAAR_NEW, length of a new-format cascade's feature list)"""
         f, n = C.c_int(), C.c_int()
         self.ctx.check(self.ctx.L.nvca_cascade_format(self.h, C.byref(f), C.byref(n)))
         return f.value, n.value
@@ -567,6 +568,19 @@ class Cascade:
         self.ctx.check(self.ctx.L.nvca_cascade_dump_lbp(self.h, rects.ctypes.data_as(ip), fidx.ctypes.data_as(ip), subsets.ctypes.data_as(C.POINTER(C.c_int32)),
                                                         leaves.ctypes.data_as(fp), ss.ctypes.data_as(ip), st.ctypes.data_as(fp)))
         return dict(size=(ow, oh), rects=rects, feature_idx=fidx, subsets=subsets, leaves=leaves, stage_sizes=ss, stage_thr=st)
+
+    def dump_haar_new(self):
+        """a new-format HAAR cascade as the loader keeps it (stage thresholds as evaluated, after the 1e-5f); ERR_ARG for any other cascade"""
+        ow, oh, ns, nw = self.info()
+        nf = self.format()[1]
+        rects, wts, counts = np.zeros((nf, 3, 4), np.int32), np.zeros((nf, 3), np.float32), np.zeros(nf, np.int32)
+        fidx, thr, leaves = np.zeros(nw, np.int32), np.zeros(nw, np.float32), np.zeros((nw, 2), np.float32)
+        ss, st = np.zeros(ns, np.int32), np.zeros(ns, np.float32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        self.ctx.check(self.ctx.L.nvca_cascade_dump_haar_new(self.h, rects.ctypes.data_as(ip), wts.ctypes.data_as(fp), counts.ctypes.data_as(ip),
+                                                             fidx.ctypes.data_as(ip), thr.ctypes.data_as(fp), leaves.ctypes.data_as(fp),
+                                                             ss.ctypes.data_as(ip), st.ctypes.data_as(fp)))
+        return dict(size=(ow, oh), rects=rects, weights=wts, rect_counts=counts, feature_idx=fidx, thr=thr, leaves=leaves, stage_sizes=ss, stage_thr=st)
 
     def free(self):
         if self.h:

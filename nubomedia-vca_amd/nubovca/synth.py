@@ -673,3 +673,154 @@ def lbp_cascade_to_xml(casc, style="traincascade"):
 
 def lbp_cascade_xml(style="traincascade", **kw):
     return lbp_cascade_to_xml(make_lbp_cascade(**kw), style)
+
+
+# ------------------------------------------------------------------ new-format HAAR cascades
+def _rand_haar_new_feature(rng, ow, oh):
+    """rects [(x, y, w, h, weight)] of a feature as opencv_traincascade's HAAR set has them (whole support -1, a part +2 / +3), one in
+    ten a single rect of weight 1"""
+    for _ in range(1000):
+        w, h = int(rng.integers(2, ow + 1)), int(rng.integers(2, oh + 1))
+        x, y = int(rng.integers(0, ow - w + 1)), int(rng.integers(0, oh - h + 1))
+        kind = int(rng.integers(0, 10))
+        if kind in (0, 1) and w % 2 == 0:
+            return [(x, y, w, h, -1.0), (x + w // 2, y, w // 2, h, 2.0)]
+        if kind in (2, 3) and h % 2 == 0:
+            return [(x, y, w, h, -1.0), (x, y + h // 2, w, h // 2, 2.0)]
+        if kind == 4 and w % 3 == 0:
+            return [(x, y, w, h, -1.0), (x + w // 3, y, w // 3, h, 3.0)]
+        if kind == 5 and h % 3 == 0:
+            return [(x, y, w, h, -1.0), (x, y + h // 3, w, h // 3, 3.0)]
+        if kind in (6, 7, 8) and w % 2 == 0 and h % 2 == 0:
+            return [(x, y, w, h, -1.0), (x, y, w // 2, h // 2, 2.0), (x + w // 2, y + h // 2, w // 2, h // 2, 2.0)]
+        if kind == 9:
+            return [(x, y, w, h, 1.0)]
+    raise RuntimeError("feature sampling failed")
+
+
+def _haar_new_values(S, Q, rects, ow, oh, xs, ys):
+    """feature value * vnf at the window origins ys x xs (f64: good enough to calibrate thresholds on, not the evaluator's arithmetic)"""
+    def rs(A, x, y, w, h):
+        return A[np.ix_(ys + y, xs + x)] - A[np.ix_(ys + y, xs + x + w)] - A[np.ix_(ys + y + h, xs + x)] + A[np.ix_(ys + y + h, xs + x + w)]
+    vs, vq = rs(S, 1, 1, ow - 2, oh - 2).astype(np.float64), rs(Q, 1, 1, ow - 2, oh - 2).astype(np.float64)
+    nf = (ow - 2) * (oh - 2) * vq - vs * vs
+    nf = np.where(nf > 0, np.sqrt(np.maximum(nf, 0)), 1.0)
+    v = sum(wt * rs(S, x, y, w, h).astype(np.float64) for (x, y, w, h, wt) in rects)
+    return v / nf
+
+
+def _integral_pair_np(img):
+    return _integral_np(img), _integral_np(img.astype(np.int64) ** 2)
+
+
+def make_haar_new_cascade(ow=24, oh=24, seed=1, stage_sizes=(3, 4, 5, 6, 7, 8, 9), pass_rate=0.5, calibrate_on=None):
+    """A new-format HAAR cascade of stumps as a dict: size=(ow, oh), features=[[(x, y, w, h, weight)] of 1 to 3 rects], stages=[dict(
+    threshold=the file's value, weak=[dict(feature=index, threshold=t, leaves=(l0, l1))])].  Every stump puts the stretched TEMPLATE on
+    the side of its higher leaf, with a margin, so pasted templates pass every stage; the stage thresholds are calibrated the way
+    make_lbp_cascade's are: on `calibrate_on` (default lbp_calibration_images()), each stage passing about `pass_rate` of the windows
+    that reach it, for as long as the sample lasts."""
+    rng = np.random.default_rng(seed)
+    imgs = lbp_calibration_images() if calibrate_on is None else list(calibrate_on)
+    tmpl = np.clip(np.rint(lbp_template(ow, oh)), 0, 255).astype(np.uint8)
+    St, Qt = _integral_pair_np(tmpl)
+    z = np.zeros(1, np.int64)
+    sample = []
+    for im in imgs:
+        for lev in (im, im[::2, ::2]):
+            if lev.shape[0] > oh and lev.shape[1] > ow:
+                sample.append(_integral_pair_np(lev) + (np.arange(0, lev.shape[1] - ow, 2), np.arange(0, lev.shape[0] - oh, 2)))
+    alive = [np.ones((len(ys), len(xs)), bool) for (_, _, xs, ys) in sample]
+    features, stages = [], []
+    for n in stage_sizes:
+        weak, sums, hi = [], [np.zeros(a.shape, np.float64) for a in alive], 0.0
+        while len(weak) < n:
+            rects = _rand_haar_new_feature(rng, ow, oh)
+            vT = float(_haar_new_values(St, Qt, rects, ow, oh, z, z)[0, 0])
+            if abs(vT) < 1e-3:
+                continue                                    # the template does not tell the sides of this feature apart
+            thr = float(np.float32(0.4 * vT if len(rects) > 1 else vT * (0.8 if vT > 0 else 1.2)))
+            a, b = float(np.float32(rng.uniform(0.3, 1.0))), float(np.float32(rng.uniform(0.3, 1.0)))
+            leaves = (-b, a) if vT >= thr else (a, -b)      # value < threshold takes leaves[0]
+            features.append(rects)
+            weak.append(dict(feature=len(features) - 1, threshold=thr, leaves=leaves))
+            hi += a
+            for k, (S, Q, xs, ys) in enumerate(sample):
+                sums[k] = sums[k] + np.where(_haar_new_values(S, Q, rects, ow, oh, xs, ys) < thr, leaves[0], leaves[1])
+        reach = np.concatenate([s[a] for s, a in zip(sums, alive)]) if alive else np.zeros(0)
+        st_thr = float(np.quantile(reach, 1.0 - pass_rate)) if len(reach) >= 16 else 0.35 * hi
+        st_thr = float(np.float32(min(st_thr, 0.7 * hi)))    # pasted templates (every vote high, but for noise) stay in
+        alive = [a & (s >= st_thr) for s, a in zip(sums, alive)]
+        stages.append(dict(threshold=st_thr, weak=weak))
+    return dict(name="synthetic_haar_new", size=(ow, oh), features=features, stages=stages)
+
+
+def haar_new_cascade_to_xml(casc, style="traincascade"):
+    """The cascade as opencv_traincascade -featureType HAAR writes it (style "traincascade": every stageParams / featureParams field,
+    stage comments) or as OpenCV's own converted haarcascade_*.xml hold it (style "minimal": maxWeakCount and maxCatCount alone)."""
+    assert style in ("traincascade", "minimal")
+    ow, oh = casc["size"]
+    mwc = max(len(s["weak"]) for s in casc["stages"])
+    o = ['<?xml version="1.0"?>', "<opencv_storage>", '<cascade type_id="opencv-cascade-classifier">', "  <stageType>BOOST</stageType>",
+         "  <featureType>HAAR</featureType>", "  <height>%d</height>" % oh, "  <width>%d</width>" % ow, "  <stageParams>"]
+    if style == "traincascade":
+        o += ["    <boostType>GAB</boostType>", "    <minHitRate>9.9500000476837158e-01</minHitRate>", "    <maxFalseAlarm>5.0000000000000000e-01</maxFalseAlarm>",
+              "    <weightTrimRate>9.4999999999999996e-01</weightTrimRate>", "    <maxDepth>1</maxDepth>"]
+    o += ["    <maxWeakCount>%d</maxWeakCount></stageParams>" % mwc, "  <featureParams>", "    <maxCatCount>0</maxCatCount>"]
+    if style == "traincascade":
+        o += ["    <featSize>1</featSize>", "    <mode>ALL</mode>"]
+    o[-1] += "</featureParams>"
+    o += ["  <stageNum>%d</stageNum>" % len(casc["stages"]), "  <stages>"]
+    for si, st in enumerate(casc["stages"]):
+        if style == "traincascade":
+            o.append("    <!-- stage %d -->" % si)
+        o += ["    <_>", "      <maxWeakCount>%d</maxWeakCount>" % len(st["weak"]), "      <stageThreshold>%s</stageThreshold>" % _f(st["threshold"]), "      <weakClassifiers>"]
+        for w in st["weak"]:
+            o += ["        <_>", "          <internalNodes>", "            0 -1 %d %s</internalNodes>" % (w["feature"], _f(w["threshold"])),
+                  "          <leafValues>", "            %s %s</leafValues></_>" % (_f(w["leaves"][0]), _f(w["leaves"][1]))]
+        o += ["      </weakClassifiers></_>"]
+    o += ["  </stages>", "  <features>"]
+    for rects in casc["features"]:
+        o += ["    <_>", "      <rects>"]
+        for (x, y, w, h, wt) in rects:
+            o += ["        <_>", "          %d %d %d %d %s</_>" % (x, y, w, h, _f(wt) + ("." if float(wt) == int(wt) and abs(float(wt)) < 1e6 else ""))]
+        o += ["      </rects>", "      <tilted>0</tilted></_>"]
+    o += ["  </features></cascade>", "</opencv_storage>", ""]
+    return "\n".join(o)
+
+
+def haar_new_cascade_xml(style="traincascade", **kw):
+    return haar_new_cascade_to_xml(make_haar_new_cascade(**kw), style)
+
+
+def haar_old_to_new_dict(casc):
+    """An old-format cascade dict of stumps on upright features (make_cascade's: per stage features / thresholds / left / right /
+    stage_threshold) as a new-format HAAR dict: one feature per stump, in file order; rects, weights, thresholds and votes as they
+    stand.  The two formats are evaluated by different arithmetic, so this carries the workload's shape, not the answers."""
+    features, stages = [], []
+    for st in casc["stages"]:
+        assert "trees" not in st and not any(st.get("tilted", [])), "stumps on upright features only"
+        weak = []
+        for j, f in enumerate(st["features"]):
+            features.append([tuple(r) for r in f])
+            weak.append(dict(feature=len(features) - 1, threshold=st["thresholds"][j], leaves=(st["left"][j], st["right"][j])))
+        stages.append(dict(threshold=st["stage_threshold"], weak=weak))
+    return dict(name=casc.get("name", "converted") + "_new", size=tuple(casc["size"]), features=features, stages=stages)
+
+
+def haar_old_xml_to_new_xml(xml, style="minimal"):
+    """the same for an old-format XML text of stumps on upright features (synthetic_cascade_xml's, calibrated_cascade_xml's)"""
+    import xml.etree.ElementTree as ET
+    c = ET.fromstring(xml)[0]
+    assert c.get("type_id") == "opencv-haar-classifier"
+    ow, oh = (int(v) for v in c.findtext("size").split())
+    stages = []
+    for st in c.find("stages"):
+        feats, thr, lv, rv = [], [], [], []
+        for tree in st.find("trees"):
+            nodes = list(tree)
+            assert len(nodes) == 1 and int(nodes[0].find("feature").findtext("tilted")) == 0, "stumps on upright features only"
+            nd = nodes[0]
+            feats.append([tuple([int(v) for v in r.text.split()[:4]] + [float(r.text.split()[4])]) for r in nd.find("feature").find("rects")])
+            thr.append(float(nd.findtext("threshold"))); lv.append(float(nd.findtext("left_val"))); rv.append(float(nd.findtext("right_val")))
+        stages.append(dict(features=feats, thresholds=thr, left=lv, right=rv, stage_threshold=float(st.findtext("stage_threshold"))))
+    return haar_new_cascade_to_xml(haar_old_to_new_dict(dict(name=c.tag, size=(ow, oh), stages=stages)), style)
