@@ -335,6 +335,29 @@ int nvca_detect_multiscale_batch(nvca_ctx *ctx, const nvca_cascade *cascade, int
 int nvca_detect_raw_batch(nvca_ctx *ctx, const nvca_cascade *cascade, int n, const void *const *gray,
                           int w, int h, int stride, int mem, double scale_factor, int flags,
                           int min_w, int min_h, int max_w, int max_h, nvca_rect *out, int cap, int *n_out);
+/* cv::CascadeClassifier::detectMultiScale(image, objects, rejectLevels, levelWeights, scaleFactor, minNeighbors, flags, minSize,
+ * maxSize, outputRejectLevels = true) (OpenCV 2.4 cascadedetect.cpp): the scan of nvca_detect_raw on a new-format
+ * cascade of n stages, emitting every visited window that passes (reject level n) or is rejected by one of the last three stages
+ * (reject level = that stage, n - 3 .. n - 1), each with the sum of the last stage evaluated on it as its level weight (an LBP
+ * cascade's f32 sum widened to double, a HAAR cascade's f64 sum).  out[i], reject_levels[i] and level_weights[i] are one
+ * detection, in the canonical (level, y, x) order of nvca_detect_raw; *n_out may exceed cap (then only cap are written).
+ * Served: new-format LBP and HAAR cascades of four stages or more, single images in host or device memory; `flags` are accepted
+ * and ignored.  NVCA_ERR_UNSUPPORTED: an old-format cascade, or one of fewer than four stages (stage-0 rejects would be
+ * emitted).  NVCA_ERR_ARG: as nvca_detect_raw, and a NULL reject_levels or level_weights when cap > 0. */
+int nvca_detect_raw_levels(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray, int w, int h,
+                           int stride, int mem, double scale_factor, int flags, int min_w, int min_h,
+                           int max_w, int max_h, nvca_rect *out, int *reject_levels, double *level_weights,
+                           int cap, int *n_out);
+/* the same overload with its grouping, cv::groupRectangles(rects, rejectLevels, levelWeights, minNeighbors, 0.2): the classes and
+ * averaged rectangles of the plain form; a class answers with the largest reject level of its members and, among those, the
+ * largest level weight.  A class is kept by that LEVEL, not by its member count (dropped when level <= min_neighbors), while the
+ * contained-box filter reads the other class's member count -- OpenCV's behaviour, kept.  min_neighbors <= 0 returns the raw
+ * triples of nvca_detect_raw_levels untouched: this library's choice (OpenCV 2.4's early return there is not remembered with
+ * certainty).  Refusals as above. */
+int nvca_detect_multiscale_levels(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray, int w, int h,
+                                  int stride, int mem, double scale_factor, int min_neighbors, int flags,
+                                  int min_w, int min_h, int max_w, int max_h, nvca_rect *out,
+                                  int *reject_levels, double *level_weights, int cap, int *n_out);
 /* cv::groupRectangles(rects, groupThreshold, eps) on the device; in place */
 int nvca_group_rectangles(nvca_ctx *ctx, nvca_rect *rects, int n, int group_threshold, double eps,
                           int *n_out);

@@ -53,6 +53,49 @@ try {
 }
 NVCA_API_CATCH(ctx)
 
+// cv::CascadeClassifier::detectMultiScale(image, objects, rejectLevels, levelWeights, scaleFactor, minNeighbors, flags, minSize, maxSize,
+// outputRejectLevels = true): one job with Request::levels, on a new-format cascade of four stages or more
+static int detect_gray_levels(nvca_ctx *ctx, const nvca_cascade *casc, const void *gray, int w, int h, int stride, int mem, double sf,
+                              int min_neighbors, int flags, int minw, int minh, int maxw, int maxh, bool raw_only,
+                              nvca_rect *out, int *reject_levels, double *level_weights, int cap, int *n_out)
+{
+    if (!n_out || cap < 0 || (cap > 0 && (!out || !reject_levels || !level_weights))) return NVCA_ERR_ARG;
+    NVCA_LOCK_OR_FAIL(ctx);
+    DetectJob j;
+    int rc = make_detect_job(ctx, j, casc, gray, w, h, stride, mem, sf, min_neighbors, flags, minw, minh, maxw, maxh, raw_only);
+    if (rc) return rc;
+    const size_t nstages = casc->format == NVCA_CASCADE_LBP ? casc->lbp.stages.size() : casc->format == NVCA_CASCADE_HAAR_NEW ? casc->hnew.stages.size() : 0;
+    if (!casc->new_format() || nstages < 4) {
+        ctx->set_error("reject levels: a new-format cascade of four stages or more (with fewer, stage-0 rejects would be emitted)");
+        return NVCA_ERR_UNSUPPORTED;
+    }
+    j.rq.levels = true;
+    DetectJob *jp = &j;
+    if ((rc = run_detect_jobs(ctx, &jp, 1, nullptr))) return rc;
+    const size_t n = j.out[0].size();
+    *n_out = (int)n;
+    for (size_t i = 0; i < std::min<size_t>((size_t)cap, n); i++) { out[i] = j.out[0][i]; reject_levels[i] = j.out_levels[i]; level_weights[i] = j.out_weights[i]; }
+    return NVCA_OK;
+}
+
+int nvca_detect_raw_levels(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray, int w, int h, int stride, int mem,
+                           double scale_factor, int flags, int min_w, int min_h, int max_w, int max_h, nvca_rect *out,
+                           int *reject_levels, double *level_weights, int cap, int *n_out)
+try {
+    return detect_gray_levels(ctx, cascade, gray, w, h, stride, mem, scale_factor, 0, flags, min_w, min_h, max_w, max_h, true, out,
+                              reject_levels, level_weights, cap, n_out);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_detect_multiscale_levels(nvca_ctx *ctx, const nvca_cascade *cascade, const void *gray, int w, int h, int stride, int mem,
+                                  double scale_factor, int min_neighbors, int flags, int min_w, int min_h, int max_w, int max_h,
+                                  nvca_rect *out, int *reject_levels, double *level_weights, int cap, int *n_out)
+try {
+    return detect_gray_levels(ctx, cascade, gray, w, h, stride, mem, scale_factor, min_neighbors, flags, min_w, min_h, max_w, max_h, false,
+                              out, reject_levels, level_weights, cap, n_out);
+}
+NVCA_API_CATCH(ctx)
+
 // n images of one geometry: jobs of up to kJobImages images (a FIND_BIGGEST search carries one: its launch sets depend on what it
 // finds), all of them handed to ONE run_detect_jobs call -- a round of the whole batch has one wait.  Image i answers into
 // out[i * cap ...], n_out[i] is its full count.

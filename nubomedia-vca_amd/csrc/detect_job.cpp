@@ -3,6 +3,7 @@
 // new-format LBP cascade's set is lbp_job.cpp's.
 #include "host_state.h"
 #include "host_logic.h"
+#include "group_levels.h"
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
@@ -195,13 +196,14 @@ int detect_job_advance(nvca_ctx *ctx, DetectJob &j)
     std::vector<std::vector<nvca_rect>> raw;
     std::vector<char> grouped;
     std::vector<std::vector<int>> sc;
+    std::vector<std::vector<LevelRec>> recs;
     bool have = j.q.dp != nullptr;
     const bool was_fused = j.sm.fused;
     if (j.sm.fused) {
         if ((rc = roi_job_candidates(ctx, j, raw, grouped, sc))) return rc;
         have = true;
     } else
-    if (j.q.dp) rc = cascade_collect(ctx, *j.q.dp, j.q.cj, raw, j.rq.kind == kJobPlain ? &grouped : nullptr, j.rq.kind == kJobBiggest ? &sc : nullptr);
+    if (j.q.dp) rc = cascade_collect(ctx, *j.q.dp, j.q.cj, raw, j.rq.kind == kJobPlain ? &grouped : nullptr, j.rq.kind == kJobBiggest ? &sc : nullptr, j.rq.levels ? &recs : nullptr);
     if (j.q.gp) { j.q.gp->inflight--; j.q.gp = nullptr; }
     if (rc == NVCA_ERR_OVERFLOW && j.q.regrown < 2 && ctx->hit_cap_wanted > ctx->hit_cap) {
         // More raw candidates than the lists hold.  OpenCV has no such limit (and a FIND_BIGGEST search would have stopped at
@@ -220,6 +222,17 @@ int detect_job_advance(nvca_ctx *ctx, DetectJob &j)
                 if (j.q.gthr && !grouped[k]) group_rectangles(raw[k], j.q.gthr, 0.2);
                 j.out[k].swap(raw[k]);
             }
+        j.q.phase = kJobDone;
+    } else if (j.rq.kind == kJobLbp && j.rq.levels) {
+        // detectMultiScale with outputRejectLevels: the triples in canonical order, grouped by the weighted form
+        j.out_levels.clear(); j.out_weights.clear();
+        if (have) {
+            for (const LevelRec &r : recs[0]) { j.out_levels.push_back(r.level); j.out_weights.push_back(r.weight); }
+            j.out[0].swap(raw[0]);
+            if (!j.rq.raw_only && !group_rectangles_levels(j.out[0], j.out_levels, j.out_weights, j.rq.min_neighbors, 0.2)) {
+                ctx->set_error("internal: a levels job's records do not match its candidates"); j.q.phase = kJobDone; return NVCA_ERR_INTERNAL;
+            }
+        }
         j.q.phase = kJobDone;
     } else if (j.rq.kind == kJobScaleImage || j.rq.kind == kJobLbp) {
         if (have) { if (!j.rq.raw_only) group_all(raw, j.rq.min_neighbors); for (int k = 0; k < j.rq.nimg; k++) j.out[k].swap(raw[k]); }

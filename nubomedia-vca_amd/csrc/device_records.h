@@ -232,6 +232,9 @@ struct CascadeArgs {
 struct LbpWeakDev { int off[16]; int subset[8]; float leaf[2]; int pad[6]; };
 static_assert(sizeof(LbpWeakDev) == 128, "LbpWeakDev is fetched with wide scalar loads");
 struct LbpStageDev { int first, count; float thr; int pad; };
+// outputRejectLevels (k_lbp_levels / k_hnew_levels): what an emitted window carries beside its key, under the key's index of the
+// candidate list -- the stage that rejected it (nstages: none) and that stage's sum, an LBP cascade's f32 sum widened
+struct LevelRec { int level, pad; double weight; };
 // one pyramid level's scan grid: window origins (gx * step, gy * step), gx < nx, gy < ny; its stage-0 pass bits lie at
 // bits[bit_off + gy * wpr + (gx >> 5)], bit gx & 31; row_first: the level's first row in the walk kernel's row numbering
 struct LbpLevelDev { int plane_off, szw, szh, nx, ny, step, wpr, bit_off, row_first, pad0, pad1, pad2; };

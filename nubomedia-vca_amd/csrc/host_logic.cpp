@@ -63,16 +63,11 @@ int partition(const std::vector<nvca_rect> &v, std::vector<int> &labels, Similar
 }
 } // namespace
 
-void group_rectangles(std::vector<nvca_rect> &rects, int groupThreshold, double eps, std::vector<int> *weights)
+int group_classes(const std::vector<nvca_rect> &rects, double eps, std::vector<int> &labels, std::vector<nvca_rect> &rr, std::vector<int> &rw)
 {
-    if (groupThreshold <= 0 || rects.empty()) {
-        if (weights) weights->assign(rects.size(), 1);
-        return;
-    }
-    std::vector<int> labels;
     const int nclasses = partition(rects, labels, SimilarRects{eps});
-    std::vector<nvca_rect> rr(nclasses, nvca_rect{0, 0, 0, 0});
-    std::vector<int> rw(nclasses, 0);
+    rr.assign(nclasses, nvca_rect{0, 0, 0, 0});
+    rw.assign(nclasses, 0);
     for (size_t i = 0; i < rects.size(); i++) {
         nvca_rect &a = rr[labels[i]];
         a.x += rects[i].x; a.y += rects[i].y; a.w += rects[i].w; a.h += rects[i].h;
@@ -83,6 +78,18 @@ void group_rectangles(std::vector<nvca_rect> &rects, int groupThreshold, double 
         nvca_rect r = rr[i];
         rr[i] = nvca_rect{cv_round(r.x * s), cv_round(r.y * s), cv_round(r.w * s), cv_round(r.h * s)};
     }
+    return nclasses;
+}
+
+void group_rectangles(std::vector<nvca_rect> &rects, int groupThreshold, double eps, std::vector<int> *weights)
+{
+    if (groupThreshold <= 0 || rects.empty()) {
+        if (weights) weights->assign(rects.size(), 1);
+        return;
+    }
+    std::vector<int> labels, rw;
+    std::vector<nvca_rect> rr;
+    const int nclasses = group_classes(rects, eps, labels, rr, rw);
     rects.clear();
     if (weights) weights->clear();
     for (int i = 0; i < nclasses; i++) {

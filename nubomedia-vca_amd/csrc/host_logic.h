@@ -9,6 +9,11 @@ namespace nvca {
 void group_rectangles(std::vector<nvca_rect> &rects, int groupThreshold, double eps,
                       std::vector<int> *weights = nullptr);
 
+// its first half, shared with the weighted form (group_levels.cpp): cv::partition under SimilarRects(eps) -- labels[i] is rects[i]'s
+// class, classes numbered by their first member -- and per class the averaged rectangle rr[c] and the member count rw[c]; returns the
+// number of classes
+int group_classes(const std::vector<nvca_rect> &rects, double eps, std::vector<int> &labels, std::vector<nvca_rect> &rr, std::vector<int> &rw);
+
 struct TrackedFace { nvca_rect box; int id; };
 struct Faces {                 // FACE/Faces.hpp: the per-stream list with ids
     std::vector<TrackedFace> faces;

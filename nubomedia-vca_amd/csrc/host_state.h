@@ -1,6 +1,6 @@
 // host_state.h -- host-side state and helpers that the library's host sources share (not part of the ABI): the workspace, the
 // cached plans and cascade jobs (plans.cpp), detectMultiScale jobs and small-image batches (detect_job.cpp, lbp_job.cpp, pyramid.cpp,
-// detect_rounds.cpp, roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, part_logic.cpp, fb_search.cpp,
+// detect_rounds.cpp, roi_batch.cpp), and the helpers one source calls in another.  plan.cpp, host_logic.cpp, group_levels.cpp, part_logic.cpp, fb_search.cpp,
 // part_stats.cpp, options.cpp, cascade_xml.cpp, pyr_levels.cpp, lbp_tables.cpp, trk_host.cpp and work_pool.cpp do not include it: the CPU
 // drivers under tests/ build those without it (part_logic.cpp, fb_search.cpp, part_stats.cpp, options.cpp, pyr_levels.cpp, lbp_tables.cpp and
 // trk_host.cpp without any HIP header, the others with host doubles of their own).
@@ -24,8 +24,9 @@ void drain_timer(nvca_ctx *ctx);                             // ... once many ha
 struct ResultBufs {
     DevBuf hits, grp, gthr, staging, srcptrs;        // staging / srcptrs: host frames on their way in, frame pointer table
     PinnedBuf h_hits, h_grp, h_gthr, h_srcptrs;   // h_srcptrs: frame pointers on their way to the device array
+    DevBuf recs; PinnedBuf h_recs;    // a levels job's LevelRec per candidate, laid out as hits without the count word (allocated by the first such job)
     std::vector<int> gthr_last;       // thresholds currently resident in gthr
-    void release() { hits.release(); grp.release(); gthr.release(); staging.release(); srcptrs.release(); h_hits.release(); h_grp.release(); h_gthr.release(); h_srcptrs.release(); gthr_last.clear(); }
+    void release() { hits.release(); grp.release(); gthr.release(); staging.release(); srcptrs.release(); h_hits.release(); h_grp.release(); h_gthr.release(); h_srcptrs.release(); recs.release(); h_recs.release(); gthr_last.clear(); }
 };
 // Working memory of the kernels, per LANE.  A lane is a HIP stream with its own planes and cascade scratch: whatever runs on a
 // lane is ordered by its stream, different lanes run side by side.  Everything uses lane 0 (the context's stream) except
@@ -111,6 +112,7 @@ struct CascadeJob {
     size_t first = 0;         // raw candidates fetched with the count (raw mode)
     unsigned long long *d_hits = nullptr, *h_hits = nullptr;
     int *d_grp = nullptr, *h_grp = nullptr;
+    LevelRec *d_recs = nullptr, *h_recs = nullptr;      // a levels job (lbp_launch_set): the record of candidate i of d_hits at [i]
 };
 
 // ---- plans.cpp
@@ -135,7 +137,8 @@ int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, 
 int group_prepare(nvca_ctx *ctx, CascadeJob &job, const int *group_thr);
 int cascade_fetch(nvca_ctx *ctx, CascadeJob &job);
 int cascade_collect(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, std::vector<std::vector<nvca_rect>> &raw,
-                    std::vector<char> *grouped, std::vector<std::vector<int>> *scale_of = nullptr);
+                    std::vector<char> *grouped, std::vector<std::vector<int>> *scale_of = nullptr,
+                    std::vector<std::vector<LevelRec>> *recs = nullptr /* a levels job: raw[b][k]'s record at (*recs)[b][k] */);
 void group_all(std::vector<std::vector<nvca_rect>> &raw, int min_neighbors);
 GeomPlan *find_plan(nvca_ctx *ctx, const std::string &key);
 GeomPlan *store_plan(nvca_ctx *ctx, const std::string &key, std::unique_ptr<GeomPlan> gp);
@@ -182,8 +185,10 @@ struct DetectJob {
         double sf = 1.1; int min_neighbors = 0, flags = 0, minw = 0, minh = 0, maxw = 0, maxh = 0;
         bool raw_only = false;
         bool image_axis = false;                             // a job of the _batch entry points on an LBP cascade: its images, however many, share the large-image evaluator's launches
+        bool levels = false;                                 // outputRejectLevels: one image, a new-format cascade of four stages or more, always the large-image evaluator
     } rq;
     std::vector<nvca_rect> out[kJobImages];          // the result, per image
+    std::vector<int> out_levels; std::vector<double> out_weights;      // a levels job: rejectLevels / levelWeights of out[0]
     // progress of the queued launch set
     struct Queued {
         JobPhase phase = kJobNew;
@@ -250,9 +255,11 @@ int pyr_build(nvca_ctx *ctx, const PyrSource &src, int cols, int rows, int nimg,
 int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, GeomPlan **out);
 // pyramid of `nimg` images of `src`, the evaluator, and -- group_thr given ([nimg] groupRectangles thresholds) and device grouping
 // allowed -- k_group on the candidate keys; the job's result slots are cj.r0 .. cj.r0 + nimg of cj.total.  early_done: recorded behind the
-// evaluator's launches.  Collected with cascade_collect(pp->det).
+// evaluator's launches.  Collected with cascade_collect(pp->det).  levels (outputRejectLevels; without group_thr): the
+// stage groups end in front of the last three stages, which ONE launch evaluates on every window left, emitting each with a LevelRec
+// (cj.d_recs); the plan is the plain scan's.
 int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, int rows, int nimg, CascadeJob &cj,
-                   const int *group_thr = nullptr, hipEvent_t early_done = nullptr);
+                   const int *group_thr = nullptr, hipEvent_t early_done = nullptr, bool levels = false);
 int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total);              // the launch set of a job on a new-format LBP cascade
 
 // ---- detect_job.cpp

@@ -10,6 +10,8 @@
 //   k_hnew_rest     stages [s0, s1) on the survivor list, compaction and final append as k_lbp_rest's; a survivor's vnf is RECOMPUTED
 //                   from its eight corners by the same function, so it has the same bits by construction and no side array has to
 //                   stay aligned with the compacted lists
+//   k_hnew_levels   outputRejectLevels: the last three stages on the survivors in front of them; every one of those
+//                   windows is appended to the candidate list with the stage that rejected it and that stage's sum
 //
 // Arithmetic (this file is compiled with -ffp-contract=off): rect sums int32; the feature value f32, one rounding per product and per
 // addition; f64 for vnf (exact integer operands, one multiply-subtract pair, a correctly rounded sqrt and division), for the product
@@ -31,8 +33,8 @@ __device__ __forceinline__ double hnew_vnf(int valsum, const unsigned *__restric
 
 __device__ __forceinline__ int hnew_rect(const int *__restrict__ p, const int *off) { return p[off[0]] - p[off[1]] - p[off[2]] + p[off[3]]; }
 
-// a stage on the window at p: the f64 sum of the stumps' leaves in file order; false: sum < thr, the window is rejected
-__device__ __forceinline__ bool hnew_stage(const int *__restrict__ p, const HnewWeakDev *__restrict__ weak, const LbpStageDev st, double vnf)
+// a stage's sum on the window at p: the f64 sum of the stumps' leaves in file order
+__device__ __forceinline__ double hnew_stage_sum(const int *__restrict__ p, const HnewWeakDev *__restrict__ weak, const LbpStageDev st, double vnf)
 {
     double sum = 0.;
 #pragma unroll 2          // the corner loads of two weak classifiers in flight at a time; the leaves are still added one by one, in file order
@@ -42,7 +44,12 @@ __device__ __forceinline__ bool hnew_stage(const int *__restrict__ p, const Hnew
         if (w.w[2] != 0.f) ret += w.w[2] * (float)hnew_rect(p, w.off + 8);          // (wave-uniform)
         sum += (double)((double)ret * vnf < (double)w.thr ? w.leaf[0] : w.leaf[1]);
     }
-    return !(sum < (double)st.thr);
+    return sum;
+}
+// a stage on the window at p; false: sum < thr, the window is rejected
+__device__ __forceinline__ bool hnew_stage(const int *__restrict__ p, const HnewWeakDev *__restrict__ weak, const LbpStageDev st, double vnf)
+{
+    return !(hnew_stage_sum(p, weak, st, vnf) < (double)st.thr);
 }
 
 template <bool LDS>
@@ -147,6 +154,74 @@ __global__ __launch_bounds__(256) void k_hnew_rest(HnewArgs h, int s0, int s1, i
             if (alive && base + rank < a.list_cap) dst[base + rank] = e;
         }
     }
+}
+
+// detectMultiScale with outputRejectLevels: k_lbp_levels with this evaluator -- the last three stages on the survivor
+// list in front of stage nstages - 3, a survivor's vnf recomputed by hnew_vnf as k_hnew_rest does; every listed window is appended to the
+// candidate list with the stage that rejected it (nstages: none did) and that stage's f64 sum in the LevelRec under the same index.
+__global__ __launch_bounds__(256) void k_hnew_levels(HnewArgs h, LevelRec *__restrict__ recs, int in, int in_cnt)
+{
+    const LbpArgs &a = h.l;
+    unsigned n = a.cnt[in_cnt];
+    if (n > a.list_cap) n = a.list_cap;
+    const unsigned long long *__restrict__ src = in ? a.list[1] : a.list[0];
+    const int lane = threadIdx.x & 63;
+    const int s0 = a.nstages - 3;
+    if (s0 < 1) return;          // (a levels job has four stages at least)
+    for (unsigned i0 = blockIdx.x * 256u; i0 < n; i0 += gridDim.x * 256u) {          // (uniform per workgroup: the ballots below see whole waves)
+        const unsigned i = i0 + threadIdx.x;
+        bool listed = i < n;
+        unsigned long long e = 0; size_t off = 0;
+        double vnf = 1.;
+        if (listed) {
+            // an entry comes from device memory: its image and its key are checked against the job and the grids before they index the planes
+            e = src[i];
+            const unsigned img = (unsigned)(e >> 32), key = (unsigned)e;
+            const unsigned lv = key >> a.key_ss, gy = (key >> a.key_sy) & ((1u << (a.key_ss - a.key_sy)) - 1u), gx = key & ((1u << a.key_sy) - 1u);
+            listed = img < (unsigned)a.nimg && lv < (unsigned)a.nlev;
+            if (listed) {
+                const LbpLevelDev &L = a.levels[lv];
+                listed = gx < (unsigned)L.nx && gy < (unsigned)L.ny;
+                if (listed) {
+                    const size_t origin = (size_t)(gy * L.step) * a.P + gx * L.step;
+                    off = (size_t)img * a.plane_total + L.plane_off + origin;
+                    const unsigned *lo = h.sq + (size_t)img * 2 * a.plane_total + L.plane_off + origin;
+                    const uint8_t *hi = (const uint8_t *)(h.sq + (size_t)img * 2 * a.plane_total + a.plane_total) + (size_t)h.hi_mul * L.plane_off + origin;
+                    vnf = hnew_vnf(hnew_rect(a.sum + off, h.nr), lo, hi, h.nr, h.area);
+                }
+            }
+        }
+        bool alive = listed;
+        int level = s0; double sum = 0.;
+        for (int s = s0; s < a.nstages; s++) {
+            if (!__ballot(alive)) break;
+            if (alive) {
+                const LbpStageDev st = a.stages[s];
+                sum = hnew_stage_sum(a.sum + off, h.gweak, st, vnf);
+                alive = !(sum < (double)st.thr);
+                level = alive ? s + 1 : s;
+            }
+        }
+        const unsigned long long m = __ballot(listed);
+        if (!m) continue;
+        const int cntm = __popcll(m), rank = __popcll(m & ((1ull << lane) - 1ull));
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(a.hits, (unsigned long long)cntm);
+        base = __shfl(base, 0);
+        if (listed && base + rank < a.hit_cap) {
+            a.hits[1 + base + rank] = e;
+            LevelRec r; r.level = level; r.pad = 0; r.weight = sum;
+            recs[base + rank] = r;
+        }
+    }
+}
+
+void launch_hnew_levels(hipStream_t st, const HnewArgs &a, LevelRec *recs, int in, int in_cnt, unsigned max_items)
+{
+    if (max_items == 0 || a.l.nstages < 4 || !recs) return;
+    unsigned blocks = (max_items + 255u) / 256u;
+    if (blocks > 4096u) blocks = 4096u;
+    NVCA_LAUNCH(k_hnew_levels, dim3(blocks), dim3(256), 0, st, a, recs, in, in_cnt);
 }
 
 void launch_hnew_stage0(hipStream_t st, const HnewArgs &a, int lds)

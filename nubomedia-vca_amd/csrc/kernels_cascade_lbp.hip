@@ -10,6 +10,8 @@
 //                  tile's stages -- a skipped column may have been evaluated there, it is never listed and so never emitted
 //   k_lbp_rest     stages [s0, s1) on a list of survivors, corners gathered from the plane; the survivors are compacted into the next
 //                  list (the host launches one per stage group), the last group appends to the candidate list
+//   k_lbp_levels   outputRejectLevels: the last three stages on the survivors in front of them; every one of those windows
+//                  is appended to the candidate list with the stage that rejected it and that stage's sum
 //
 // A job's images (LbpArgs::nimg, one geometry) share every launch: stage 0 has the image in grid.y, the walk a lane per (image, scan
 // row), and from there on ONE survivor list holds every image's windows as img << 32 | key -- a stage group runs once on all of them,
@@ -46,9 +48,9 @@ __device__ __forceinline__ float lbp_vote(int code, const LbpWeakDev &w)
     return ((unsigned)word >> (code & 31)) & 1u ? w.leaf[0] : w.leaf[1];
 }
 
-// a stage on the window at p: the f32 sum of the votes in file order, one rounding per addition (this file is compiled with
-// -ffp-contract=off); false: tmp < thr, the window is rejected
-__device__ __forceinline__ bool lbp_stage(const int *__restrict__ p, const LbpWeakDev *__restrict__ weak, const LbpStageDev st)
+// a stage's sum on the window at p: the f32 sum of the votes in file order, one rounding per addition (this file is compiled with
+// -ffp-contract=off)
+__device__ __forceinline__ float lbp_stage_sum(const int *__restrict__ p, const LbpWeakDev *__restrict__ weak, const LbpStageDev st)
 {
     float tmp = 0.f;
 #pragma unroll 2          // the corner loads of two weak classifiers in flight at a time; the votes are still added one by one, in file order
@@ -56,7 +58,12 @@ __device__ __forceinline__ bool lbp_stage(const int *__restrict__ p, const LbpWe
         const LbpWeakDev &w = weak[st.first + k];
         tmp += lbp_vote(lbp_code(p, w), w);
     }
-    return !(tmp < st.thr);
+    return tmp;
+}
+// a stage on the window at p; false: tmp < thr, the window is rejected
+__device__ __forceinline__ bool lbp_stage(const int *__restrict__ p, const LbpWeakDev *__restrict__ weak, const LbpStageDev st)
+{
+    return !(lbp_stage_sum(p, weak, st) < st.thr);
 }
 
 template <bool LDS>
@@ -207,6 +214,67 @@ __global__ __launch_bounds__(256) void k_lbp_rest(LbpArgs a, int s0, int s1, int
             if (alive && base + rank < a.list_cap) dst[base + rank] = e;
         }
     }
+}
+
+// detectMultiScale with outputRejectLevels: the last three stages on the survivor list in front of stage nstages - 3.
+// No window drops out: each ends with the stage that rejected it (nstages: none did) and that stage's sum -- the last stage's on a
+// pass --, and every one is appended to the candidate list, its LevelRec under the same index of `recs` (hit_cap records).  The
+// list's count stays exact past hit_cap, as k_lbp_rest's.
+__global__ __launch_bounds__(256) void k_lbp_levels(LbpArgs a, LevelRec *__restrict__ recs, int in, int in_cnt)
+{
+    unsigned n = a.cnt[in_cnt];
+    if (n > a.list_cap) n = a.list_cap;
+    const unsigned long long *__restrict__ src = in ? a.list[1] : a.list[0];
+    const int lane = threadIdx.x & 63;
+    const int s0 = a.nstages - 3;
+    if (s0 < 1) return;          // (a levels job has four stages at least)
+    for (unsigned i0 = blockIdx.x * 256u; i0 < n; i0 += gridDim.x * 256u) {          // (uniform per workgroup: the ballots below see whole waves)
+        const unsigned i = i0 + threadIdx.x;
+        bool listed = i < n;
+        unsigned long long e = 0; size_t off = 0;
+        if (listed) {
+            // an entry comes from device memory: its image and its key are checked against the job and the grids before they index the planes
+            e = src[i];
+            const unsigned img = (unsigned)(e >> 32), key = (unsigned)e;
+            const unsigned lv = key >> a.key_ss, gy = (key >> a.key_sy) & ((1u << (a.key_ss - a.key_sy)) - 1u), gx = key & ((1u << a.key_sy) - 1u);
+            listed = img < (unsigned)a.nimg && lv < (unsigned)a.nlev;
+            if (listed) {
+                const LbpLevelDev &L = a.levels[lv];
+                listed = gx < (unsigned)L.nx && gy < (unsigned)L.ny;
+                if (listed) off = (size_t)img * a.plane_total + (size_t)L.plane_off + (size_t)(gy * L.step) * a.P + gx * L.step;
+            }
+        }
+        bool alive = listed;
+        int level = s0; float sum = 0.f;
+        for (int s = s0; s < a.nstages; s++) {
+            if (!__ballot(alive)) break;
+            if (alive) {
+                const LbpStageDev st = a.stages[s];
+                sum = lbp_stage_sum(a.sum + off, a.gweak, st);
+                alive = !(sum < st.thr);
+                level = alive ? s + 1 : s;
+            }
+        }
+        const unsigned long long m = __ballot(listed);
+        if (!m) continue;
+        const int cntm = __popcll(m), rank = __popcll(m & ((1ull << lane) - 1ull));
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(a.hits, (unsigned long long)cntm);
+        base = __shfl(base, 0);
+        if (listed && base + rank < a.hit_cap) {
+            a.hits[1 + base + rank] = e;
+            LevelRec r; r.level = level; r.pad = 0; r.weight = (double)sum;
+            recs[base + rank] = r;
+        }
+    }
+}
+
+void launch_lbp_levels(hipStream_t st, const LbpArgs &a, LevelRec *recs, int in, int in_cnt, unsigned max_items)
+{
+    if (max_items == 0 || a.nstages < 4 || !recs) return;
+    unsigned blocks = (max_items + 255u) / 256u;
+    if (blocks > 4096u) blocks = 4096u;
+    NVCA_LAUNCH(k_lbp_levels, dim3(blocks), dim3(256), 0, st, a, recs, in, in_cnt);
 }
 
 void launch_lbp_stage0(hipStream_t st, const LbpArgs &a, int lds)

@@ -69,8 +69,12 @@ int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double
 // The launch set of a new-format scan, stated once: the pyramid of `nimg` images of `src` (the caller's images, or a lane's gray slots read
 // through their LUTs), the evaluator on all of them, and -- group_thr given -- groupRectangles on the device; results into slots
 // cj.r0 .. cj.r0 + nimg of cj.total.  Work buffers are the current lane's.
+// A levels job (cv::CascadeClassifier::detectMultiScale with outputRejectLevels) is this scan with three differences: the
+// tile stages stop in front of the last three stages (tile_stages = min(its value, nstages - 3): an argument of the launches, the tables
+// hold every stage at either pitch, so the plan is the plain scan's), the stage groups end there too, and ONE launch evaluates the last
+// three stages on every window left, emitting each of them with the stage that rejected it and that stage's sum.
 int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, int rows, int nimg, CascadeJob &cj, const int *group_thr,
-                   hipEvent_t early_done)
+                   hipEvent_t early_done, bool levels)
 {
     Workspace &ws = *ctx->ws;
     ResultBufs &rb = ws.res[ws.cur_res];
@@ -90,6 +94,14 @@ int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, 
         rb.hits.ensure(hits_stride * tot * sizeof(unsigned long long)) || rb.h_hits.ensure(hits_stride * tot * sizeof(unsigned long long))) {
         ctx->set_error("device allocation failed for the cascade workspace"); return NVCA_ERR_NOMEM;
     }
+    if (levels) {
+        if (lp.args.nstages < 4 || group_thr) { ctx->set_error("internal: a levels scan needs four stages and groups on the host"); return NVCA_ERR_INTERNAL; }
+        // a record per candidate the list can hold: slot r's records at + hit_cap * r
+        if (rb.recs.ensure((size_t)ctx->hit_cap * tot * sizeof(LevelRec)) || rb.h_recs.ensure((size_t)ctx->hit_cap * tot * sizeof(LevelRec))) {
+            ctx->set_error("device allocation failed for the cascade workspace"); return NVCA_ERR_NOMEM;
+        }
+        cj.d_recs = rb.recs.as<LevelRec>() + (size_t)ctx->hit_cap * r0; cj.h_recs = rb.h_recs.as<LevelRec>() + (size_t)ctx->hit_cap * r0;
+    }
     cj.n = nimg;
     cj.cap = (unsigned)ctx->hit_cap * (unsigned)nimg;         // one list for all the job's slots, as cascade_enqueue's
     cj.d_hits = rb.hits.as<unsigned long long>() + hits_stride * r0;
@@ -104,6 +116,9 @@ int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, 
     a.cnt = ws.ln().deep.as<unsigned>();
     a.list[0] = (unsigned long long *)(ws.ln().deep.as<unsigned>() + kCnt); a.list[1] = ws.ln().vnf.as<unsigned long long>(); a.list_cap = (unsigned)entries;
     a.hits = cj.d_hits; a.hit_cap = cj.cap;
+    // where the tile stages and the stage groups end: at the cascade's end, or in front of the three stages a levels job's last launch takes
+    const int s_end = levels ? a.nstages - 3 : a.nstages;
+    if (levels) a.tile_stages = std::min(a.tile_stages, s_end);
     {   // the first stages everywhere, the serial walk's skip rule, then the later stages group by group on ever shorter survivor
         // lists (groups of 2, 3, 4 ... stages: survivors thin out by about half per stage).  All booked as "window per lane".
         TimedLaunch t(ctx, NVCA_K_STRIP);
@@ -112,13 +127,15 @@ int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, 
         h.l = a; h.sq = ws.ln().sqsum.as<unsigned>(); h.hi_mul = pp->pyr_ok ? 1 : 4;          // (where pyr_build left the levels' high-byte planes)
         if (hnew) launch_hnew_stage0(ctx->cs(), h, lp.lds); else launch_lbp_stage0(ctx->cs(), a, lp.lds);
         launch_lbp_walk(ctx->cs(), a);
-        int g = 0;
-        for (int s0 = a.tile_stages, len = 2; s0 < a.nstages && g + 1 < (int)kCnt; s0 += len, len++, g++) {
+        int g = 0;          // groups launched: the survivors in front of stage s_end lie in list g & 1, counted by cnt[g]
+        for (int s0 = a.tile_stages, len = 2; s0 < s_end && g + 1 < (int)kCnt; s0 += len, len++) {
             // (the last group takes every stage that is left: the counters bound the number of groups)
-            const int s1 = g + 2 == (int)kCnt ? a.nstages : std::min(a.nstages, s0 + len);
+            const int s1 = g + 2 == (int)kCnt ? s_end : std::min(s_end, s0 + len);
             if (hnew) launch_hnew_rest(ctx->cs(), h, s0, s1, g & 1, g, (unsigned)entries); else launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)entries);
-            if (s1 >= a.nstages) break;
+            g++;
+            if (s1 >= s_end) break;
         }
+        if (levels) { if (hnew) launch_hnew_levels(ctx->cs(), h, cj.d_recs, g & 1, g, (unsigned)entries); else launch_lbp_levels(ctx->cs(), a, cj.d_recs, g & 1, g, (unsigned)entries); }
     }
     if (early_done) NVCA_HIP_CHECK(ctx, hipEventRecord(early_done, ctx->cs()));
     if (cj.dev_group) {
@@ -145,7 +162,7 @@ int lbp_enqueue(nvca_ctx *ctx, DetectJob &j, int r0, int total)
     if ((rc = pyr_job_source(ctx, j, src))) return rc;
     CascadeJob &cj = j.q.cj;
     cj = CascadeJob(); cj.r0 = r0; cj.total = total;
-    if ((rc = lbp_launch_set(ctx, pp, src, j.rq.cols, j.rq.rows, j.rq.nimg, cj))) return rc;      // (grouped on the host: detect_job_advance)
+    if ((rc = lbp_launch_set(ctx, pp, src, j.rq.cols, j.rq.rows, j.rq.nimg, cj, nullptr, nullptr, j.rq.levels))) return rc;      // (grouped on the host: detect_job_advance)
     j.q.gp = pp; pp->inflight++; j.q.dp = &pp->det;
     return NVCA_OK;
 }

@@ -333,7 +333,7 @@ int cascade_enqueue(nvca_ctx *ctx, DetectPlan &dp, size_t sum_slot, int spitch, 
 
 // after the stream has been synchronised: raw[b] / grouped[b] for the job's n frames
 int cascade_collect(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, std::vector<std::vector<nvca_rect>> &raw,
-                    std::vector<char> *grouped, std::vector<std::vector<int>> *scale_of)
+                    std::vector<char> *grouped, std::vector<std::vector<int>> *scale_of, std::vector<std::vector<LevelRec>> *recs)
 {
     const bool hostprof = ctx->sw.host_profile;
     const int batch = job.n;
@@ -379,6 +379,19 @@ int cascade_collect(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, std::v
                                            hipMemcpyDeviceToHost, ctx->cs()));
         NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
     }
+    if (recs) {
+        // a levels job: candidate i's record lies under the same index; the keys are sorted with their records attached
+        recs->assign(batch, {});
+        if (!job.d_recs || !job.h_recs || job.dev_group) { ctx->set_error("internal: a levels job without its record array"); return NVCA_ERR_INTERNAL; }
+        if (total) {
+            NVCA_HIP_CHECK(ctx, hipMemcpyAsync(job.h_recs, job.d_recs, total * sizeof(LevelRec), hipMemcpyDeviceToHost, ctx->cs()));
+            NVCA_HIP_CHECK(ctx, hipStreamSynchronize(ctx->cs()));
+        }
+        std::vector<std::pair<unsigned long long, LevelRec>> kv(total);
+        for (unsigned long long i = 0; i < total; i++) kv[i] = {hh[1 + i], job.h_recs[i]};
+        std::sort(kv.begin(), kv.end(), [](const std::pair<unsigned long long, LevelRec> &x, const std::pair<unsigned long long, LevelRec> &y) { return x.first < y.first; });
+        for (unsigned long long i = 0; i < total; i++) { hh[1 + i] = kv[i].first; job.h_recs[i] = kv[i].second; }
+    } else
     std::sort(hh + 1, hh + 1 + total);
     for (unsigned long long i = 0; i < total; i++) {
         // a candidate word comes from the device: it indexes host tables only after it has been checked against them (a kernel that
@@ -392,6 +405,7 @@ int cascade_collect(nvca_ctx *ctx, DetectPlan &dp, const CascadeJob &job, std::v
         if (!job.dev_group || !(*grouped)[slot]) {
             raw[slot].push_back(dp.hit_rect((unsigned)hh[1 + i]));
             if (scale_of) (*scale_of)[slot].push_back((int)((unsigned)hh[1 + i] >> dp.key_ss));
+            if (recs) (*recs)[slot].push_back(job.h_recs[i]);
         }
     }
     return NVCA_OK;

@@ -18,7 +18,7 @@ namespace nvca {
 static constexpr int kRoiMaxWords = 14848;          // (cols + 1) * (rows + 2) words per plane: the part detectors' 160 x 90 face-pass image still fits (two planes + queues + a level image = 157 KB of the 160 KB of LDS)
 bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round)
 {
-    if (!ctx->sw.roi) return false;
+    if (!ctx->sw.roi || j.rq.levels) return false;          // (a levels job always takes the large-image evaluator: k_roi_lbp has no last-stages launch)
     if (j.rq.kind == kJobLbp && j.rq.casc->format != NVCA_CASCADE_LBP) return false;      // a new-format HAAR cascade: neither k_roi nor k_roi_lbp evaluates it
     if (j.rq.kind == kJobLbp) {
         // a new-format LBP cascade (its Haar model is empty): ONE image whose working set fits k_roi_lbp's LDS (kRoiLbpMaxBytes,

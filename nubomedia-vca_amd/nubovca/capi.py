@@ -88,7 +88,7 @@ SYMBOLS = [
     "nvca_ctx_kernel_timing", "nvca_kernel_name", "nvca_cascade_load_xml", "nvca_cascade_load_mem",
     "nvca_cascade_free", "nvca_cascade_info", "nvca_cascade_dump", "nvca_bgr2gray", "nvca_resize_linear",
     "nvca_equalize_hist", "nvca_integral", "nvca_detect_multiscale", "nvca_detect_raw", "nvca_group_rectangles",
-    "nvca_detect_multiscale_batch", "nvca_detect_raw_batch",
+    "nvca_detect_multiscale_batch", "nvca_detect_raw_batch", "nvca_detect_raw_levels", "nvca_detect_multiscale_levels",
     "nvca_face_params_default", "nvca_face_stream_create", "nvca_face_stream_create_any", "nvca_face_stream_destroy",
     "nvca_face_stream_set_params", "nvca_face_stream_motion_event", "nvca_face_stream_process",
     "nvca_face_batch_process", "nvca_tracker_params_default", "nvca_tracker_create", "nvca_tracker_destroy",
@@ -182,6 +182,11 @@ def load():
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
     L.nvca_detect_raw_batch.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, ip]
+    if hasattr(L, "nvca_detect_raw_levels"):      # (NVCA_LIB may name an older library: A/B runs against a parent commit)
+        L.nvca_detect_raw_levels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.POINTER(Rect), ip, C.POINTER(C.c_double), C.c_int, ip]
+        L.nvca_detect_multiscale_levels.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, C.c_int, C.POINTER(Rect), ip, C.POINTER(C.c_double), C.c_int, ip]
     L.nvca_group_rectangles.argtypes = [vp, C.POINTER(Rect), C.c_int, C.c_int, C.c_double, ip]
     L.nvca_face_params_default.argtypes = [C.POINTER(FaceParams)]
     L.nvca_face_params_default.restype = None
@@ -418,6 +423,33 @@ class Context:
         self.check(self.L.nvca_detect_raw(self.h, casc.h, gray.ctypes.data, w, h, gray.strides[0], MEM_HOST, scale_factor,
                                           flags, min_size[0], min_size[1], max_size[0], max_size[1], buf, cap, C.byref(n)))
         return _rects(buf, min(n.value, cap))
+
+    def _detect_levels(self, call, gray, cap, mem=MEM_HOST, shape=None, stride=None):
+        """a levels call and its answer as (rects (k, 4) int32, reject levels (k,) int32, level weights (k,) float64).  gray: a host array,
+        or -- shape=(rows, cols) and stride given -- the address of an image in `mem`"""
+        if shape is None:
+            gray = np.ascontiguousarray(gray, np.uint8)
+            (h, w), stride, ptr = gray.shape, gray.strides[0], gray.ctypes.data
+        else:
+            (h, w), ptr = shape, int(gray)
+        buf, lv, wt, n = (Rect * max(cap, 1))(), (C.c_int * max(cap, 1))(), (C.c_double * max(cap, 1))(), C.c_int()
+        self.check(call(ptr, w, h, stride, mem, buf, lv, wt, cap, C.byref(n)))
+        k = min(n.value, cap)
+        return _rects(buf, k), np.array(lv[:k], np.int32), np.array(wt[:k], np.float64)
+
+    def detect_raw_levels(self, casc, gray, scale_factor=1.1, flags=0, min_size=(0, 0), max_size=(0, 0), cap=1 << 18, **where):
+        """nvca_detect_raw_levels (detectMultiScale with outputRejectLevels, before grouping): (rects, reject levels, level weights) in the
+        canonical order.  where: mem / shape / stride of _detect_levels"""
+        return self._detect_levels(lambda ptr, w, h, stride, mem, buf, lv, wt, cap_, n: self.L.nvca_detect_raw_levels(
+            self.h, casc.h, ptr, w, h, stride, mem, scale_factor, flags, min_size[0], min_size[1], max_size[0], max_size[1], buf, lv, wt,
+            cap_, n), gray, cap, **where)
+
+    def detect_multiscale_levels(self, casc, gray, scale_factor=1.1, min_neighbors=3, flags=0, min_size=(0, 0), max_size=(0, 0),
+                                 cap=1 << 18, **where):
+        """nvca_detect_multiscale_levels: the grouped (rects, reject levels, level weights)"""
+        return self._detect_levels(lambda ptr, w, h, stride, mem, buf, lv, wt, cap_, n: self.L.nvca_detect_multiscale_levels(
+            self.h, casc.h, ptr, w, h, stride, mem, scale_factor, min_neighbors, flags, min_size[0], min_size[1], max_size[0],
+            max_size[1], buf, lv, wt, cap_, n), gray, cap, **where)
 
     def _detect_batch(self, call, grays, cap):
         """the images of a batch call (host arrays of one shape and row stride) and its answer as a list of (k, 4) arrays"""
