@@ -216,6 +216,16 @@ int  nvca_cascade_dump_lbp(const nvca_cascade *c, int *rects, int *feature_idx, 
  * one; nvca_cascade_kind reports (0, 0)). */
 int  nvca_cascade_dump_haar_new(const nvca_cascade *c, int *rects, float *weights, int *rect_counts, int *feature_idx, float *thr,
                                 float *leaves, int *stage_sizes, float *stage_thr);
+/* The small-image route of a new-format HAAR cascade (cv::CascadeClassifier::detectMultiScale on a file written by
+ * opencv_traincascade -featureType HAAR), opt-in per cascade.  on != 0: a detectMultiScale job of ONE image on this
+ * cascade whose two integral planes fit a workgroup's LDS (8 (cols + 1)(rows + 1) <= 122 800 bytes: 160 x 90 is inside) is served,
+ * with every other small job of its round, by one launch and one wait instead of the large-image launch set and its cached plan per
+ * image size -- what a part detector's face-region searches are.  The flag is read when a job is built: a submitted ticket keeps the
+ * route it was built with.  Results never depend on it, and the "roi" option = 0 sends every job down the large-image route, flag or
+ * not.  Default 0: a cascade nobody opted in is routed exactly as before.  On an old-format or an LBP cascade the setter returns
+ * NVCA_OK and changes nothing -- their small routes are always available -- and the getter reports 1.  NVCA_ERR_ARG for NULL. */
+int  nvca_cascade_set_small_route(nvca_cascade *c, int on);
+int  nvca_cascade_get_small_route(const nvca_cascade *c, int *on);
 
 /* ---- imgproc primitives (each = one cv:: call of the reference) -------- */
 /* cv::cvtColor(CV_BGR2GRAY) FACE/kmsfacedetect.cpp:806, TRK/gstnubotracker.cpp:356 (channels 4) */

@@ -380,6 +380,23 @@ try {
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))
 
+// the small-image route of a new-format HAAR cascade (k_roi_hnew), opt-in: the flag is read when a job is built (make_detect_job)
+int nvca_cascade_set_small_route(nvca_cascade *c, int on)
+try {
+    if (!c) return NVCA_ERR_ARG;
+    if (c->format == NVCA_CASCADE_HAAR_NEW) c->small_route.store(on ? 1 : 0, std::memory_order_relaxed);
+    return NVCA_OK;
+}
+NVCA_API_CATCH((c ? c->ctx : nullptr))
+
+int nvca_cascade_get_small_route(const nvca_cascade *c, int *on)
+try {
+    if (!c || !on) return NVCA_ERR_ARG;
+    *on = c->format == NVCA_CASCADE_HAAR_NEW ? c->small_route.load(std::memory_order_relaxed) : 1;
+    return NVCA_OK;
+}
+NVCA_API_CATCH((c ? c->ctx : nullptr))
+
 int nvca_cascade_kind(const nvca_cascade *c, int *has_tilted, int *has_trees)
 try {
     if (!c) return NVCA_ERR_ARG;

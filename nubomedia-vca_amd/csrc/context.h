@@ -1,6 +1,7 @@
 // context.h -- the context (nvca_ctx), its buffers, work spaces and timers, the ABI's exception barrier and the detect-job API:
 // what the host sources of the library share (not part of the ABI).
 #pragma once
+#include <atomic>
 #include <string>
 #include <vector>
 #include <map>
@@ -97,6 +98,9 @@ struct nvca_cascade {       // format LBP / HAAR_NEW: `lbp` / `hnew` is the mode
     nvca::Cascade c; nvca_ctx *ctx; nvca::LbpCascade lbp; int format = NVCA_CASCADE_HAAR; nvca::HnewCascade hnew;
     // a new-format file, whatever its features: the new-format scan (its own pyramid levels, step and skip rule; `flags` ignored)
     bool new_format() const { return format != NVCA_CASCADE_HAAR; }
+    // NVCA_CASCADE_HAAR_NEW only (nvca_cascade_set_small_route): small images of this cascade may take k_roi_hnew.  Read when a job is
+    // built (DetectJob::Request::small_route): a submitted ticket keeps the route it was built with
+    std::atomic<int> small_route{0};
 };
 
 namespace nvca {

@@ -283,5 +283,6 @@ int nvca::make_detect_job(nvca_ctx *ctx, DetectJob &j, const nvca_cascade *casc,
     } else if (flags & NVCA_HAAR_SCALE_IMAGE) j.rq.kind = kJobScaleImage;
     else j.rq.kind = kJobPlain;
     j.rq.flags = flags;
+    j.rq.small_route = casc->format == NVCA_CASCADE_HAAR_NEW && casc->small_route.load(std::memory_order_relaxed) != 0;
     return NVCA_OK;
 }

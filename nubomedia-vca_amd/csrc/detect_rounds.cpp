@@ -77,7 +77,7 @@ static int jobs_round_end(nvca_ctx *ctx, DetectJob *const *jobs, int n, const in
     if (stats && !rb.jobs.empty() && n >= ctx->sw.part_stats) {
         int kinds[kJobKinds] = {0}, narrowed = 0;
         for (DetectJob *o : rb.owners) { kinds[o->rq.kind]++; if (o->sm.roi_prev_phase == kJobNarrowedQueued) narrowed++; }
-        ps.report_round(rb.jobs.size(), kinds, narrowed, rb.steps.size() + rb.lbp_steps.size(), waited_s);
+        ps.report_round(rb.jobs.size(), kinds, narrowed, rb.steps.size() + rb.lbp_steps.size() + rb.hnew_steps.size(), waited_s);
     }
     PartStats::Timer t_advance(stats, ps.advance);
     PartStats::Timer t_collect(stats && !rc && !rb.jobs.empty(), ps.collect);

@@ -328,4 +328,29 @@ static constexpr int kRoiLbpVoteWords = 4096;
 NVCA_HD constexpr int roi_lbp_fixed_bytes() { return 2 * kRoiMaxWin * 2 + 16 + kRoiLbpVoteWords * 4; }
 NVCA_HD constexpr int roi_lbp_lds_bytes(int plane_words, int lev_bytes) { return ((plane_words + 3) & ~3) * 4 + roi_lbp_fixed_bytes() + ((lev_bytes + 15) & ~15); }
 
+// ---- detectMultiScale of a new-format HAAR cascade on a small image in one workgroup (kernels_roi_hnew.hip), for the
+// cascades opted in through nvca_cascade_set_small_route.  A job is a RoiJobDev (scale_image == 3; `stages` points at the cascade's
+// RoiHnew table: nstages LbpStageDev, then -- at roi_hnew_weak_off(nstages) bytes -- its weak classifiers), a level or a band of a
+// level's rows a RoiStep as k_roi_lbp's.  The level's planes live in LDS at the level's own pitch, so a weak classifier keeps its
+// RECTANGLES (x, y, w, h) and the kernel forms the twelve corner offsets in scalar registers; a missing rect is all zero with weight 0.
+struct alignas(16) RoiHnewWeak { int rect[3][4]; float w[3]; float thr; float leaf[2]; int pad[2]; };
+static_assert(sizeof(RoiHnewWeak) == 80, "RoiHnewWeak is fetched with wide scalar loads, as HnewWeakDev");
+NVCA_HD inline size_t roi_hnew_weak_off(int nstages) { return ((size_t)nstages * sizeof(LbpStageDev) + 63) & ~(size_t)63; }
+// A stage on a short queue (at most kRoiHnewShortWin windows): a wave per (stump, 64 windows), the f32 leaf each window's vote selected
+// stored to LDS, one lane per window adding them in file order into its f64 sum -- the same additions as a window per lane.  A stage
+// with more votes than kRoiHnewVoteWords runs in consecutive chunks of stumps, the partial sum carried in the owning lane's register.
+// 0 switches the form off.
+#ifndef NVCA_ROI_HNEW_SHORT_WIN
+#define NVCA_ROI_HNEW_SHORT_WIN 256
+#endif
+static constexpr int kRoiHnewShortWin = NVCA_ROI_HNEW_SHORT_WIN;
+static constexpr int kRoiHnewVoteWords = 4096;
+static_assert(kRoiHnewShortWin <= kRoiHnewVoteWords, "a chunk holds one stump's votes of the longest short queue at least");
+// k_roi_hnew's dynamic LDS (host sizing and kernel carve-up agree through this): sum plane | squared plane | two queues | counters |
+// votes | vnf (an f64 per grid position of the band), every part a multiple of 16 bytes.  The resized level image (bytes, dead once the
+// planes stand) lies OVER votes + vnf: kRoiHnewLevBytes of room.
+static constexpr int kRoiHnewLevBytes = kRoiHnewVoteWords * 4 + kRoiMaxWin * 8;
+NVCA_HD constexpr int roi_hnew_fixed_bytes() { return 2 * kRoiMaxWin * 2 + 16 + kRoiHnewLevBytes; }
+NVCA_HD constexpr int roi_hnew_lds_bytes(int plane_words) { return 2 * ((plane_words + 3) & ~3) * 4 + roi_hnew_fixed_bytes(); }
+
 } // namespace nvca

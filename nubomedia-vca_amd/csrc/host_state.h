@@ -184,6 +184,7 @@ struct DetectJob {
         int cols = 0, rows = 0, stride = 0, mem = 0;
         double sf = 1.1; int min_neighbors = 0, flags = 0, minw = 0, minh = 0, maxw = 0, maxh = 0;
         bool raw_only = false;
+        bool small_route = false;                            // a new-format HAAR cascade: its small-route flag when the job was built (nvca_cascade_set_small_route)
         bool image_axis = false;                             // a job of the _batch entry points on an LBP cascade: its images, however many, share the large-image evaluator's launches
         bool levels = false;                                 // outputRejectLevels: one image, a new-format cascade of four stages or more, always the large-image evaluator
     } rq;
@@ -217,17 +218,18 @@ struct DetectJob {
 };
 
 struct RoiBatch {
-    std::vector<RoiJobDev> jobs; std::vector<RoiStep> steps, lbp_steps /* k_roi_lbp's: the LBP jobs' */; std::vector<unsigned char> tabs; std::vector<DetectJob *> owners; std::vector<int> owner_img;
+    std::vector<RoiJobDev> jobs; std::vector<RoiStep> steps, lbp_steps /* k_roi_lbp's: the LBP jobs' */, hnew_steps /* k_roi_hnew's: the opted-in new-format HAAR jobs' */; std::vector<unsigned char> tabs; std::vector<DetectJob *> owners; std::vector<int> owner_img;
     std::vector<ScaleTable *> held;                 // stump tables of the launch: kept from eviction until it has been collected
     int plane_words = 0, lev_bytes = 0, lane = 0; unsigned cap = 0; size_t first = 0;
     int lbp_plane_words = 0, lbp_lev_bytes = 0;     // k_roi_lbp's LDS: the largest level's sum plane (words, a multiple of 4) and resized level (bytes)
+    int hnew_plane_words = 0;                       // k_roi_hnew's: the largest level's plane (words, a multiple of 4; the sum and the squared plane have this size each)
     size_t rej_words = 0;                           // stage-0 reject bitmaps of the launch's dense steps (u64 words)
     void release() { for (ScaleTable *t : held) if (t->refs > 0) t->refs--; held.clear(); }
     ~RoiBatch() { release(); }
     RoiBatch() = default;
     RoiBatch(const RoiBatch &) = delete; RoiBatch &operator=(const RoiBatch &) = delete;
     // (a round object is reused from round to round: what the previous round held is released first)
-    void reset() { release(); jobs.clear(); steps.clear(); lbp_steps.clear(); tabs.clear(); owners.clear(); owner_img.clear(); plane_words = 0; lev_bytes = 0; lbp_plane_words = 0; lbp_lev_bytes = 0; lane = 0; cap = 0; first = 0; rej_words = 0; }
+    void reset() { release(); jobs.clear(); steps.clear(); lbp_steps.clear(); hnew_steps.clear(); tabs.clear(); owners.clear(); owner_img.clear(); plane_words = 0; lev_bytes = 0; lbp_plane_words = 0; lbp_lev_bytes = 0; hnew_plane_words = 0; lane = 0; cap = 0; first = 0; rej_words = 0; }
 };
 
 // ---- roi_batch.cpp

@@ -16,7 +16,7 @@
 // Arithmetic (this file is compiled with -ffp-contract=off): rect sums int32; the feature value f32, one rounding per product and per
 // addition; f64 for vnf (exact integer operands, one multiply-subtract pair, a correctly rounded sqrt and division), for the product
 // value = (double)ret * vnf, its compare with the threshold, and the stage sum.
-#include "launch.h"
+#include "hnew_device.h"
 
 namespace nvca {
 
@@ -26,9 +26,7 @@ __device__ __forceinline__ double hnew_vnf(int valsum, const unsigned *__restric
     const unsigned long long q0 = ((unsigned long long)hi[nr[0]] << 32) | lo[nr[0]], q1 = ((unsigned long long)hi[nr[1]] << 32) | lo[nr[1]];
     const unsigned long long q2 = ((unsigned long long)hi[nr[2]] << 32) | lo[nr[2]], q3 = ((unsigned long long)hi[nr[3]] << 32) | lo[nr[3]];
     const double valsq = (double)(long long)(q0 - q1 - q2 + q3);          // an integer below 2^40: exact
-    double nf = area * valsq - (double)valsum * (double)valsum;
-    nf = nf > 0. ? sqrt(nf) : 1.;
-    return 1. / nf;
+    return hnew_norm(area, valsq, valsum);
 }
 
 __device__ __forceinline__ int hnew_rect(const int *__restrict__ p, const int *off) { return p[off[0]] - p[off[1]] - p[off[2]] + p[off[3]]; }

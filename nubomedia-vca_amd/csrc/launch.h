@@ -152,5 +152,9 @@ int roi_grant_lds(int bytes);     // dynamic LDS above 64 KiB is granted per fun
 void launch_roi_lbp(hipStream_t st, const RoiJobDev *jobs, int nsteps, const RoiStep *steps, const unsigned char *tabs, unsigned long long *hits,
                     unsigned hit_cap, int plane_words, int lds_bytes);
 int roi_lbp_grant_lds(int bytes);
+// ---- ... of a new-format HAAR cascade that was opted in (kernels_roi_hnew.hip): likewise, its LDS sized by roi_hnew_lds_bytes
+void launch_roi_hnew(hipStream_t st, const RoiJobDev *jobs, int nsteps, const RoiStep *steps, const unsigned char *tabs, unsigned long long *hits,
+                     unsigned hit_cap, int plane_words, int lds_bytes);
+int roi_hnew_grant_lds(int bytes);
 
 } // namespace nvca

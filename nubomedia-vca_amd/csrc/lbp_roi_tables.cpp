@@ -9,14 +9,19 @@ namespace nvca {
 
 void build_lbp_roi_steps(const LbpCascade &c, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t tab0, LbpRoiSteps &out)
 {
+    build_lbp_roi_steps(c.ow, c.oh, cols, rows, sf, minw, minh, maxw, maxh, tab0, out);
+}
+
+void build_lbp_roi_steps(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t tab0, LbpRoiSteps &out)
+{
     out = LbpRoiSteps();
     // (one level more than the key holds is enough to know that the job does not fit)
-    const std::vector<SiLevel> levels = lbp_levels(c.ow, c.oh, cols, rows, sf, minw, minh, maxw, maxh, 64);
+    const std::vector<SiLevel> levels = lbp_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, 64);
     if (levels.size() > 63) { out.fits = false; return; }
     for (const SiLevel &sl : levels) {
         RoiStep st; memset(&st, 0, sizeof(st));
         st.szw = sl.szw; st.szh = sl.szh; st.step = level_step(sl.factor);
-        st.startX = 0; st.endX = sl.szw - c.ow; st.startY = 0; st.endY = sl.szh - c.oh;       // origins below size - window (level_positions)
+        st.startX = 0; st.endX = sl.szw - ow; st.startY = 0; st.endY = sl.szh - oh;       // origins below size - window (level_positions)
         if (st.endX <= 0 || st.endY <= 0) continue;
         ResizeTab tab; build_resize_tab(cols, rows, sl.szw, sl.szh, tab);
         st.mode = tab.mode; st.xmax = tab.xmax;

@@ -32,6 +32,8 @@ struct LbpRoiSteps {
 // the levels of detectMultiScale(cols x rows, sf, min, max) on cascade c, each with its grid and resize tables; tab0: bytes the
 // launch's table blob holds already
 void build_lbp_roi_steps(const LbpCascade &c, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t tab0, LbpRoiSteps &out);
+// the same on the window size alone, which is all of a cascade that the levels read: what the new-format HAAR route (hnew_roi_tables.h) calls
+void build_lbp_roi_steps(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t tab0, LbpRoiSteps &out);
 // A step's rows are independent of one another: a step with more grid positions than the queues hold goes out as several records,
 // a band of whole rows each, all with the step's number in the key.  false: a single grid row is longer than the queues.
 bool roi_split_bands(std::vector<RoiStep> &steps);

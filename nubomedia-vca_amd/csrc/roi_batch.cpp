@@ -1,8 +1,9 @@
 // roi_batch.cpp -- the small-image path of detectMultiScale: every small job of a round in one k_roi launch (kernels_roi.hip) --
-// the jobs on new-format LBP cascades in one k_roi_lbp launch beside it (kernels_roi_lbp.hip) --, and their candidates handed
+// the jobs on new-format LBP cascades in one k_roi_lbp launch beside it (kernels_roi_lbp.hip), the jobs on new-format HAAR cascades
+// that were opted in (nvca_cascade_set_small_route) in one k_roi_hnew launch (kernels_roi_hnew.hip) --, and their candidates handed
 // back to the jobs.
 #include "host_state.h"
-#include "lbp_roi_tables.h"
+#include "hnew_roi_tables.h"
 #include <cstring>
 #include <algorithm>
 
@@ -19,7 +20,12 @@ static constexpr int kRoiMaxWords = 14848;          // (cols + 1) * (rows + 2) w
 bool roi_eligible(const nvca_ctx *ctx, const DetectJob &j, int njobs_in_round)
 {
     if (!ctx->sw.roi || j.rq.levels) return false;          // (a levels job always takes the large-image evaluator: k_roi_lbp has no last-stages launch)
-    if (j.rq.kind == kJobLbp && j.rq.casc->format != NVCA_CASCADE_LBP) return false;      // a new-format HAAR cascade: neither k_roi nor k_roi_lbp evaluates it
+    if (j.rq.kind == kJobLbp && j.rq.casc->format != NVCA_CASCADE_LBP) {
+        // a new-format HAAR cascade: neither k_roi nor k_roi_lbp evaluates it.  One that was opted in when the job was built takes
+        // k_roi_hnew under the LBP branch's rules, with its own LDS bound (kRoiHnewMaxBytes, hnew_roi_tables.h)
+        if (!j.rq.small_route || j.rq.nimg != 1 || j.rq.image_axis || !hnew_roi_fits_lds(j.rq.cols, j.rq.rows)) return false;
+        return j.rq.mem == NVCA_MEM_DEVICE || njobs_in_round == 1;              // a host image is staged in the lane's one gray buffer
+    }
     if (j.rq.kind == kJobLbp) {
         // a new-format LBP cascade (its Haar model is empty): ONE image whose working set fits k_roi_lbp's LDS (kRoiLbpMaxBytes,
         // lbp_roi_tables.h); a job of several images, and every job of the _batch entry points, keeps the image axis of the
@@ -60,6 +66,20 @@ static const StageRec *roi_lbp_recs(nvca_ctx *ctx, const nvca_cascade *casc)
     ctx->roi_stage_recs[casc->c.uid] = d.release();
     return p;
 }
+// ... and for k_roi_hnew (hnew_roi_tables.cpp), in the same cache: a cascade has one format
+static const StageRec *roi_hnew_recs(nvca_ctx *ctx, const nvca_cascade *casc)
+{
+    auto it = ctx->roi_stage_recs.find(casc->c.uid);
+    if (it != ctx->roi_stage_recs.end()) return it->second->as<StageRec>();
+    std::vector<unsigned char> blob; build_hnew_roi_table(casc->hnew, blob);
+    std::unique_ptr<DevBuf> d(new DevBuf());
+    if (d->ensure(blob.size()) || hipMemcpy(d->p, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        d->release(); ctx->set_error("allocation failed (HAAR cascade records)"); return nullptr;
+    }
+    const StageRec *p = d->as<StageRec>();
+    ctx->roi_stage_recs[casc->c.uid] = d.release();
+    return p;
+}
 static ScaleTable *roi_table(nvca_ctx *ctx, RoiBatch &rb, const Cascade &c, double factor)
 {
     ScaleTable *t = get_scale_table(ctx, c, factor);
@@ -78,8 +98,8 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
     const Cascade &c = j.rq.casc->c;
     const int cols = j.rq.cols, rows = j.rq.rows;
     j.sm.fused = false;
-    const bool lbp = j.rq.kind == kJobLbp;
-    const StageRec *d_stages = lbp ? roi_lbp_recs(ctx, j.rq.casc) : roi_stage_recs(ctx, c);
+    const bool lbp = j.rq.kind == kJobLbp, hnew = lbp && j.rq.casc->format == NVCA_CASCADE_HAAR_NEW;      // (lbp: either new-format evaluator)
+    const StageRec *d_stages = hnew ? roi_hnew_recs(ctx, j.rq.casc) : lbp ? roi_lbp_recs(ctx, j.rq.casc) : roi_stage_recs(ctx, c);
     if (!d_stages) return NVCA_ERR_NOMEM;
     std::vector<RoiStep> steps; std::vector<DetectJob::RoiStepInfo> info; std::vector<unsigned char> tabs;
     const size_t tab0 = rb.tabs.size();
@@ -92,8 +112,10 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
         // the levels of detectMultiScale on a new-format cascade, each with its cv::resize tables (lbp_roi_tables.cpp); a candidate maps
         // to its rectangle as a CV_HAAR_SCALE_IMAGE level's does: (cvRound(x f), cvRound(y f), cvRound(ow f), cvRound(oh f))
         LbpRoiSteps ls;
-        build_lbp_roi_steps(j.rq.casc->lbp, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, tab0, ls);
+        build_lbp_roi_steps(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, tab0, ls);      // (c holds the window of either model)
         fits = ls.fits;
+        // HaarEvaluator::setImage's normrect (1, 1, ow - 2, oh - 2), in the record's variance rectangle
+        if (hnew) for (RoiStep &st : ls.steps) { st.ex = 1; st.ey = 1; st.ew = c.ow - 2; st.eh = c.oh - 2; }
         steps.swap(ls.steps); tabs.swap(ls.tabs); lev_bytes = ls.lev_bytes; lbp_plane_words = ls.plane_words;
         for (const LbpRoiLevel &l : ls.info) info.push_back(DetectJob::RoiStepInfo{0., l.factor, l.winw, l.winh, -1});
         j.q.phase = kJobFirstQueued;
@@ -176,23 +198,27 @@ int roi_add_job(nvca_ctx *ctx, RoiBatch &rb, DetectJob &j)
             if ((rc = stage_2d(ctx, ctx->ws->ln().gray.p, g.gpitch, j.rq.img[0], j.rq.stride, cols, rows, j.rq.mem))) return rc;
             d.img = ctx->ws->ln().gray.as<uint8_t>(); d.stride = g.gpitch;
         }
-        std::vector<RoiStep> &all = lbp ? rb.lbp_steps : rb.steps;        // (k_roi_lbp's records apart: each kernel is launched on its own)
-        d.first_step = (int)all.size(); d.nsteps = (int)steps.size(); d.scale_image = lbp ? 2 : j.rq.kind == kJobScaleImage;
-        d.stages = d_stages; d.nstages = lbp ? (int)j.rq.casc->lbp.stages.size() : (int)c.stages.size(); d.pair_policy = ctx->policy == NVCA_SUM_F32PAIR; d.slot = (int)rb.jobs.size();
+        std::vector<RoiStep> &all = hnew ? rb.hnew_steps : lbp ? rb.lbp_steps : rb.steps;        // (k_roi_lbp's and k_roi_hnew's records apart: each kernel is launched on its own)
+        d.first_step = (int)all.size(); d.nsteps = (int)steps.size(); d.scale_image = hnew ? 3 : lbp ? 2 : j.rq.kind == kJobScaleImage;
+        d.stages = d_stages; d.nstages = hnew ? (int)j.rq.casc->hnew.stages.size() : lbp ? (int)j.rq.casc->lbp.stages.size() : (int)c.stages.size(); d.pair_policy = ctx->policy == NVCA_SUM_F32PAIR; d.slot = (int)rb.jobs.size();
         for (RoiStep &st : steps) st.job = d.slot;
         all.insert(all.end(), steps.begin(), steps.end());
         rb.jobs.push_back(d); rb.owners.push_back(&j); rb.owner_img.push_back(k);
     }
-    if (lbp) { rb.lbp_plane_words = std::max(rb.lbp_plane_words, (lbp_plane_words + 3) & ~3); rb.lbp_lev_bytes = std::max(rb.lbp_lev_bytes, lev_bytes); }
+    if (hnew) rb.hnew_plane_words = std::max(rb.hnew_plane_words, (lbp_plane_words + 3) & ~3);
+    else if (lbp) { rb.lbp_plane_words = std::max(rb.lbp_plane_words, (lbp_plane_words + 3) & ~3); rb.lbp_lev_bytes = std::max(rb.lbp_lev_bytes, lev_bytes); }
     else { rb.plane_words = std::max(rb.plane_words, (cols + 1) * (rows + 2)); rb.lev_bytes = std::max(rb.lev_bytes, lev_bytes); }
     return NVCA_OK;
 }
-// upload the round's tables and launch k_roi (the Haar jobs' steps) and k_roi_lbp (the LBP jobs') on the current lane
+// upload the round's tables and launch k_roi (the Haar jobs' steps), k_roi_lbp (the LBP jobs') and k_roi_hnew (the opted-in new-format
+// HAAR jobs') on the current lane
 int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap)
 {
     const int nj = (int)rb.jobs.size();
-    const size_t jb = (size_t)nj * sizeof(RoiJobDev), sb = rb.steps.size() * sizeof(RoiStep), lb = rb.lbp_steps.size() * sizeof(RoiStep);
-    const size_t o_steps = (jb + 255) & ~(size_t)255, o_lsteps = (o_steps + sb + 255) & ~(size_t)255, o_tabs = (o_lsteps + lb + 255) & ~(size_t)255,
+    const size_t jb = (size_t)nj * sizeof(RoiJobDev), sb = rb.steps.size() * sizeof(RoiStep), lb = rb.lbp_steps.size() * sizeof(RoiStep),
+                 hb = rb.hnew_steps.size() * sizeof(RoiStep);
+    const size_t o_steps = (jb + 255) & ~(size_t)255, o_lsteps = (o_steps + sb + 255) & ~(size_t)255, o_hsteps = (o_lsteps + lb + 255) & ~(size_t)255,
+                 o_tabs = (o_hsteps + hb + 255) & ~(size_t)255,
                  total = o_tabs + rb.tabs.size() + 64;
     // the list starts at a quarter of a million candidates for the whole launch however many jobs share it; a launch that
     // overflows it is queued again with the exact size (run_detect_jobs raises hit_cap for the rest of the call)
@@ -208,20 +234,25 @@ int roi_launch(nvca_ctx *ctx, RoiBatch &rb, bool full_cap)
     memcpy(h, rb.jobs.data(), jb);
     if (sb) memcpy(h + o_steps, rb.steps.data(), sb);
     if (lb) memcpy(h + o_lsteps, rb.lbp_steps.data(), lb);
+    if (hb) memcpy(h + o_hsteps, rb.hnew_steps.data(), hb);
     if (!rb.tabs.empty()) memcpy(h + o_tabs, rb.tabs.data(), rb.tabs.size());
     NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().tables.p, h, total - 64, hipMemcpyHostToDevice, ctx->cs()));
     NVCA_HIP_CHECK(ctx, hipMemsetAsync(ctx->rbuf().hits.p, 0, sizeof(unsigned long long), ctx->cs()));
     const int lds = rb.plane_words * 8 + kRoiMaxWin * (8 + 2 + 2) + 16 + ((rb.lev_bytes + 15) & ~15) + 64;      // k_roi's carve-up
     const int lbp_lds = roi_lbp_lds_bytes(rb.lbp_plane_words, rb.lbp_lev_bytes);                                 // k_roi_lbp's
+    const int hnew_lds = roi_hnew_lds_bytes(rb.hnew_plane_words);                                                // k_roi_hnew's
+    if (const int e = hb ? roi_hnew_grant_lds(hnew_lds) : 0) { ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e)); return NVCA_ERR_HIP; }
     if (const int e = sb ? roi_grant_lds(lds) : 0) { ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e)); return NVCA_ERR_HIP; }
     if (const int e = lb ? roi_lbp_grant_lds(lbp_lds) : 0) { ctx->set_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString((hipError_t)e)); return NVCA_ERR_HIP; }
     const unsigned char *d = ctx->rbuf().tables.as<unsigned char>();
-    // the Haar jobs' steps and the LBP jobs' steps: two kernels on one lane, one job table, one candidate list, one wait
+    // the Haar jobs' steps, the LBP jobs' and the new-format HAAR jobs': three kernels on one lane, one job table, one candidate list, one wait
     { TimedLaunch t(ctx, NVCA_K_ROI);
       if (sb) launch_roi(ctx->cs(), (const RoiJobDev *)d, (int)rb.steps.size(), (const RoiStep *)(d + o_steps), d + o_tabs, ctx->rbuf().hits.as<unsigned long long>(), rb.cap, rb.plane_words, lds,
                  ctx->rbuf().rej.as<unsigned long long>());
       if (lb) launch_roi_lbp(ctx->cs(), (const RoiJobDev *)d, (int)rb.lbp_steps.size(), (const RoiStep *)(d + o_lsteps), d + o_tabs, ctx->rbuf().hits.as<unsigned long long>(), rb.cap,
-                             rb.lbp_plane_words, lbp_lds); }
+                             rb.lbp_plane_words, lbp_lds);
+      if (hb) launch_roi_hnew(ctx->cs(), (const RoiJobDev *)d, (int)rb.hnew_steps.size(), (const RoiStep *)(d + o_hsteps), d + o_tabs, ctx->rbuf().hits.as<unsigned long long>(), rb.cap,
+                              rb.hnew_plane_words, hnew_lds); }
     if (rb.rej_words) NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().h_rej.p, ctx->rbuf().rej.p, rb.rej_words * 8, hipMemcpyDeviceToHost, ctx->cs()));
     NVCA_LAUNCH_CHECK(ctx);
     NVCA_HIP_CHECK(ctx, hipMemcpyAsync(ctx->rbuf().h_hits.p, ctx->rbuf().hits.p, (first + 1) * 8, hipMemcpyDeviceToHost, ctx->cs()));

@@ -101,6 +101,7 @@ SYMBOLS = [
     "nvca_part_batch_submit", "nvca_part_batch_collect", "nvca_face_stream_set_input", "nvca_yuv420_to_bgr",
     "nvca_part_stream_set_input", "nvca_tracker_set_input", "nvca_bgr_to_yuv420", "nvca_draw_shapes_yuv420",
     "nvca_overlay_blend_yuv420", "nvca_cascade_format", "nvca_cascade_dump_lbp", "nvca_cascade_dump_haar_new",
+    "nvca_cascade_set_small_route", "nvca_cascade_get_small_route",
 ]
 
 _lib = None
@@ -172,6 +173,9 @@ def load():
     L.nvca_integral_tilted.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
     L.nvca_cascade_kind.argtypes = [vp, ip, ip]
     L.nvca_cascade_format.argtypes = [vp, ip, ip]
+    if hasattr(L, "nvca_cascade_set_small_route"):      # (NVCA_LIB may name an older library: A/B runs against a parent commit)
+        L.nvca_cascade_set_small_route.argtypes = [vp, C.c_int]
+        L.nvca_cascade_get_small_route.argtypes = [vp, ip]
     L.nvca_cascade_dump_lbp.argtypes = [vp, ip, ip, C.POINTER(C.c_int32), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
     L.nvca_cascade_dump_haar_new.argtypes = [vp, ip, C.POINTER(C.c_float), ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
     L.nvca_detect_multiscale.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
@@ -588,6 +592,16 @@ class Cascade:
         f, n = C.c_int(), C.c_int()
         self.ctx.check(self.ctx.L.nvca_cascade_format(self.h, C.byref(f), C.byref(n)))
         return f.value, n.value
+
+    def set_small_route(self, on):
+        """opt a new-format HAAR cascade into (or out of) the small-image route; nothing changes on the other formats"""
+        self.ctx.check(self.ctx.L.nvca_cascade_set_small_route(self.h, int(bool(on))))
+
+    def small_route(self):
+        """whether small images of this cascade may take a one-launch route (always True for old-format and LBP cascades)"""
+        v = C.c_int()
+        self.ctx.check(self.ctx.L.nvca_cascade_get_small_route(self.h, C.byref(v)))
+        return bool(v.value)
 
     def dump_lbp(self):
         """an LBP cascade as the loader keeps it (stage thresholds as evaluated, after the 1e-5f); ERR_ARG for an old-format cascade"""
