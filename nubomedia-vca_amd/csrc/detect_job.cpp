@@ -44,8 +44,9 @@ static int si_plan(nvca_ctx *ctx, const DetectJob &j, GeomPlan **out)
     GeomPlan *pp = find_plan(ctx, key);
     if (!pp) {
         std::unique_ptr<GeomPlan> np(new GeomPlan());
-        // (a plan holds at most 63 levels.  The pyramid's two halves apart: the scan tables go to the device between them)
-        if ((rc = pyr_plan_tabs(ctx, *np, cols, rows, si_levels(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, 63)))) return rc;
+        // (a plan holds every level the call has: build_custom sizes the candidate key for them and refuses, loudly, what no key holds.
+        // The pyramid's two halves apart: the scan tables go to the device between them)
+        if ((rc = pyr_plan_tabs(ctx, *np, cols, rows, si_levels(c.ow, c.oh, cols, rows, j.rq.sf, j.rq.minw, j.rq.minh, j.rq.maxw, j.rq.maxh, kMaxPyrLevels + 1)))) return rc;
         if (!np->lv.empty()) {
             std::vector<ScaleSpec> specs;
             for (const PyrLevel &L : np->lv) specs.push_back(level_spec(np->P, L, c.ow, c.oh, 0));

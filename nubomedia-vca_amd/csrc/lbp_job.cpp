@@ -26,7 +26,8 @@ int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double
     GeomPlan *pp = find_plan(ctx, key);
     if (!pp) {
         std::unique_ptr<GeomPlan> np(new GeomPlan());
-        if ((rc = pyr_plan_init(ctx, *np, cols, rows, lbp_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, 63)))) return rc;
+        // every level the call has: build_scan_tables sizes the candidate key for them and refuses, loudly, what no key holds
+        if ((rc = pyr_plan_init(ctx, *np, cols, rows, lbp_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, kMaxPyrLevels + 1)))) return rc;
         if (!np->lv.empty()) {
             // the scan grids: what hit_valid / hit_rect check and map a candidate key with
             for (const PyrLevel &L : np->lv) np->det.specs.push_back(level_spec(np->P, L, ow, oh, 1));

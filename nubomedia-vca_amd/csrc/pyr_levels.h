@@ -7,6 +7,11 @@
 
 namespace nvca {
 
+// The most levels a plan of the large-image routes holds.  OpenCV's loop has no bound (a scale factor just above 1 makes it as long as
+// one likes); a call with more levels is refused with NVCA_ERR_ARG, never answered from its first levels.  The callers ask for one
+// level more than this, so that "too many" shows.
+constexpr size_t kMaxPyrLevels = 4095;
+
 // the pyramid levels of a CV_HAAR_SCALE_IMAGE call, smallest factor first, at most `cap` of them
 struct SiLevel { double factor; int szw, szh, winw, winh; };
 std::vector<SiLevel> si_levels(int ow, int oh, int cols, int rows, double sf, int minw, int minh, int maxw, int maxh, size_t cap);

@@ -1,6 +1,7 @@
 // pyramid.cpp -- the image pyramid of the CV_HAAR_SCALE_IMAGE and new-format LBP scans on the device: a plan's layout (pyr_levels.h),
 // resize tables and level table, a level's scan grid, and the launches that resize a job's images to every level and integrate them.
 #include "host_state.h"
+#include <climits>
 #include <cstring>
 #include <algorithm>
 
@@ -11,7 +12,11 @@ namespace nvca {
 // the plan's pyramid for a cols x rows image: the layout of `levels` and every level's resize table, the tables on the device
 int pyr_plan_tabs(nvca_ctx *ctx, GeomPlan &np, int cols, int rows, const std::vector<SiLevel> &levels)
 {
+    // What a plan cannot hold is refused here, before anything is built: a call is answered from all of its levels or not at all.
+    if (levels.size() > kMaxPyrLevels) { ctx->set_error("scan too large: more than 4095 pyramid levels (a scale factor this close to 1)"); return NVCA_ERR_ARG; }
     PyrLayout lay = pyr_layout(levels, cols);
+    // (a level's planes lie at an int offset: PyrLevel::plane_off, LbpLevelDev, ScaleSpec)
+    if (lay.plane_total > (size_t)INT_MAX) { ctx->set_error("scan too large: the pyramid's integral planes pass 2^31 elements an image"); return NVCA_ERR_ARG; }
     np.P = lay.P; np.gray_total = lay.gray_total; np.plane_total = lay.plane_total; np.lv = std::move(lay.lv);
     for (const PyrLevel &L : np.lv) {
         std::unique_ptr<GeomPlan> gp(new GeomPlan());
@@ -101,6 +106,8 @@ int pyr_build(nvca_ctx *ctx, const PyrSource &src, int cols, int rows, int nimg,
     int rc;
     const int P = pp->P;
     const size_t gray_total = pp->gray_total, plane_total = pp->plane_total;
+    // (the one-launch resize has a (level, image) pair in grid.z, which ends at 65535)
+    if (pp->pyr_ok && pp->lv.size() * (size_t)nimg > 65535) { ctx->set_error("scan too large: pyramid levels x images of one job beyond 65535"); return NVCA_ERR_ARG; }
     if (ws.ln().aux.ensure(gray_total * nimg + 64) || ws.ln().sum.ensure((plane_total * nimg + 4 * (size_t)P) * sizeof(int)) || ws.ln().sqsum.ensure(plane_total * nimg * sizeof(unsigned long long)) ||
         (has_tilted && ws.ln().tilted.ensure((plane_total * nimg + 4 * (size_t)P) * sizeof(int)))) {
         ctx->set_error("allocation failed (pyramid)"); return NVCA_ERR_NOMEM;

@@ -54,7 +54,7 @@ int main(int argc, char **argv)
                rc ? 0 : (int)(hnew ? c.hnew.weak.size() : lbp ? c.lbp.weak.size() : c.haar.cls.size()), err.empty() ? "false" : "true", rc ? 0 : sum);
         if (hnew) {
             const int cols = c.hnew.ow > 30 ? 3 * c.hnew.ow : 97, rows = c.hnew.oh > 30 ? 3 * c.hnew.oh : 83;
-            const PyrLayout lay = pyr_layout(lbp_levels(c.hnew.ow, c.hnew.oh, cols, rows, 1.2, 0, 0, cols, rows, 63), cols);
+            const PyrLayout lay = pyr_layout(lbp_levels(c.hnew.ow, c.hnew.oh, cols, rows, 1.2, 0, 0, cols, rows, kMaxPyrLevels + 1), cols);
             HnewTables t; std::string terr;
             const int trc = lay.lv.empty() ? -1 : build_hnew_tables(c.hnew, lay.lv, lay.P, t, terr);
             printf(", \"tables\": {\"rc\": %d, \"P\": %d, \"TP\": %d, \"levels\": %zu, \"tiles\": %zu, \"stages\": %zu, \"tile_stages\": %d, \"lds\": %d, \"scan_weak\": %zu, "

@@ -1,7 +1,7 @@
 // lbp_group_tables_driver.cpp -- the tables k_group reads on a new-format LBP scan (csrc/lbp_tables.cpp: a ScaleRec per pyramid level and
 // the levels' output coordinates) under AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program built without any HIP
 // include path: tests/test_lbp_streams_cpu.py hands it a manifest and checks every line it prints.  Manifest lines:
-//   scan ID XML cols rows sf minw minh maxw maxh      lbp_levels(..., 63) -> pyr_layout -> build_lbp_tables
+//   scan ID XML cols rows sf minw minh maxw maxh      lbp_levels(..., every level) -> pyr_layout -> build_lbp_tables
 // One JSON line per case: the key layout, per level [factor, step, nx, ny] and the ScaleRec fields k_group and its launch use, the
 // position table, and whether every field k_group does not read is zero.
 #include "lbp_tables.h"
@@ -32,7 +32,7 @@ int main(int argc, char **argv)
         const std::string text = ss.str();
         CascadeFile c; std::string err;
         if (parse_cascade_file(text.data(), text.size(), c, err) || c.format != NVCA_CASCADE_LBP) { fprintf(stderr, "%s: not a new-format LBP cascade (%s)\n", path.c_str(), err.c_str()); return 2; }
-        const PyrLayout lay = pyr_layout(lbp_levels(c.lbp.ow, c.lbp.oh, cols, rows, sf, minw, minh, maxw, maxh, 63), cols);
+        const PyrLayout lay = pyr_layout(lbp_levels(c.lbp.ow, c.lbp.oh, cols, rows, sf, minw, minh, maxw, maxh, kMaxPyrLevels + 1), cols);
         LbpTables t;
         const int rc = lay.lv.empty() ? 0 : build_lbp_tables(c.lbp, lay.lv, lay.P, t, err);
         printf("{\"case\": \"%s\", \"rc\": %d, \"key_sy\": %d, \"key_ss\": %d, \"levels\": [", id.c_str(), rc, t.key_sy, t.key_ss);

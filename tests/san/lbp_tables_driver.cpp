@@ -1,7 +1,7 @@
 // lbp_tables_driver.cpp -- the pyramid rules (csrc/pyr_levels.cpp) and the LBP table builder (csrc/lbp_tables.cpp) on the loader's
 // cascades (csrc/cascade_xml.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone program built without any HIP
 // include path: tests/test_lbp_tables_cpu.py hands it a manifest and checks every line it prints.  Manifest lines:
-//   scan   ID XML cols rows sf minw minh maxw maxh      lbp_levels(..., 63) -> pyr_layout -> build_lbp_tables
+//   scan   ID XML cols rows sf minw minh maxw maxh      lbp_levels(..., every level) -> pyr_layout -> build_lbp_tables
 //   levels ID XML n szw szh [szw szh ...]               the same from a level list given directly (factor 1, the cascade's window)
 //   rules  ID ow oh cols rows sf minw minh maxw maxh    si_levels beside lbp_levels
 // One JSON line per case.
@@ -91,7 +91,7 @@ int main(int argc, char **argv)
             int cols, rows, minw, minh, maxw, maxh; double sf;
             if (!(in >> path >> cols >> rows >> sf >> minw >> minh >> maxw >> maxh)) { fprintf(stderr, "bad line: %s\n", line.c_str()); return 2; }
             CascadeFile c; load(path, c);
-            tables(id, c.lbp, lbp_levels(c.lbp.ow, c.lbp.oh, cols, rows, sf, minw, minh, maxw, maxh, 63), cols);
+            tables(id, c.lbp, lbp_levels(c.lbp.ow, c.lbp.oh, cols, rows, sf, minw, minh, maxw, maxh, kMaxPyrLevels + 1), cols);
         } else if (verb == "levels") {
             int nl;
             if (!(in >> path >> nl)) { fprintf(stderr, "bad line: %s\n", line.c_str()); return 2; }
@@ -108,8 +108,8 @@ int main(int argc, char **argv)
             int ow, oh, cols, rows, minw, minh, maxw, maxh; double sf;
             if (!(in >> ow >> oh >> cols >> rows >> sf >> minw >> minh >> maxw >> maxh)) { fprintf(stderr, "bad line: %s\n", line.c_str()); return 2; }
             printf("{\"case\": \"%s\", ", id.c_str());
-            put_levels("si", si_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, 63)); printf(", ");
-            put_levels("lbp", lbp_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, 63));
+            put_levels("si", si_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, kMaxPyrLevels + 1)); printf(", ");
+            put_levels("lbp", lbp_levels(ow, oh, cols, rows, sf, minw, minh, maxw, maxh, kMaxPyrLevels + 1));
             printf(", \"steps\": [%d, %d, %d]}\n", level_step(1.), level_step(2.), level_step(2.0000001));
         } else { fprintf(stderr, "unknown verb: %s\n", line.c_str()); return 2; }
         n++;
