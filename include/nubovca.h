@@ -86,6 +86,15 @@ typedef struct nvca_frame {
 #define NVCA_PIX_BGR  0   /* packed, as nvca_frame describes it */
 #define NVCA_PIX_NV12 1   /* plane 0: Y, w x h; plane 1: U,V interleaved, w bytes x h/2 rows */
 #define NVCA_PIX_I420 2   /* plane 0: Y; plane 1: U, w/2 x h/2; plane 2: V, w/2 x h/2 */
+/* (3 is no format: refused with NVCA_ERR_ARG)
+ * Packed 4:2:2, what V4L2 cameras, capture cards and SDI / USB devices emit: ONE plane of 2 bytes a pixel, four bytes a pixel pair,
+ * every row with its own chroma.  A stream that takes them stands for cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) plus the element
+ * (in row y, pixels 2k and 2k + 1 take U and V from the same four bytes; the arithmetic is A.13's).  Plane 0 only:
+ * offset[0] and stride[0] >= 2 * width; offset[1..2] and stride[1..2] are ignored (a stream stores them as zero).  The width must be
+ * even; the height is any positive number. */
+#define NVCA_PIX_YUY2 4   /* bytes Y0 U Y1 V (YUYV) */
+#define NVCA_PIX_UYVY 5   /* bytes U Y0 V Y1 */
+#define NVCA_PIX_YVYU 6   /* bytes Y0 V Y1 U */
 typedef struct nvca_pixel_layout {
     int    format;          /* NVCA_PIX_* */
     size_t offset[3];       /* byte offset of each plane from nvca_frame.data */
@@ -239,6 +248,13 @@ int nvca_resize_linear(nvca_ctx *ctx, const void *src, int sw, int sh, int sstri
  * layout's offsets count from; w x h: the luma size, both even; src and dst are both host or both device memory (mem);
  * dst_bgr: packed BGR rows dst_stride bytes apart. */
 int nvca_yuv420_to_bgr(nvca_ctx *ctx, const void *base, int w, int h, const nvca_pixel_layout *layout, int mem,
+                       void *dst_bgr, int dst_stride);
+/* cv::cvtColor(CV_YUV2BGR_YUY2 / CV_YUV2BGR_UYVY / CV_YUV2BGR_YVYU), the sibling of nvca_yuv420_to_bgr for packed 4:2:2 buffers
+ * (layout->format NVCA_PIX_YUY2 / _UYVY / _YVYU; anything else, a null layout included, is NVCA_ERR_ARG): BT.601 limited range,
+ * integer, SURVEY.md A.18.  base: the buffer offset[0] counts from; w: even; h: any positive number; stride[0] >= 2 * w; src and dst
+ * are both host or both device memory (mem); dst_bgr: packed BGR rows dst_stride >= 3 * w bytes apart, only the pixels' own bytes are
+ * written. */
+int nvca_yuv422_to_bgr(nvca_ctx *ctx, const void *base, int w, int h, const nvca_pixel_layout *layout, int mem,
                        void *dst_bgr, int dst_stride);
 /* cv::cvtColor(CV_BGR2YUV_I420), the inverse of nvca_yuv420_to_bgr: what the pipeline's videoconvert behind the element does
  * (FACE/run_plugin.sh:3) when a viewed frame goes on to an encoder.  OpenCV 2.4 color.cpp (RGB888toYUV420pInvoker), BT.601 limited
@@ -408,7 +424,10 @@ int  nvca_face_stream_set_params(nvca_face_stream *s, const nvca_face_params *pa
  * reference's order: resize on BGR, BGR2GRAY, equalizeHist).  layout == NULL or format NVCA_PIX_BGR: back to packed BGR.
  * A frame of a 4:2:0 stream is refused with NVCA_ERR_ARG -- before any stream's frame gate advances -- when its width or
  * height is odd, its stride is not the layout's stride[0], a plane's stride is shorter than its row, or planes overlap;
- * planes may have gaps between them (1080 rows in a 1088-row allocation).  BGR and 4:2:0 streams mix in one batch. */
+ * planes may have gaps between them (1080 rows in a 1088-row allocation).  BGR and 4:2:0 streams mix in one batch.
+ * Packed 4:2:2 frames (NVCA_PIX_YUY2 / _UYVY / _YVYU, cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) in front of :805, SURVEY.md
+ * A.18) are taken by the same rules: refused when the width is odd, stride[0] < 2 * width or the frame's stride is not stride[0]; any
+ * height.  Packed, 4:2:0 and 4:2:2 streams of any byte order mix in one batch. */
 int  nvca_face_stream_set_input(nvca_face_stream *s, const nvca_pixel_layout *layout);
 /* a "motion" custom event arrived (FACE/kmsfacedetect.cpp:680-755): analyse the
  * next NUM_FRAMES_TO_PROCESS (10) frames */
@@ -476,7 +495,9 @@ int  nvca_part_stream_set_params(nvca_part_stream *s, const nvca_part_params *pa
  * from the next nvca_part_stream_process / nvca_part_batch_process / _submit on; a submitted ticket keeps the layout it was submitted
  * with.  Packed, NV12 and I420 streams mix in one call; streams share a frame's upload and work only when the layout is equal too.
  * A frame of a 4:2:0 stream is refused with NVCA_ERR_ARG -- the whole call, before any stream's frame gate advances -- when its
- * width or height is odd, its stride is not the layout's stride[0], a plane's stride is shorter than its row, or planes overlap. */
+ * width or height is odd, its stride is not the layout's stride[0], a plane's stride is shorter than its row, or planes overlap.
+ * Packed 4:2:2 frames (NVCA_PIX_YUY2 / _UYVY / _YVYU: cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) in front of the same order,
+ * SURVEY.md A.18) by the same rules: an even width, any height, stride[0] >= 2 * width; they mix with the others in one call. */
 int  nvca_part_stream_set_input(nvca_part_stream *s, const nvca_pixel_layout *layout);
 /* one upstream "message" worth of faces, original-frame pixels (EYE/kmseyedetect.cpp:680-764) */
 int  nvca_part_stream_push_faces(nvca_part_stream *s, const nvca_rect *faces, int n);
@@ -537,7 +558,9 @@ int  nvca_tracker_set_params(nvca_tracker *t, const nvca_tracker_params *params)
  * nvca_frame.stride is the luma stride (stride >= width * 4 is asked of packed trackers only).  Previous gray image and motion
  * history persist across a format change at the same size.  Packed, NV12 and I420 trackers mix in one nvca_tracker_batch_process
  * (one launch set per size and format).  A bad frame (odd width or height, a stride that is not the layout's stride[0], a plane
- * stride shorter than its row, overlapping planes) refuses the whole call with NVCA_ERR_ARG before any tracker's state advances. */
+ * stride shorter than its row, overlapping planes) refuses the whole call with NVCA_ERR_ARG before any tracker's state advances.
+ * Packed 4:2:2 frames (NVCA_PIX_YUY2 / _UYVY / _YVYU: cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) in front of :356)
+ * by the same rules: an even width, any height (odd ones included), stride[0] >= 2 * width; one launch set per size and byte order. */
 int  nvca_tracker_set_input(nvca_tracker *t, const nvca_pixel_layout *layout);
 /* timestamp_ms: the reference passes 1000*clock()/CLOCKS_PER_SEC (:349) */
 int  nvca_tracker_process(nvca_tracker *t, const nvca_frame *frame_bgra, double timestamp_ms,

@@ -296,7 +296,7 @@ static int face_submit(nvca_ctx *ctx, int n, nvca_face_stream *const *streams, c
               TimedLaunch t(ctx, NVCA_K_GRAY);                             // cvtColor(YUV2BGR) + cv::resize + cvtColor :805-806 (+ histogram)
               const bool wide = launch_gray_yuv(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, yuv_planes(yuv), gp->view(),
                               ws.ln().gray.as<uint8_t>(), ws.ln().hist.as<unsigned>(), nc, frames_yuv_aligned16(frames, idx.data() + s0, nc, *yuv));
-              if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 gray of %d frame(s) %d x %d -> %d x %d: %s\n", nc, f0.width, f0.height, cols, rows, wide ? "k_gray_yuv16" : "k_gray_yuv_generic");
+              if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] %s gray of %d frame(s) %d x %d -> %d x %d: %s\n", yuv_is_422(yuv->format) ? "4:2:2" : "4:2:0", nc, f0.width, f0.height, cols, rows, gray_yuv_kernel_name(yuv->format, wide));
             } else
             { TimedLaunch t(ctx, NVCA_K_GRAY);                             // cv::resize + cvtColor :805-806 (+ histogram)
               launch_gray(ctx->cs(), ws.res[ws.cur_res].srcptrs.as<const uint8_t *>() + gbase + s0, gp->g, gp->view(),

@@ -201,26 +201,8 @@ int check_img(nvca_ctx *ctx, const void *p, int w, int h, int stride, int bpp, i
     return NVCA_OK;
 }
 
-// ---- 4:2:0 layouts (nvca_pixel_layout); the planes' rows, bytes and the frame's extent: yuv_layout.h
-// what is wrong with a w x h frame in this layout (null: nothing) -- the one set of layout rules, for the streams and for the
-// calls that take a host frame without a context
-const char *yuv_layout_fault(const nvca_pixel_layout &l, int w, int h)
-{
-    if (l.format != NVCA_PIX_NV12 && l.format != NVCA_PIX_I420) return "pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420";
-    if (w <= 0 || h <= 0) return "4:2:0 frame: width and height must be positive";
-    if ((w | h) & 1) return "4:2:0 frame: width and height must be even (OpenCV's 4:2:0 conversions assert it)";
-    const int np = yuv_planes_of(l);
-    for (int p = 0; p < np; p++) {
-        if (l.stride[p] <= 0 || (size_t)l.stride[p] < yuv_plane_row_bytes(l, p, w)) return "4:2:0 frame: a plane's stride is shorter than its row";
-        if (l.offset[p] > ((size_t)1 << 40)) return "4:2:0 frame: plane offset out of range";
-    }
-    for (int p = 0; p < np; p++)
-        for (int q = p + 1; q < np; q++) {
-            const size_t a0 = l.offset[p], a1 = a0 + yuv_plane_bytes(l, p, w, h), b0 = l.offset[q], b1 = b0 + yuv_plane_bytes(l, q, w, h);
-            if (a0 < b1 && b0 < a1) return "4:2:0 frame: planes overlap";
-        }
-    return nullptr;
-}
+// ---- 4:2:0 and packed 4:2:2 layouts (nvca_pixel_layout); the planes' rows, bytes, the frame's extent and the layout rules
+// (yuv_layout_fault): yuv_layout.h
 int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h)
 {
     const char *fault = yuv_layout_fault(l, w, h);
@@ -234,7 +216,7 @@ int parse_pixel_layout(nvca_ctx *ctx, const nvca_pixel_layout *layout, nvca_pixe
 {
     nvca_pixel_layout in{};
     if (layout && layout->format != NVCA_PIX_BGR) {
-        if (layout->format != NVCA_PIX_NV12 && layout->format != NVCA_PIX_I420) { ctx->set_error("pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12 or NVCA_PIX_I420"); return NVCA_ERR_ARG; }
+        if (!yuv_is_420(layout->format) && !yuv_is_422(layout->format)) { ctx->set_error("pixel layout: format must be NVCA_PIX_BGR, NVCA_PIX_NV12, NVCA_PIX_I420, NVCA_PIX_YUY2, NVCA_PIX_UYVY or NVCA_PIX_YVYU"); return NVCA_ERR_ARG; }
         in.format = layout->format;
         for (int p = 0; p < yuv_planes_of(*layout); p++) {
             if (layout->stride[p] <= 0) { ctx->set_error("pixel layout: plane strides must be positive"); return NVCA_ERR_ARG; }
@@ -244,18 +226,12 @@ int parse_pixel_layout(nvca_ctx *ctx, const nvca_pixel_layout *layout, nvca_pixe
     out = in;
     return NVCA_OK;
 }
-bool same_layout(const nvca_pixel_layout &a, const nvca_pixel_layout &b)
-{
-    if (a.format != b.format) return false;
-    for (int p = 0; p < 3; p++) if (a.offset[p] != b.offset[p] || a.stride[p] != b.stride[p]) return false;
-    return true;
-}
-// a frame of a 4:2:0 stream against the stream's layout
+// a frame of a 4:2:0 / 4:2:2 stream against the stream's layout
 int check_yuv_frame(nvca_ctx *ctx, const nvca_pixel_layout &l, const nvca_frame &f)
 {
     if (!f.data || (f.mem != NVCA_MEM_HOST && f.mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
     if (check_yuv_layout(ctx, l, f.width, f.height)) return NVCA_ERR_ARG;
-    if (f.stride != l.stride[0]) { if (ctx) ctx->set_error("4:2:0 frame: its stride is not the stride[0] of the stream's layout"); return NVCA_ERR_ARG; }
+    if (f.stride != l.stride[0]) { if (ctx) ctx->set_error(yuv_is_422(l.format) ? "4:2:2 frame: its stride is not the stride[0] of the stream's layout" : "4:2:0 frame: its stride is not the stride[0] of the stream's layout"); return NVCA_ERR_ARG; }
     return NVCA_OK;
 }
 // a host 4:2:0 frame to device memory, plane by plane, each at the caller's offset (gaps between planes are not copied); `dst` holds
@@ -276,7 +252,7 @@ YuvPlanes yuv_planes(const nvca_pixel_layout *l)
 }
 
 // stage `n` source frames (host or device) and return device pointers in ws.srcptrs
-// yuv: the frames are 4:2:0 buffers of this layout (staged with their planes at the caller's offsets)
+// yuv: the frames are 4:2:0 / 4:2:2 buffers of this layout (staged with their planes at the caller's offsets)
 size_t staging_need(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout *yuv)
 {
     size_t need = 0;
@@ -293,15 +269,13 @@ size_t staging_need(const nvca_frame *frames, const int *idx, int n, const nvca_
 static int copy_row_runs(nvca_ctx *ctx, uint8_t *d, const uint8_t *s, size_t stride, size_t row_bytes, size_t rows,
                          size_t first, size_t period, size_t run, size_t count, hipStream_t st)
 {
-    int rc;
-    const size_t pitch = period * stride, start = first * stride;
-    const bool tail = first + (count - 1) * period + run == rows;
-    const size_t full = tail ? count - 1 : count;
-    if (full == 1) { if ((rc = caller_h2d(ctx, d + start, s + start, run * stride, st))) return rc; }       // one run: no pitch to speak of
-    else if (full > 0 && (rc = caller_h2d_rows(ctx, d + start, pitch, s + start, pitch, run * stride, full, st))) return rc;
-    if (tail) {
-        const size_t o = start + full * pitch;
-        if ((rc = caller_h2d(ctx, d + o, s + o, (run - 1) * stride + row_bytes, st))) return rc;
+    RowPiece pc[2];
+    const int np = row_run_pieces(stride, row_bytes, rows, first, period, run, count, pc);
+    for (int k = 0; k < np; k++) {
+        int rc;
+        if (pc[k].n == 1) rc = caller_h2d(ctx, d + pc[k].off, s + pc[k].off, pc[k].width, st);          // one run: no pitch to speak of
+        else rc = caller_h2d_rows(ctx, d + pc[k].off, pc[k].pitch, s + pc[k].off, pc[k].pitch, pc[k].width, pc[k].n, st);
+        if (rc) return rc;
     }
     return NVCA_OK;
 }
@@ -347,7 +321,8 @@ int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n,
             int rc;
             if (yuv) {
                 // plane by plane, each at the caller's offset: whole planes (the staging every 4:2:0 element shares), or the luma rows
-                // the resize reads and exactly the chroma rows those use
+                // the resize reads and exactly the chroma rows those use (packed 4:2:2: its one plane, 2 * w bytes a row; every row
+                // carries its own chroma, so the rows the resize reads are all there is to copy)
                 if (!rows) { if ((rc = caller_h2d_planes(ctx, d, f.data, *yuv, f.width, f.height, st))) return rc; }
                 else for (int p = 0; p < yuv_planes_of(*yuv); p++) {
                     uint8_t *dp = d + yuv->offset[p];
@@ -385,15 +360,8 @@ bool frames_aligned4(const nvca_frame *frames, const int *idx, int n)
     return true;
 }
 
-// 4:2:0 frames of one layout: every plane and stride takes k_gray_yuv16's loads (staged host frames start on 256 bytes)
-bool yuv_layout_aligned16(const nvca_pixel_layout &l)
-{
-    const bool nv12 = l.format == NVCA_PIX_NV12;
-    const size_t cmask = nv12 ? 15 : 7;
-    if ((l.offset[0] & 15) || (l.stride[0] & 15) || (l.offset[1] & cmask) || ((size_t)l.stride[1] & cmask)) return false;
-    if (!nv12 && ((l.offset[2] & 7) || (l.stride[2] & 7))) return false;
-    return true;
-}
+// frames of one 4:2:0 / 4:2:2 layout: the layout (yuv_layout_aligned16, yuv_layout.h) and every device frame's base take the wide gray
+// kernel's loads -- k_gray_yuv16 / k_gray_yuv422_16 (staged host frames start on 256 bytes)
 bool frames_yuv_aligned16(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout &l)
 {
     if (!yuv_layout_aligned16(l)) return false;

@@ -157,15 +157,12 @@ int check_img(nvca_ctx *ctx, const void *p, int w, int h, int stride, int bpp, i
 // 4:2:0 frames (nvca_pixel_layout): a w x h frame against its layout (NVCA_ERR_ARG with an error text) and the layout as the kernels
 // read it (null / BGR: fmt 0); the bytes from its base to the end of its last plane: yuv_layout.h's yuv_extent
 int check_yuv_layout(nvca_ctx *ctx, const nvca_pixel_layout &l, int w, int h);      // (ctx may be null: no error text then)
-const char *yuv_layout_fault(const nvca_pixel_layout &l, int w, int h);
 YuvPlanes yuv_planes(const nvca_pixel_layout *l);
 // what every nvca_*_set_input and every 4:2:0 stream's frame check share: the caller's layout as a stream keeps it, layouts by value,
 // a frame against its stream's layout, a host frame's planes to the device at the caller's offsets
 int parse_pixel_layout(nvca_ctx *ctx, const nvca_pixel_layout *layout, nvca_pixel_layout &out);
-bool same_layout(const nvca_pixel_layout &a, const nvca_pixel_layout &b);
 int check_yuv_frame(nvca_ctx *ctx, const nvca_pixel_layout &l, const nvca_frame &f);     // (ctx may be null)
 int caller_h2d_planes(nvca_ctx *ctx, void *dst, const void *src, const nvca_pixel_layout &l, int w, int h, hipStream_t st);
-bool yuv_layout_aligned16(const nvca_pixel_layout &l);      // every plane offset and stride takes k_gray_yuv16's loads
 size_t staging_need(const nvca_frame *frames, const int *idx, int n, const nvca_pixel_layout *yuv = nullptr);
 int stage_frames(nvca_ctx *ctx, const nvca_frame *frames, const int *idx, int n, int bpp, int r0 = 0, hipStream_t st = nullptr,
                  size_t *off_io = nullptr, const RowCopy *rows = nullptr, const nvca_pixel_layout *yuv = nullptr);

@@ -50,6 +50,7 @@ int nvca_yuv420_to_bgr(nvca_ctx *ctx, const void *base, int w, int h, const nvca
 try {
     NVCA_LOCK_OR_FAIL(ctx);
     if (!base || !layout || !dst || (mem != NVCA_MEM_HOST && mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+    if (yuv_is_422(layout->format)) { ctx->set_error("nvca_yuv420_to_bgr: the layout is packed 4:2:2 (nvca_yuv422_to_bgr converts those)"); return NVCA_ERR_ARG; }
     int rc = check_yuv_layout(ctx, *layout, w, h);
     if (rc) return rc;
     if (dst_stride < w * 3) return NVCA_ERR_ARG;
@@ -71,12 +72,42 @@ try {
 }
 NVCA_API_CATCH(ctx)
 
+// cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU): nvca_yuv420_to_bgr's path with the one packed plane
+int nvca_yuv422_to_bgr(nvca_ctx *ctx, const void *base, int w, int h, const nvca_pixel_layout *layout, int mem, void *dst, int dst_stride)
+try {
+    NVCA_LOCK_OR_FAIL(ctx);
+    if (!base || !layout || !dst || (mem != NVCA_MEM_HOST && mem != NVCA_MEM_DEVICE)) return NVCA_ERR_ARG;
+    if (!yuv_is_422(layout->format)) { ctx->set_error("nvca_yuv422_to_bgr: format must be NVCA_PIX_YUY2, NVCA_PIX_UYVY or NVCA_PIX_YVYU"); return NVCA_ERR_ARG; }
+    int rc = check_yuv_layout(ctx, *layout, w, h);
+    if (rc) return rc;
+    if (dst_stride < w * 3) { ctx->set_error("nvca_yuv422_to_bgr: dst_stride is shorter than a row of 3 * width bytes"); return NVCA_ERR_ARG; }
+    (void)hipSetDevice(ctx->device);
+    nvca_pixel_layout one{};                 // plane 0 only: what the format does not use is ignored
+    one.format = layout->format; one.offset[0] = layout->offset[0]; one.stride[0] = layout->stride[0];
+    const YuvPlanes planes = yuv_planes(&one);
+    if (mem == NVCA_MEM_DEVICE) {          // read and written where they are (ordered on the context's stream)
+        { TimedLaunch t(ctx, NVCA_K_GRAY);
+          launch_yuv422_to_bgr(ctx->cs(), (const uint8_t *)base, w, h, one.stride[0], planes, (uint8_t *)dst, dst_stride); }
+        return finish_device_op(ctx);
+    }
+    Workspace &ws = *ctx->ws;
+    const size_t dp = round_up((size_t)w * 3, 64);
+    if (ws.ln().aux.ensure(dp * h + 64)) { ctx->set_error("allocation failed"); return NVCA_ERR_NOMEM; }
+    nvca_frame f{base, w, h, one.stride[0], mem, 0};
+    if ((rc = stage_frames(ctx, &f, nullptr, 1, 1, 0, nullptr, nullptr, nullptr, &one))) return rc;
+    { TimedLaunch t(ctx, NVCA_K_GRAY);
+      launch_yuv422_to_bgr(ctx->cs(), ws.res[ws.cur_res].staging.as<uint8_t>(), w, h, one.stride[0], planes, ws.ln().aux.as<uint8_t>(), (int)dp); }
+    return unstage_2d(ctx, dst, dst_stride, ws.ln().aux.p, dp, (size_t)w * 3, h, mem);
+}
+NVCA_API_CATCH(ctx)
+
 int nvca_bgr_to_yuv420(nvca_ctx *ctx, const void *src, int w, int h, int stride, int channels, int mem, void *base, const nvca_pixel_layout *layout)
 try {
     NVCA_LOCK_OR_FAIL(ctx);
     if (channels != 3 && channels != 4) return NVCA_ERR_ARG;
     int rc = check_img(ctx, src, w, h, stride, channels, mem);
     if (rc || !base || !layout) return NVCA_ERR_ARG;
+    if (yuv_is_422(layout->format)) { ctx->set_error("nvca_bgr_to_yuv420: the layout must be NVCA_PIX_NV12 or NVCA_PIX_I420 (the way out is 4:2:0 only)"); return NVCA_ERR_ARG; }
     if ((rc = check_yuv_layout(ctx, *layout, w, h))) return rc;
     (void)hipSetDevice(ctx->device);
     const YuvPlanes planes = yuv_planes(layout);
@@ -244,6 +275,7 @@ NVCA_API_CATCH(ctx)
 static int check_yuv_target(nvca_ctx *ctx, const nvca_frame *frame, const nvca_pixel_layout *layout)
 {
     if (!frame || !layout) return NVCA_ERR_ARG;
+    if (yuv_is_422(layout->format)) { if (ctx) ctx->set_error("drawing on a frame: the layout must be NVCA_PIX_NV12 or NVCA_PIX_I420 (the way out is 4:2:0 only)"); return NVCA_ERR_ARG; }
     if (!ctx && frame->mem != NVCA_MEM_HOST) return NVCA_ERR_ARG;
     return check_yuv_frame(ctx, *layout, *frame);
 }

@@ -208,9 +208,110 @@ __global__ __launch_bounds__(256) void k_gray_yuv_generic(
     if (hist) hist_flush(lh, hist + slot * 256, tid);
 }
 
+// ---- packed 4:2:2 sources (YUY2 / UYVY / YVYU face streams, the eye chain's gray image): cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU)
+// in front of FACE/kmsfacedetect.cpp:805, computed where the frame is read (the fetches: yuv_device.h).
+// K1 at full resolution, beside k_gray_yuv16: a thread owns 16 pixels of ONE row -- every row carries its own chroma -- and reads them
+// with two 16-byte loads of the packed row (8 pixel pairs, a word each), one 16-byte gray store.  Units are numbered along the rows and
+// on from row to row; the unit at the end of a row that holds fewer than 16 pixels goes byte by byte.  Wants the base, the offset and
+// the stride 16-byte aligned (launch_gray_yuv sends anything else to k_gray_yuv422_generic).
+template <int FMT>
+__global__ __launch_bounds__(256) void k_gray_yuv422_16(
+    const uint8_t *const *__restrict__ srcs, PreGeom g, YuvPlanes p, uint8_t *__restrict__ gray, unsigned *__restrict__ hist)
+{
+    __shared__ unsigned lh[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6, slot = blockIdx.z;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    const uint8_t *__restrict__ src = srcs[slot];
+    const int upr = (g.w + 15) >> 4;                        // units per row
+    const int unit = blockIdx.x * 256 + tid;
+    if (unit < upr * g.h) {
+        const int y = unit / upr, x = (unit - y * upr) << 4;
+        const uint8_t *row = src + p.off_y + (size_t)y * g.sstride + 2 * (size_t)x;
+        uint8_t *go = gray + (size_t)slot * g.gray_slot + (size_t)y * g.gpitch + x;
+        if (x + 16 <= g.w) {
+            const uint4 a = *(const uint4 *)row, b = *(const uint4 *)(row + 16);
+            const unsigned pw[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            unsigned o[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const ChromaTerm c = chroma_of_pair<FMT>(pw[k]);
+                const int v0 = yuv_gray(luma_of_pair<FMT>(pw[k], 0), c), v1 = yuv_gray(luma_of_pair<FMT>(pw[k], 1), c);
+                o[k >> 1] |= ((unsigned)v0 | ((unsigned)v1 << 8)) << ((k & 1) * 16);
+                if (hist) { atomicAdd(&lh[wave][v0], 1u); atomicAdd(&lh[wave][v1], 1u); }
+            }
+            *(uint4 *)go = make_uint4(o[0], o[1], o[2], o[3]);
+        } else {
+            for (int k = 0; x + k < g.w; k++) {             // (the width is even: whole pairs; the term of a pair is formed for each of its pixels here)
+                ChromaTerm c;
+                const int Y = yuv422_at<FMT>(src, p, g.sstride, y, x + k, c), v = yuv_gray(Y, c);
+                go[k] = (uint8_t)v;
+                if (hist) atomicAdd(&lh[wave][v], 1u);
+            }
+        }
+    }
+    if (hist) hist_flush(lh, hist + slot * 256, tid);
+}
+
+// K1 generic for packed 4:2:2 frames, beside k_gray_yuv_generic: one output pixel per thread, any resize mode, any alignment; every
+// tap of the resize is a converted pixel
+template <int FMT>
+__global__ __launch_bounds__(256) void k_gray_yuv422_generic(
+    const uint8_t *const *__restrict__ srcs, PreGeom g, YuvPlanes p, ResizeView t,
+    uint8_t *__restrict__ gray, unsigned *__restrict__ hist)
+{
+    __shared__ unsigned lh[4][256];
+    const int tid = threadIdx.x, wave = tid >> 6, slot = blockIdx.z;
+    for (int i = tid; i < 1024; i += 256) (&lh[0][0])[i] = 0;
+    __syncthreads();
+    const uint8_t *__restrict__ src = srcs[slot];
+    const int x = blockIdx.x * 256 + tid;
+    uint8_t *grow = gray + (size_t)slot * g.gray_slot;
+    auto tap = [&](int r, int c, int *v) {
+        ChromaTerm ct;
+        const int Y = yuv422_at<FMT>(src, p, g.sstride, r, c, ct);
+        yuv_bgr(Y, ct, v[0], v[1], v[2]);
+    };
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= g.h) break;
+        if (x < g.w) {
+            int c[3];
+            resize_sample<3>(tap, g.sh, t, x, y, c);
+            const int v = gray_of(c[0] & 255, c[1] & 255, c[2] & 255);
+            grow[(size_t)y * g.gpitch + x] = (uint8_t)v;
+            if (hist) atomicAdd(&lh[wave][v], 1u);
+        }
+    }
+    if (hist) hist_flush(lh, hist + slot * 256, tid);
+}
+
+template <int FMT>
+static bool launch_gray_yuv422(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, const ResizeView &t,
+                               uint8_t *gray, unsigned *hist, int batch, bool aligned16)
+{
+    if (t.mode == 0 && aligned16) {
+        const int units = ((g.w + 15) >> 4) * g.h;
+        NVCA_LAUNCH(k_gray_yuv422_16<FMT>, dim3((units + 255) / 256, 1, batch), dim3(256), 0, st, d_src, g, p, gray, hist);
+        return true;
+    }
+    dim3 grid((g.w + 255) / 256, (g.h + kGrayRows - 1) / kGrayRows, batch);
+    NVCA_LAUNCH(k_gray_yuv422_generic<FMT>, grid, dim3(256), 0, st, d_src, g, p, t, gray, hist);
+    return false;
+}
+
+const char *gray_yuv_kernel_name(int fmt, bool wide)
+{
+    if (fmt >= NVCA_PIX_YUY2) return wide ? "k_gray_yuv422_16" : "k_gray_yuv422_generic";
+    return wide ? "k_gray_yuv16" : "k_gray_yuv_generic";
+}
+
 bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, const ResizeView &t,
                      uint8_t *gray, unsigned *hist, int batch, bool aligned16)
 {
+    if (p.fmt == NVCA_PIX_YUY2) return launch_gray_yuv422<NVCA_PIX_YUY2>(st, d_src, g, p, t, gray, hist, batch, aligned16);
+    if (p.fmt == NVCA_PIX_UYVY) return launch_gray_yuv422<NVCA_PIX_UYVY>(st, d_src, g, p, t, gray, hist, batch, aligned16);
+    if (p.fmt == NVCA_PIX_YVYU) return launch_gray_yuv422<NVCA_PIX_YVYU>(st, d_src, g, p, t, gray, hist, batch, aligned16);
     if (t.mode == 0 && aligned16) {
         const int units = ((g.w + 15) >> 4) * (g.h >> 1);
         dim3 grid((units + 255) / 256, 1, batch);
@@ -255,6 +356,36 @@ void launch_yuv420_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int 
     dim3 grid((w / 2 + 255) / 256, (h / 2 + kGrayRows - 1) / kGrayRows, 1);
     if (p.fmt == 1) NVCA_LAUNCH(k_yuv420_to_bgr<1>, grid, dim3(256), 0, st, src, w, h, ystride, p, dst, dstride);
     else            NVCA_LAUNCH(k_yuv420_to_bgr<2>, grid, dim3(256), 0, st, src, w, h, ystride, p, dst, dstride);
+}
+
+// ---- cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) as a primitive (nvca_yuv422_to_bgr): a thread converts one pixel pair, kGrayRows
+// rows of it; byte reads and byte stores, any alignment
+template <int FMT>
+__global__ __launch_bounds__(256) void k_yuv422_to_bgr(const uint8_t *__restrict__ src, int w, int h, int sstride, YuvPlanes p,
+                                                       uint8_t *__restrict__ dst, int dstride)
+{
+    const int cx = blockIdx.x * 256 + threadIdx.x;
+    if (2 * cx >= w) return;
+    for (int ry = 0; ry < kGrayRows; ry++) {
+        const int y = blockIdx.y * kGrayRows + ry;
+        if (y >= h) break;
+        uint8_t *d = dst + (size_t)y * dstride + (size_t)cx * 6;
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            ChromaTerm c;
+            int B, G, R;
+            const int Y = yuv422_at<FMT>(src, p, sstride, y, 2 * cx + i, c);
+            yuv_bgr(Y, c, B, G, R);
+            d[3 * i] = (uint8_t)B; d[3 * i + 1] = (uint8_t)G; d[3 * i + 2] = (uint8_t)R;
+        }
+    }
+}
+void launch_yuv422_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int sstride, const YuvPlanes &p, uint8_t *dst, int dstride)
+{
+    dim3 grid((w / 2 + 255) / 256, (h + kGrayRows - 1) / kGrayRows, 1);
+    if (p.fmt == NVCA_PIX_UYVY)      NVCA_LAUNCH(k_yuv422_to_bgr<NVCA_PIX_UYVY>, grid, dim3(256), 0, st, src, w, h, sstride, p, dst, dstride);
+    else if (p.fmt == NVCA_PIX_YVYU) NVCA_LAUNCH(k_yuv422_to_bgr<NVCA_PIX_YVYU>, grid, dim3(256), 0, st, src, w, h, sstride, p, dst, dstride);
+    else                             NVCA_LAUNCH(k_yuv422_to_bgr<NVCA_PIX_YUY2>, grid, dim3(256), 0, st, src, w, h, sstride, p, dst, dstride);
 }
 
 // ---- 8UC1 resize (gray-then-resize order of the part detectors, pyramid levels): resize_sample on one channel, the value as a
@@ -362,7 +493,10 @@ void launch_resize1(hipStream_t st, const uint8_t *src, int sw, int sh, int sstr
 // resize, EYE/kmseyedetect.cpp:948-956, NOSE/kmsnosedetect.cpp:836-841 -- without writing the full-size gray image; kWorkNv12 /
 // kWorkI420: the same with cv::cvtColor(CV_YUV2BGR_NV12 / _I420) in front, tap (r, c) = yuv_gray(Y[r][c], chroma(c >> 1, r >> 1))) or
 // resize(lut[gray z]) (kWorkGray: the eye detector equalizes the full-size gray image first, EYE :950), plus its histogram.
-enum { kWorkGray = 0, kWorkBgr = 1, kWorkNv12 = 2, kWorkI420 = 3 };
+// kWorkYuy2 / kWorkUyvy / kWorkYvyu: the same with cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) in front, tap (r, c) = yuv_gray of the
+// pixel's luma and its pair's chroma in row r (yuv422_at).
+enum { kWorkGray = 0, kWorkBgr = 1, kWorkNv12 = 2, kWorkI420 = 3, kWorkYuy2 = 4, kWorkUyvy = 5, kWorkYvyu = 6 };
+static_assert(kWorkYuy2 == NVCA_PIX_YUY2 && kWorkUyvy == NVCA_PIX_UYVY && kWorkYvyu == NVCA_PIX_YVYU, "a 4:2:2 source's number is its format");
 template <int SRC>
 __global__ __launch_bounds__(256) void k_work_resize(
     const uint8_t *const *__restrict__ srcs, const int *__restrict__ lut_idx, const uint8_t *__restrict__ luts, YuvPlanes yp,
@@ -386,6 +520,8 @@ __global__ __launch_bounds__(256) void k_work_resize(
             if (SRC == kWorkBgr) v = resize1_sample([&](int r, int c) { const uint8_t *p = src + (size_t)r * sstride + (size_t)c * 3; return gray_of(p[0], p[1], p[2]); }, sh, t, x, y);
             else if (SRC == kWorkNv12 || SRC == kWorkI420)
                 v = resize1_sample([&](int r, int c) { return yuv_gray(src[yp.off_y + (size_t)r * sstride + c], chroma_at<SRC == kWorkNv12 ? 1 : 2>(src, yp, c >> 1, r >> 1)); }, sh, t, x, y);
+            else if (SRC >= kWorkYuy2)
+                v = resize1_sample([&](int r, int c) { ChromaTerm ct; const int Y = yuv422_at<SRC>(src, yp, sstride, r, c, ct); return yuv_gray(Y, ct); }, sh, t, x, y);
             else if (use_lut) v = resize1_sample([&](int r, int c) { return (int)sl[src[(size_t)r * sstride + c]]; }, sh, t, x, y);
             else v = resize1_value(src, sh, sstride, t, x, y);
             dst[(size_t)y * dstride + x] = (uint8_t)v;
@@ -403,6 +539,9 @@ void launch_work_resize(hipStream_t st, bool bgr, const uint8_t *const *d_srcs, 
 #define NVCA_WORK_RESIZE(SRC) NVCA_LAUNCH(k_work_resize<SRC>, grid, dim3(256), 0, st, d_srcs, d_lut_idx, d_luts, yp, sh, sstride, t, dst, dw, dh, dstride, dst_slot, hist)
     if (yp.fmt == 1) NVCA_WORK_RESIZE(kWorkNv12);
     else if (yp.fmt == 2) NVCA_WORK_RESIZE(kWorkI420);
+    else if (yp.fmt == NVCA_PIX_YUY2) NVCA_WORK_RESIZE(kWorkYuy2);
+    else if (yp.fmt == NVCA_PIX_UYVY) NVCA_WORK_RESIZE(kWorkUyvy);
+    else if (yp.fmt == NVCA_PIX_YVYU) NVCA_WORK_RESIZE(kWorkYvyu);
     else if (bgr) NVCA_WORK_RESIZE(kWorkBgr);
     else NVCA_WORK_RESIZE(kWorkGray);
 #undef NVCA_WORK_RESIZE

@@ -200,13 +200,57 @@ __global__ __launch_bounds__(256) void k_trk_pixel_yuv8(const TrkSlot *__restric
     }
 }
 
+// ---- the pixel pass on packed 4:2:2 frames (FMT: NVCA_PIX_YUY2 / _UYVY / _YVYU): cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) in front
+// of TRK/gstnubotracker.cpp:356 -- gray = gray_of(yuv_bgr(Y, the chroma of the pixel's pair IN ITS ROW)).  Both kernels
+// have k_trk_pixel's shape and grid: up to 4 pixels (two pairs) of one row per thread, a row per blockIdx.y -- any height, odd ones too.
+// General path: byte reads, any alignment, any stride, any even width.
+template <int FMT>
+__global__ __launch_bounds__(256) void k_trk_pixel_yuv422(const TrkSlot *__restrict__ slots, int w, int h, uint8_t *__restrict__ flags, int *__restrict__ out, int *__restrict__ roots, int *__restrict__ tiles, int tick)
+{
+    pixel_pass_clears(out, roots, tiles, w, h, tick);
+    const TrkSlot s = slots[blockIdx.z];
+    const int x4 = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y;
+    bool any = false;
+    const size_t o = (size_t)y * w + x4;
+    const int n = x4 >= w ? 0 : (w - x4 < 4 ? w - x4 : 4);
+    for (int k = 0; k < n; k++) {                          // (the width is even: whole pairs)
+        ChromaTerm c;
+        const int Y = yuv422_at<FMT>(s.src, s.yuv, s.sstride, y, x4 + k, c);
+        if (trk_update1(s, o + k, yuv_gray(Y, c))) any = true;
+    }
+    segment_flag(flags, w, h, any, tiles, tick);
+}
+// Wide path, beside k_trk_pixel4: w % 4 == 0, rows 8-byte aligned (trk_wide_ok): one 8-byte load = two pairs = 4 pixels, prev and
+// the motion history through trk_update4
+template <int FMT>
+__global__ __launch_bounds__(256) void k_trk_pixel_yuv422x4(const TrkSlot *__restrict__ slots, int w, int h, uint8_t *__restrict__ flags, int *__restrict__ out, int *__restrict__ roots, int *__restrict__ tiles, int tick)
+{
+    pixel_pass_clears(out, roots, tiles, w, h, tick);
+    const TrkSlot s = slots[blockIdx.z];
+    const int x4 = (blockIdx.x * 256 + threadIdx.x) * 4, y = blockIdx.y;
+    bool any = false;
+    if (x4 < w) {
+        const uint2 px = *(const uint2 *)(s.src + s.yuv.off_y + (size_t)y * s.sstride + (size_t)x4 * 2);
+        const ChromaTerm c0 = chroma_of_pair<FMT>(px.x), c1 = chroma_of_pair<FMT>(px.y);
+        any = trk_update4(s, (size_t)y * w + x4, yuv_gray(luma_of_pair<FMT>(px.x, 0), c0), yuv_gray(luma_of_pair<FMT>(px.x, 1), c0),
+                          yuv_gray(luma_of_pair<FMT>(px.y, 0), c1), yuv_gray(luma_of_pair<FMT>(px.y, 1), c1));
+    }
+    segment_flag(flags, w, h, any, tiles, tick);
+}
 
-// 4 pixels per thread in the packed and the general 4:2:0 kernels (w4 = ceil(w / 4)); rows packed (prev / mhi pitch == w)
+// 4 pixels per thread in the packed, the general 4:2:0 and the 4:2:2 kernels (w4 = ceil(w / 4)); rows packed (prev / mhi pitch == w)
 void launch_trk_pixel(hipStream_t st, const TrkLaunch &L)
 {
     const int w = L.w, h = L.h;
     dim3 gp(((w + 3) / 4 + 255) / 256, h, L.batch);
     dim3 gw((seg_per_row(w) + 3) / 4, (h + 3) / 4, L.batch);        // k_trk_pixel_yuv8: a wave per segment and four rows
+#define NVCA_TRK_422(FMT) do { if (L.wide) NVCA_LAUNCH(k_trk_pixel_yuv422x4<FMT>, gp, dim3(256), 0, st, L.slots, w, h, L.flags, L.out, L.roots, L.tiles, L.tick); \
+                               else NVCA_LAUNCH(k_trk_pixel_yuv422<FMT>, gp, dim3(256), 0, st, L.slots, w, h, L.flags, L.out, L.roots, L.tiles, L.tick); } while (0)
+    if (L.fmt == NVCA_PIX_YUY2) NVCA_TRK_422(NVCA_PIX_YUY2);
+    else if (L.fmt == NVCA_PIX_UYVY) NVCA_TRK_422(NVCA_PIX_UYVY);
+    else if (L.fmt == NVCA_PIX_YVYU) NVCA_TRK_422(NVCA_PIX_YVYU);
+    else
+#undef NVCA_TRK_422
     if (L.fmt == 1 && L.wide) NVCA_LAUNCH(k_trk_pixel_yuv8<1>, gw, dim3(256), 0, st, L.slots, w, h, L.flags, L.out, L.roots, L.tiles, L.tick);
     else if (L.fmt == 2 && L.wide) NVCA_LAUNCH(k_trk_pixel_yuv8<2>, gw, dim3(256), 0, st, L.slots, w, h, L.flags, L.out, L.roots, L.tiles, L.tick);
     else if (L.fmt == 1) NVCA_LAUNCH(k_trk_pixel_yuv<1>, gp, dim3(256), 0, st, L.slots, w, h, L.flags, L.out, L.roots, L.tiles, L.tick);

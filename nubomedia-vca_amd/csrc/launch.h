@@ -32,10 +32,13 @@ hipError_t take_launch_error(const char **kernel);     // returns and clears the
 void launch_gray(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const ResizeView &t,
                  uint8_t *gray, unsigned *hist, int batch, bool aligned4);
 // the same for a 4:2:0 frame (planes `p`); aligned16: every plane and stride of every frame takes 16-byte (I420 chroma: 8-byte) loads.
-// Returns whether k_gray_yuv16 took the launch (identity geometry and aligned16) and not k_gray_yuv_generic.
+// Returns whether k_gray_yuv16 took the launch (identity geometry and aligned16) and not k_gray_yuv_generic.  A packed 4:2:2 frame
+// (p.fmt NVCA_PIX_YUY2 / _UYVY / _YVYU; aligned16: base, offset and stride take 16-byte loads): k_gray_yuv422_16 / k_gray_yuv422_generic.
 bool launch_gray_yuv(hipStream_t st, const uint8_t *const *d_src, const PreGeom &g, const YuvPlanes &p, const ResizeView &t,
                      uint8_t *gray, unsigned *hist, int batch, bool aligned16);
+const char *gray_yuv_kernel_name(int fmt, bool wide);       // the kernel launch_gray_yuv ran (the plan_debug lines name it)
 void launch_yuv420_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int ystride, const YuvPlanes &p, uint8_t *dst, int dstride);
+void launch_yuv422_to_bgr(hipStream_t st, const uint8_t *src, int w, int h, int sstride, const YuvPlanes &p, uint8_t *dst, int dstride);
 void launch_pyr_resize(hipStream_t st, const uint8_t *src, int sw, int sh, int sstride, size_t src_slot, const PyrLevelDev *levels,
                        int nlev, int nimg, int maxw, int maxh, uint8_t *aux, size_t aux_slot,
                        const uint8_t *luts = nullptr /* [nimg][256]: the pyramid of lut[img][image]; null: of the image */);
@@ -73,8 +76,8 @@ void launch_small_integral(hipStream_t st, const uint8_t *gray, const uint8_t *l
 // and the live-segment counts), tiles (the live-tile list), roots (the folded path's tile roots), out (the component list).
 struct TrkLaunch {
     const TrkSlot *slots; int batch, w, h;
-    int fmt;                      // 0 BGRA frames, 1 / 2: NV12 / I420 frames, planes per slot
-    bool wide;                    // every slot takes the wide pixel kernel's loads (k_trk_pixel4 / k_trk_pixel_yuv8; trk_host.h, trk_wide_ok)
+    int fmt;                      // 0 BGRA frames, 1 / 2: NV12 / I420 frames, planes per slot; 4 .. 6: packed 4:2:2 (NVCA_PIX_YUY2 / _UYVY / _YVYU)
+    bool wide;                    // every slot takes the wide pixel kernel's loads (k_trk_pixel4 / k_trk_pixel_yuv8 / k_trk_pixel_yuv422x4; trk_host.h, trk_wide_ok)
     int *labels; CompAcc *acc;    // [batch][h][w] parent words / per-root records
     int *out; int cap;            // component list and the components it holds
     uint8_t *flags; int *roots; int roots_cap; int *tiles; int tick;

@@ -27,7 +27,7 @@ namespace {
 // computed on the fly (cvtColor then resize); gray sources go through LUT lut_idx[k] of `luts` first when lut_idx is given
 struct PartImageBatch {
     bool bgr = true, post_eq = true;
-    YuvPlanes yuv{};                             // fmt 1 / 2: the sources are 4:2:0 frames of these planes (cvtColor(YUV2BGR), cvtColor, resize)
+    YuvPlanes yuv{};                             // fmt 1 / 2: the sources are 4:2:0 frames of these planes (cvtColor(YUV2BGR), cvtColor, resize); 4 .. 6: packed 4:2:2
     int sw = 0, sh = 0, sstride = 0, dw = 0, dh = 0;
     std::vector<const void *> src; std::vector<int> lut_idx;
     uint8_t *dst = nullptr; size_t slot = 0;
@@ -58,13 +58,13 @@ int part_gray_eq(nvca_ctx *ctx, const void *const *bgr, int n, int w, int h, int
     g.gpitch = w; g.gray_slot = slot;
     unsigned *hist = ctx->pw().hist.as<unsigned>();
     if (yuv) {
-        // k_gray_yuv16 stores 16 bytes at gray + row * gpitch + x: the image's pitch is its width here, so the width, the slot and the
+        // k_gray_yuv16 / k_gray_yuv422_16 store 16 bytes at gray + row * gpitch + x: the image's pitch is its width here, so the width, the slot and the
         // base must take the stores as the planes take the loads
         bool wide = yuv_layout_aligned16(*yuv) && w % 16 == 0 && slot % 16 == 0 && ((uintptr_t)gray & 15) == 0;
         for (int k = 0; k < n; k++) wide = wide && ((uintptr_t)bgr[k] & 15) == 0;
         TimedLaunch t(ctx, NVCA_K_GRAY);
         wide = launch_gray_yuv(ctx->cs(), (const uint8_t *const *)d_ptrs, g, yuv_planes(yuv), ResizeView{}, gray, hist, n, wide);
-        if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 eye gray of %d frame(s) %d x %d: %s\n", n, w, h, wide ? "k_gray_yuv16" : "k_gray_yuv_generic");
+        if (ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] %s eye gray of %d frame(s) %d x %d: %s\n", yuv_is_422(yuv->format) ? "4:2:2" : "4:2:0", n, w, h, gray_yuv_kernel_name(yuv->format, wide));
     } else {
       bool aligned = stride % 4 == 0 && w % 4 == 0 && slot % 4 == 0 && ((uintptr_t)gray & 3) == 0;
       for (int k = 0; k < n; k++) aligned = aligned && ((uintptr_t)bgr[k] & 3) == 0;

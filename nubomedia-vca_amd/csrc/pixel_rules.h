@@ -115,6 +115,15 @@ NVCA_HD_INLINE void yuv_bgr(int Y, const ChromaTerm &c, int &B, int &G, int &R)
     const int y = (Y > 16 ? Y - 16 : 0) * 1220542;
     B = sat8((y + c.b) >> 20); G = sat8((y + c.g) >> 20); R = sat8((y + c.r) >> 20);
 }
+// A.18: cv::cvtColor(CV_YUV2BGR_YUY2 / _UYVY / _YVYU) on packed 4:2:2 -- in row y, pixels 2k and 2k + 1 take U and V from the four bytes
+// 4k .. 4k + 3 of that row; nothing is shared between rows; the arithmetic is A.13's (chroma_term, yuv_bgr).  THE statement of the three
+// byte orders: where Y0, U and V lie within a pair's four bytes (Y1 two bytes behind Y0).  Kernels (through the format as a template
+// value), host code and the tests' driver read the positions here and nowhere else.
+struct Yuv422Pos { int y0, u, v; };
+NVCA_HD_INLINE constexpr Yuv422Pos yuv422_pos(int format)
+{
+    return format == NVCA_PIX_UYVY ? Yuv422Pos{1, 0, 2} : format == NVCA_PIX_YVYU ? Yuv422Pos{0, 3, 1} : Yuv422Pos{0, 1, 3};      // else: NVCA_PIX_YUY2
+}
 // A.14: cv::cvtColor(CV_BGR2YUV_I420), OpenCV 2.4 color.cpp (RGB888toYUV420pInvoker), BT.601 limited range, shift 20, all int32.  Y of
 // every pixel; the chroma sample of a 2 x 2 block is (U, V) of the block's top-left pixel alone, nothing is averaged.  Over all 2^24
 // colours Y stays in 16 .. 235 and U, V in 16 .. 240: nothing saturates.

@@ -249,7 +249,8 @@ try {
         L.order = ctx->sw.trk_order; L.rows = tune.rows; L.rows_uf = tune.rows_uf;
         // launch (the result header and the root list's header are cleared by the pixel kernel)
         if (!fold) if (int rc = clear_segment_counts(ctx, ws, W, H, batch)) return rc;
-        if (fmt != NVCA_PIX_BGR && ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 tracker pass of %d frame(s) %d x %d: %s\n", batch, W, H, wide ? "k_trk_pixel_yuv8" : "k_trk_pixel_yuv");
+        if (yuv_is_422(fmt) && ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:2 tracker pass of %d frame(s) %d x %d: %s\n", batch, W, H, wide ? "k_trk_pixel_yuv422x4" : "k_trk_pixel_yuv422");
+        else if (fmt != NVCA_PIX_BGR && ctx->sw.plan_debug) fprintf(stderr, "[nvca plan] 4:2:0 tracker pass of %d frame(s) %d x %d: %s\n", batch, W, H, wide ? "k_trk_pixel_yuv8" : "k_trk_pixel_yuv");
         if (int rc = launch_route(ctx, L, !any_ccl ? kTrkPixelOnly : fold ? kTrkFolded : kTrkPerPixel)) return rc;
         tp1 = std::chrono::steady_clock::now();
         // read back; fallback

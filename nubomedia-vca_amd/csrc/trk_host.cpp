@@ -26,6 +26,7 @@ bool trk_wide_ok(int fmt, const nvca_pixel_layout *layout, int mem, uintptr_t ba
     if (width % 4) return false;
     if (mem != NVCA_MEM_DEVICE) base = 0;
     if (fmt == NVCA_PIX_BGR) return !(stride & 15) && !(base & 15);
+    if (yuv_is_422(fmt)) return !((base + layout->offset[0]) & 7) && !(layout->stride[0] & 7);       // k_trk_pixel_yuv422x4: 8-byte loads of the one plane
     const size_t cmask = fmt == NVCA_PIX_NV12 ? 7 : 3;
     if (((base + layout->offset[0]) & 7) || (layout->stride[0] & 7) || ((base + layout->offset[1]) & cmask) || ((size_t)layout->stride[1] & cmask)) return false;
     return !(fmt == NVCA_PIX_I420 && (((base + layout->offset[2]) & 3) || (layout->stride[2] & 3)));

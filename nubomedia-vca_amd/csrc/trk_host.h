@@ -23,11 +23,12 @@ void trk_launch_sets(const TrkFrameKey *keys, int n, TrkLaunchSets &sets);
 // ---- the wide pixel kernels' loads, for ONE member of a launch set (one member that fails sends its whole set to the general kernel).
 // Every format: width % 4 == 0.  BGRA (k_trk_pixel4: 16-byte loads of four pixels): `stride` and a device frame's base on 16 bytes.
 // 4:2:0 (k_trk_pixel_yuv8; the strides are the layout's, `stride` is not read): luma rows and NV12 chroma rows on 8 bytes (8-byte loads),
-// I420 chroma rows on 4 (4 bytes of each plane).  A host frame is staged and counts as base 0: the staging buffer is 256-byte aligned
+// I420 chroma rows on 4 (4 bytes of each plane).  Packed 4:2:2 (k_trk_pixel_yuv422x4: 8-byte loads of two pixel pairs): the plane's rows
+// on 8 bytes -- base + offset[0] and stride[0].  A host frame is staged and counts as base 0: the staging buffer is 256-byte aligned
 // and every staged frame starts on a multiple of 256 bytes in it (trk_staged_bytes).
 bool trk_wide_ok(int fmt, const nvca_pixel_layout *layout, int mem, uintptr_t base, int stride, int width);
 
-// ---- bytes a host frame takes in the staging buffer (what is copied: a 4:2:0 frame's extent, a packed frame's rows), a multiple of 256
+// ---- bytes a host frame takes in the staging buffer (what is copied: a 4:2:0 / 4:2:2 frame's extent, a packed frame's rows), a multiple of 256
 size_t trk_staged_bytes(const nvca_pixel_layout *yuv, int stride, int w, int h);
 
 // ---- the component list as the device left it (trk_layout.h).  trk_component_count: the header's count against the list -- NVCA_OK, or

@@ -19,6 +19,7 @@ HAAR_DO_CANNY_PRUNING, HAAR_SCALE_IMAGE, HAAR_FIND_BIGGEST_OBJECT, HAAR_DO_ROUGH
 SUM_F32PAIR, SUM_F64 = 0, 1
 K_COUNT = 14
 PIX_BGR, PIX_NV12, PIX_I420 = 0, 1, 2
+PIX_YUY2, PIX_UYVY, PIX_YVYU = 4, 5, 6          # packed 4:2:2: bytes Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U (3 is no format)
 CASCADE_HAAR, CASCADE_LBP, CASCADE_HAAR_NEW = 0, 1, 2
 
 
@@ -101,7 +102,7 @@ SYMBOLS = [
     "nvca_part_batch_submit", "nvca_part_batch_collect", "nvca_face_stream_set_input", "nvca_yuv420_to_bgr",
     "nvca_part_stream_set_input", "nvca_tracker_set_input", "nvca_bgr_to_yuv420", "nvca_draw_shapes_yuv420",
     "nvca_overlay_blend_yuv420", "nvca_cascade_format", "nvca_cascade_dump_lbp", "nvca_cascade_dump_haar_new",
-    "nvca_cascade_set_small_route", "nvca_cascade_get_small_route",
+    "nvca_cascade_set_small_route", "nvca_cascade_get_small_route", "nvca_yuv422_to_bgr",
 ]
 
 _lib = None
@@ -202,6 +203,8 @@ def load():
     L.nvca_face_stream_motion_event.argtypes = [vp]
     L.nvca_face_stream_set_input.argtypes = [vp, C.POINTER(PixelLayout)]
     L.nvca_yuv420_to_bgr.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(PixelLayout), C.c_int, vp, C.c_int]
+    if hasattr(L, "nvca_yuv422_to_bgr"):      # (NVCA_LIB may name an older library: A/B runs against a parent commit)
+        L.nvca_yuv422_to_bgr.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(PixelLayout), C.c_int, vp, C.c_int]
     L.nvca_bgr_to_yuv420.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(PixelLayout)]
     L.nvca_draw_shapes_yuv420.argtypes = [vp, C.POINTER(Frame), C.POINTER(PixelLayout), C.POINTER(Shape), C.c_int]
     L.nvca_overlay_blend_yuv420.argtypes = [vp, C.POINTER(Frame), C.POINTER(PixelLayout), C.POINTER(Rect), C.c_int, C.POINTER(Overlay)]
@@ -375,6 +378,15 @@ class Context:
             self.check(self.L.nvca_yuv420_to_bgr(self.h, buf.ctypes.data, w, h, C.byref(layout), MEM_HOST, out.ctypes.data, w * 3))
             return out
         self.check(self.L.nvca_yuv420_to_bgr(self.h, int(buf), w, h, C.byref(layout), MEM_DEVICE, int(dst), dst_stride))
+
+    def yuv422_to_bgr(self, buf, w, h, layout, mem=MEM_HOST, dst=None, dst_stride=None):
+        """nvca_yuv422_to_bgr (packed YUY2 / UYVY / YVYU), as yuv420_to_bgr: host buffers return the BGR image, device pointers write dst"""
+        if mem == MEM_HOST:
+            buf = np.ascontiguousarray(buf, np.uint8)
+            out = np.empty((h, w, 3), np.uint8)
+            self.check(self.L.nvca_yuv422_to_bgr(self.h, buf.ctypes.data, w, h, C.byref(layout), MEM_HOST, out.ctypes.data, w * 3))
+            return out
+        self.check(self.L.nvca_yuv422_to_bgr(self.h, int(buf), w, h, C.byref(layout), MEM_DEVICE, int(dst), dst_stride))
 
     def bgr_to_yuv420(self, src, w, h, layout, base, mem=MEM_HOST, stride=None, channels=3):
         """nvca_bgr_to_yuv420 into the planes of `layout`.  Host: src is a numpy image [h, w, 3 or 4], base a writable flat uint8 numpy

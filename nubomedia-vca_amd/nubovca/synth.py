@@ -517,6 +517,45 @@ def make_yuv420(W, H, seed, fmt, kind="natural", faces=(), pad=0, luma_rows=None
     return buf, (fmt, offsets, strides)
 
 
+# packed 4:2:2: format (the values of NVCA_PIX_YUY2 / _UYVY / _YVYU) -> positions of (Y0, U, V) within a pixel pair's four bytes; Y1 lies
+# two bytes behind Y0
+YUV422_POS = {4: (0, 1, 3), 5: (1, 0, 2), 6: (0, 3, 1)}
+
+
+def pack_yuv422(y, u, v, fmt, pad=0, base=0, seed=0):
+    """The planes y [H, W], u and v [H, W / 2] (a chroma sample per row and pixel pair) as a packed 4:2:2 buffer: (flat uint8 buffer,
+    (format, offsets, strides)) with rows of 2 W + pad bytes from byte `base` on.  The buffer ends with the last row's last pixel; every
+    byte that is no pixel (the bytes in front of the base, the row padding) holds seeded noise."""
+    y, u, v = (np.asarray(a, np.uint8) for a in (y, u, v))
+    H, W = y.shape
+    assert W % 2 == 0 and u.shape == v.shape == (H, W // 2) and fmt in YUV422_POS
+    py, pu, pv = YUV422_POS[fmt]
+    stride = 2 * W + pad
+    buf = np.random.default_rng(seed ^ 0xC422).integers(0, 256, size=base + stride * (H - 1) + 2 * W).astype(np.uint8)
+    rows = np.zeros((H, W // 2, 4), np.uint8)
+    rows[..., py], rows[..., py + 2], rows[..., pu], rows[..., pv] = y[:, 0::2], y[:, 1::2], u, v
+    idx = base + np.arange(H)[:, None] * stride + np.arange(2 * W)[None, :]
+    buf[idx] = rows.reshape(H, 2 * W)
+    return buf, (fmt, [base, 0, 0], [stride, 0, 0])
+
+
+def make_yuv422(W, H, seed, fmt, kind="natural", faces=(), pad=0, base=0):
+    """A packed 4:2:2 frame as a camera lays it out (pack_yuv422's arrangement: byte order `fmt`, row padding, base offset, seeded noise
+    in every byte that is no pixel).  Y = 16 + gray * 219 / 255 of make_gray's field, as make_yuv420; chroma around 128 with seeded noise
+    that differs from ROW to row, one pair in eight at an extreme (16 or 240: a channel of the converted pixel saturates, and its gray value
+    moves with the chroma): a reader that shares chroma between rows 2k and 2k + 1 converts another image."""
+    assert W % 2 == 0
+    g = make_gray(W, H, seed, kind, faces).astype(np.int32)
+    rng = np.random.default_rng(seed ^ 0xC420)
+    y = (16 + (g * 219 + 127) // 255).astype(np.uint8)
+    u = (128 + rng.integers(-40, 41, size=(H, W // 2))).astype(np.uint8)
+    v = (128 + rng.integers(-40, 41, size=(H, W // 2))).astype(np.uint8)
+    salt = rng.integers(0, 8, size=(H, W // 2)) == 0
+    u[salt] = rng.choice(np.array([16, 240], np.uint8), size=int(salt.sum()))
+    v[salt] = rng.choice(np.array([16, 240], np.uint8), size=int(salt.sum()))
+    return pack_yuv422(y, u, v, fmt, pad=pad, base=base, seed=seed)
+
+
 def frame_seed(stream_id, frame_idx):
     """seed = 0xC0FFEE + stream_id*1000 + frame_idx."""
     return 0xC0FFEE + stream_id * 1000 + frame_idx
