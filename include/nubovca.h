@@ -235,6 +235,36 @@ int  nvca_cascade_dump_haar_new(const nvca_cascade *c, int *rects, float *weight
  * NVCA_OK and changes nothing -- their small routes are always available -- and the getter reports 1.  NVCA_ERR_ARG for NULL. */
 int  nvca_cascade_set_small_route(nvca_cascade *c, int on);
 int  nvca_cascade_get_small_route(const nvca_cascade *c, int *on);
+/* Loading with flags.  flags == 0 is nvca_cascade_load_xml / _load_mem / _validate_mem itself; a bit that is not defined here is
+ * NVCA_ERR_ARG.
+ * NVCA_LOAD_HAAR_GENERAL: a new-format HAAR file may hold tree weak classifiers (internalNodes "left right featureIdx threshold" per
+ * node, one leaf value more than nodes; at most 15 nodes a weak classifier, NVCA_ERR_UNSUPPORTED beyond) and tilted features
+ * (<tilted>1</tilted>: every rect of the feature reads the tilted integral, with the file's weight).  The header's maxDepth is not
+ * consulted.  NVCA_ERR_PARSE for a tree the evaluator could not walk safely: a node word count that is no multiple of 4, a leaf count
+ * other than nodes + 1, a child node that does not lie behind its parent or lies outside the tree, a leaf index outside the leaf
+ * values, a threshold or leaf that is not finite, a feature index outside the list, a tilted rect with x - h < 0, x + w > width or
+ * y + w + h > height.  The format stays NVCA_CASCADE_HAAR_NEW and every entry point that takes such a cascade takes this one
+ * (detectMultiScale, batches, levels, face and part streams made with _create_any).  A flagged file of stumps "0 -1" on upright
+ * features is the cascade the plain load makes: the same kernels, eligible for the small route.  A cascade that does hold a tree or
+ * a tilted feature ("general": nvca_cascade_kind reports which) is evaluated by its own kernels on the large-image route only:
+ * nvca_cascade_set_small_route returns NVCA_OK and changes nothing, the getter reports 0, nvca_cascade_dump_haar_new answers
+ * NVCA_ERR_ARG (nvca_cascade_dump_haar_tree expresses it).  On old-format and LBP files the flag changes nothing: LBP trees stay
+ * refused. */
+#define NVCA_LOAD_HAAR_GENERAL 1
+int  nvca_cascade_load_xml_ex(nvca_ctx *ctx, const char *path, unsigned flags, nvca_cascade **out);
+int  nvca_cascade_load_mem_ex(nvca_ctx *ctx, const char *xml, int64_t len, unsigned flags, nvca_cascade **out);
+int  nvca_cascade_validate_mem_ex(const char *xml, int64_t len, unsigned flags, int *win_w, int *win_h, int *n_stages, int *n_weak,
+                                  char *err, int err_cap);
+/* the sizes of nvca_cascade_dump_haar_tree's arrays and whether the cascade is general (any pointer may be NULL); NVCA_ERR_ARG for a
+ * cascade that is not NVCA_CASCADE_HAAR_NEW */
+int  nvca_cascade_tree_info(const nvca_cascade *c, int *n_nodes, int *n_leaves, int *general);
+/* flat dump of a new-format HAAR cascade, general or not, in terms that express trees (any pointer may be NULL):
+ * rects[n_features*12], weights[n_features*3], rect_counts[n_features] as nvca_cascade_dump_haar_new's, tilted[n_features];
+ * node_counts[n_weak]; per node, in file order, nodes[n_nodes*3] = left, right, featureIdx as the file has them (a child > 0: a node
+ * of the same weak classifier, <= 0: its leaf -child) and node_thr[n_nodes]; leaves[n_leaves] (a weak classifier's node count + 1,
+ * in file order); stage_sizes / stage_thr[n_stages], thresholds as evaluated. */
+int  nvca_cascade_dump_haar_tree(const nvca_cascade *c, int *rects, float *weights, int *rect_counts, int *tilted, int *node_counts,
+                                 int *nodes, float *node_thr, float *leaves, int *stage_sizes, float *stage_thr);
 
 /* ---- imgproc primitives (each = one cv:: call of the reference) -------- */
 /* cv::cvtColor(CV_BGR2GRAY) FACE/kmsfacedetect.cpp:806, TRK/gstnubotracker.cpp:356 (channels 4) */

@@ -226,13 +226,20 @@ const char *nvca_kernel_name(int k)
 // =========================================================================
 int nvca_cascade_load_mem(nvca_ctx *ctx, const char *xml, int64_t len, nvca_cascade **out)
 try {
+    return nvca_cascade_load_mem_ex(ctx, xml, len, 0u, out);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_cascade_load_mem_ex(nvca_ctx *ctx, const char *xml, int64_t len, unsigned flags, nvca_cascade **out)
+try {
     NVCA_LOCK_OR_FAIL(ctx);
     if (!ctx || !xml || len <= 0 || !out) return NVCA_ERR_ARG;
     *out = nullptr;
+    if (flags & ~(unsigned)NVCA_LOAD_HAAR_GENERAL) { ctx->set_error("cascade load: unknown flag bits"); return NVCA_ERR_ARG; }
     std::unique_ptr<nvca_cascade> c(new nvca_cascade());
     std::string err;
     CascadeFile f;
-    int rc = parse_cascade_file(xml, (size_t)len, f, err);
+    int rc = parse_cascade_file(xml, (size_t)len, flags, f, err);
     if (rc) { ctx->set_error("cascade XML: " + err); return rc; }
     c->c = std::move(f.haar); c->lbp = std::move(f.lbp); c->hnew = std::move(f.hnew); c->format = f.format;
     c->ctx = ctx;
@@ -246,17 +253,23 @@ NVCA_API_CATCH(ctx)
 // CPU test-suite and the sanitizer build run the parser through the ABI this way)
 int nvca_cascade_validate_mem(const char *xml, int64_t len, int *win_w, int *win_h, int *n_stages, int *n_weak, char *err, int err_cap)
 try {
+    return nvca_cascade_validate_mem_ex(xml, len, 0u, win_w, win_h, n_stages, n_weak, err, err_cap);
+}
+NVCA_API_CATCH(nullptr)
+
+int nvca_cascade_validate_mem_ex(const char *xml, int64_t len, unsigned flags, int *win_w, int *win_h, int *n_stages, int *n_weak, char *err, int err_cap)
+try {
     if (err && err_cap > 0) err[0] = 0;
-    if (!xml || len <= 0) return NVCA_ERR_ARG;
+    if (!xml || len <= 0 || (flags & ~(unsigned)NVCA_LOAD_HAAR_GENERAL)) return NVCA_ERR_ARG;
     CascadeFile f;
     std::string msg;
-    const int rc = parse_cascade_file(xml, (size_t)len, f, msg);
+    const int rc = parse_cascade_file(xml, (size_t)len, flags, f, msg);
     if (rc) { if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", msg.c_str()); return rc; }
     const bool lbp = f.format == NVCA_CASCADE_LBP, hnew = f.format == NVCA_CASCADE_HAAR_NEW;
     if (win_w) *win_w = f.haar.ow;
     if (win_h) *win_h = f.haar.oh;
     if (n_stages) *n_stages = lbp ? (int)f.lbp.stages.size() : hnew ? (int)f.hnew.stages.size() : (int)f.haar.stages.size();
-    if (n_weak) *n_weak = lbp ? (int)f.lbp.weak.size() : hnew ? (int)f.hnew.weak.size() : (int)f.haar.cls.size();
+    if (n_weak) *n_weak = lbp ? (int)f.lbp.weak.size() : hnew ? (int)f.hnew.nweak() : (int)f.haar.cls.size();
     return NVCA_OK;
 }
 NVCA_API_CATCH(nullptr)
@@ -278,13 +291,19 @@ NVCA_API_CATCH(nullptr)
 
 int nvca_cascade_load_xml(nvca_ctx *ctx, const char *path, nvca_cascade **out)
 try {
+    return nvca_cascade_load_xml_ex(ctx, path, 0u, out);
+}
+NVCA_API_CATCH(ctx)
+
+int nvca_cascade_load_xml_ex(nvca_ctx *ctx, const char *path, unsigned flags, nvca_cascade **out)
+try {
     if (!ctx || !path || !out) return NVCA_ERR_ARG;
     std::ifstream f(path, std::ios::binary);
     if (!f) { ctx->set_error(std::string("cannot open cascade file ") + path); return NVCA_ERR_IO; }
     std::stringstream ss; ss << f.rdbuf();
     const std::string s = ss.str();
     if (s.empty()) { ctx->set_error(std::string("empty cascade file ") + path); return NVCA_ERR_IO; }
-    return nvca_cascade_load_mem(ctx, s.data(), (int64_t)s.size(), out);
+    return nvca_cascade_load_mem_ex(ctx, s.data(), (int64_t)s.size(), flags, out);
 }
 NVCA_API_CATCH(ctx)
 
@@ -322,7 +341,7 @@ try {
     if (win_h) *win_h = c->c.oh;
     const bool lbp = c->format == NVCA_CASCADE_LBP, hnew = c->format == NVCA_CASCADE_HAAR_NEW;
     if (n_stages) *n_stages = lbp ? (int)c->lbp.stages.size() : hnew ? (int)c->hnew.stages.size() : (int)c->c.stages.size();
-    if (n_weak) *n_weak = lbp ? (int)c->lbp.weak.size() : hnew ? (int)c->hnew.weak.size() : (int)c->c.cls.size();
+    if (n_weak) *n_weak = lbp ? (int)c->lbp.weak.size() : hnew ? (int)c->hnew.nweak() : (int)c->c.cls.size();
     return NVCA_OK;
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))
@@ -360,7 +379,7 @@ NVCA_API_CATCH((c ? c->ctx : nullptr))
 int nvca_cascade_dump_haar_new(const nvca_cascade *c, int *rects, float *weights, int *rect_counts, int *feature_idx, float *thr, float *leaves,
                                int *stage_sizes, float *stage_thr)
 try {
-    if (!c || c->format != NVCA_CASCADE_HAAR_NEW) return NVCA_ERR_ARG;
+    if (!c || c->format != NVCA_CASCADE_HAAR_NEW || c->hnew.general) return NVCA_ERR_ARG;          // (a general cascade: nvca_cascade_dump_haar_tree)
     const HnewCascade &h = c->hnew;
     for (size_t i = 0; i < h.features.size(); i++) {
         if (rects) memcpy(rects + i * 12, h.features[i].rect, sizeof(int) * 12);
@@ -380,11 +399,56 @@ try {
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))
 
+int nvca_cascade_tree_info(const nvca_cascade *c, int *n_nodes, int *n_leaves, int *general)
+try {
+    if (!c || c->format != NVCA_CASCADE_HAAR_NEW) return NVCA_ERR_ARG;
+    const HnewCascade &h = c->hnew;
+    if (n_nodes) *n_nodes = h.general ? (int)h.nodes.size() : (int)h.weak.size();
+    if (n_leaves) *n_leaves = h.general ? (int)h.leaves.size() : 2 * (int)h.weak.size();
+    if (general) *general = h.general ? 1 : 0;
+    return NVCA_OK;
+}
+NVCA_API_CATCH((c ? c->ctx : nullptr))
+
+// a new-format HAAR cascade in terms that express trees: a stump cascade's weak classifiers as the one-node trees "0 -1" they are
+int nvca_cascade_dump_haar_tree(const nvca_cascade *c, int *rects, float *weights, int *rect_counts, int *tilted, int *node_counts,
+                                int *nodes, float *node_thr, float *leaves, int *stage_sizes, float *stage_thr)
+try {
+    if (!c || c->format != NVCA_CASCADE_HAAR_NEW) return NVCA_ERR_ARG;
+    const HnewCascade &h = c->hnew;
+    for (size_t i = 0; i < h.features.size(); i++) {
+        if (rects) memcpy(rects + i * 12, h.features[i].rect, sizeof(int) * 12);
+        if (weights) memcpy(weights + i * 3, h.features[i].weight, sizeof(float) * 3);
+        if (rect_counts) rect_counts[i] = h.features[i].nrect;
+        if (tilted) tilted[i] = h.general ? (int)h.tilted[i] : 0;
+    }
+    if (h.general) {
+        for (size_t i = 0; i < h.trees.size() && node_counts; i++) node_counts[i] = h.trees[i].nnodes;
+        for (size_t i = 0; i < h.nodes.size(); i++) {
+            if (nodes) { nodes[i * 3] = h.nodes[i].left; nodes[i * 3 + 1] = h.nodes[i].right; nodes[i * 3 + 2] = h.nodes[i].feature; }
+            if (node_thr) node_thr[i] = h.nodes[i].threshold;
+        }
+        for (size_t i = 0; i < h.leaves.size() && leaves; i++) leaves[i] = h.leaves[i];
+    } else
+        for (size_t i = 0; i < h.weak.size(); i++) {
+            if (node_counts) node_counts[i] = 1;
+            if (nodes) { nodes[i * 3] = 0; nodes[i * 3 + 1] = -1; nodes[i * 3 + 2] = h.weak[i].feature; }
+            if (node_thr) node_thr[i] = h.weak[i].threshold;
+            if (leaves) { leaves[i * 2] = h.weak[i].leaf[0]; leaves[i * 2 + 1] = h.weak[i].leaf[1]; }
+        }
+    for (size_t s = 0; s < h.stages.size(); s++) {
+        if (stage_sizes) stage_sizes[s] = h.stages[s].count;
+        if (stage_thr) stage_thr[s] = h.stages[s].threshold;
+    }
+    return NVCA_OK;
+}
+NVCA_API_CATCH((c ? c->ctx : nullptr))
+
 // the small-image route of a new-format HAAR cascade (k_roi_hnew), opt-in: the flag is read when a job is built (make_detect_job)
 int nvca_cascade_set_small_route(nvca_cascade *c, int on)
 try {
     if (!c) return NVCA_ERR_ARG;
-    if (c->format == NVCA_CASCADE_HAAR_NEW) c->small_route.store(on ? 1 : 0, std::memory_order_relaxed);
+    if (c->format == NVCA_CASCADE_HAAR_NEW && !c->hnew.general) c->small_route.store(on ? 1 : 0, std::memory_order_relaxed);
     return NVCA_OK;
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))
@@ -400,8 +464,10 @@ NVCA_API_CATCH((c ? c->ctx : nullptr))
 int nvca_cascade_kind(const nvca_cascade *c, int *has_tilted, int *has_trees)
 try {
     if (!c) return NVCA_ERR_ARG;
-    if (has_tilted) *has_tilted = c->c.has_tilted ? 1 : 0;
-    if (has_trees) *has_trees = c->c.stump_based ? 0 : 1;
+    bool trees = !c->c.stump_based;          // (an old-format model that was never filled says stumps, upright)
+    if (c->format == NVCA_CASCADE_HAAR_NEW) for (const HgenTree &t : c->hnew.trees) trees = trees || t.nnodes > 1;
+    if (has_tilted) *has_tilted = c->c.has_tilted || (c->format == NVCA_CASCADE_HAAR_NEW && c->hnew.has_tilted) ? 1 : 0;
+    if (has_trees) *has_trees = trees ? 1 : 0;
     return NVCA_OK;
 }
 NVCA_API_CATCH((c ? c->ctx : nullptr))

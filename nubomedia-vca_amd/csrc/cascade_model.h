@@ -55,11 +55,24 @@ struct LbpCascade {
 // --------------------------------------------------------------------------
 struct HnewFeature { int rect[3][4]; float weight[3]; int nrect; };      // x, y, w, h, window-relative
 struct HnewWeak { int feature; float threshold; float leaf[2]; };        // vote = value < threshold ? leaf[0] : leaf[1]
+// A general cascade (loaded with NVCA_LOAD_HAAR_GENERAL from a file that holds a tree or a tilted feature): a weak
+// classifier is a tree of 1 .. kHgenMaxNodes nodes, in file order with every child node behind its parent; a child > 0 is a node of the
+// same tree, a child <= 0 its leaf -child.  `weak` is empty then; a stage's first / count index `trees`.
+static constexpr int kHgenMaxNodes = 15;      // nodes of one weak classifier (a depth-4 tree is full at 15)
+struct HgenNode { int left, right, feature; float threshold; };
+struct HgenTree { int first_node, nnodes, first_leaf; };          // nnodes + 1 leaves from first_leaf
 struct HnewCascade {
     int ow = 0, oh = 0;
     std::vector<HnewFeature> features;
     std::vector<HnewWeak> weak;
     std::vector<LbpStage> stages;          // (threshold as evaluated: (float)value - 1e-5f, as an LBP cascade's)
+    bool general = false;                  // trees / nodes / leaves / tilted hold the weak classifiers (kernels_cascade_hgen.hip evaluates them)
+    std::vector<HgenTree> trees;
+    std::vector<HgenNode> nodes;
+    std::vector<float> leaves;
+    std::vector<unsigned char> tilted;     // per feature: all of its rects read the tilted integral
+    bool has_tilted = false;
+    size_t nweak() const { return general ? trees.size() : weak.size(); }
 };
 
 // a cascade file of either format: `format` says which model the loader filled (haar.ow / haar.oh hold the window either way)
@@ -68,5 +81,7 @@ struct CascadeFile { int format = NVCA_CASCADE_HAAR; Cascade haar; LbpCascade lb
 // returns NVCA_OK or NVCA_ERR_PARSE / NVCA_ERR_UNSUPPORTED; err gets a message
 int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &err);      // old-format files only
 int parse_cascade_file(const char *text, size_t len, CascadeFile &out, std::string &err); // both formats, by the type_id of the first child of <opencv_storage>
+// the same with load flags (NVCA_LOAD_*; 0: the call above): NVCA_LOAD_HAAR_GENERAL admits trees and tilted features in a new-format HAAR file
+int parse_cascade_file(const char *text, size_t len, unsigned flags, CascadeFile &out, std::string &err);
 
 } // namespace nvca

@@ -248,7 +248,7 @@ std::string word(const XNode *n)
 // takes it, for either feature type: everything in front of the stages and the features.  maxCatCount is checked against the feature
 // type here, before any feature or node is read: Data::read takes a stump's nodes for categorical ones whenever it is not 0.
 struct NewEnvelope { const XNode *stages = nullptr, *features = nullptr; int ow = 0, oh = 0, nstages = 0; bool haar = false; };
-int read_envelope(const XNode &cn, NewEnvelope &e, std::string &err)
+int read_envelope(const XNode &cn, bool general, NewEnvelope &e, std::string &err)
 {
     const XNode *stype = cn.child("stageType"), *ftype = cn.child("featureType"), *hn = cn.child("height"), *wn = cn.child("width");
     const XNode *sparams = cn.child("stageParams"), *fparams = cn.child("featureParams"), *snum = cn.child("stageNum");
@@ -266,7 +266,8 @@ int read_envelope(const XNode &cn, NewEnvelope &e, std::string &err)
     if (!one_int(sparams->child("maxWeakCount"), v)) { err = "stageParams without maxWeakCount"; return NVCA_ERR_PARSE; }
     if (const XNode *md = sparams->child("maxDepth")) {
         if (!one_int(md, v)) { err = "bad <maxDepth>"; return NVCA_ERR_PARSE; }
-        if (v > 1) { err = "weak classifiers with maxDepth > 1 (trees) are not supported"; return NVCA_ERR_UNSUPPORTED; }
+        // (a general HAAR load reads the trees themselves: the header's maxDepth chooses nothing)
+        if (v > 1 && !(general && e.haar)) { err ="weak classifiers with maxDepth > 1 (trees) are not supported"; return NVCA_ERR_UNSUPPORTED; }
     }
     if (!one_int(fparams->child("maxCatCount"), v)) { err = "featureParams without maxCatCount"; return NVCA_ERR_PARSE; }
     if (!e.haar && v != 256) { err = "maxCatCount is not 256 (LBP codes are 8 bits)"; return NVCA_ERR_UNSUPPORTED; }
@@ -321,17 +322,22 @@ int parse_lbp(const NewEnvelope &e, LbpCascade &out, std::string &err)
 
 // featureType HAAR: what Data::read and HaarEvaluator::Feature::read keep of a cascade of stumps on upright features.
 // A stump's internalNodes is "0 -1 featureIdx threshold" (the threshold a real), a feature one to three rects "x y w h weight".
-int parse_hnew(const NewEnvelope &e, HnewCascade &out, std::string &err)
+// `general` (NVCA_LOAD_HAAR_GENERAL): a feature may be tilted -- all of its rects read the tilted integral, CV_TILTED_PTRS --
+// and a weak classifier a tree: internalNodes holds "left right featureIdx threshold" per node, leafValues one value more than nodes.
+// The checks are stricter than Data::read's, so that no walk loops or leaves its tables: a child node lies behind its parent and inside
+// the tree, a leaf index inside [0, nodeCount].  A file that turns out to hold stumps "0 -1" on upright features alone leaves the very
+// model the plain load leaves.
+int parse_hnew(const NewEnvelope &e, bool general, HnewCascade &out, std::string &err)
 {
+    out = HnewCascade();
     out.ow = e.ow; out.oh = e.oh;
-    out.features.clear(); out.weak.clear(); out.stages.clear();
     std::vector<double> dv, lv;
     for (auto &f : e.features->kids) {
         const XNode *rects = f->child("rects"), *tilted = f->child("tilted");
         if (!rects) { err = "feature without <rects>"; return NVCA_ERR_PARSE; }
         int tl = 0;
         if (tilted && !one_int(tilted, tl)) { err = "bad <tilted>"; return NVCA_ERR_PARSE; }
-        if (tl != 0) { err = "tilted features are not supported in a new-format HAAR cascade"; return NVCA_ERR_UNSUPPORTED; }
+        if (tl != 0 && !general) { err = "tilted features are not supported in a new-format HAAR cascade"; return NVCA_ERR_UNSUPPORTED; }
         if (rects->kids.empty() || rects->kids.size() > 3) { err = "feature must have 1 to 3 rects"; return NVCA_ERR_PARSE; }
         HnewFeature hf; memset(&hf, 0, sizeof(hf));
         hf.nrect = (int)rects->kids.size();
@@ -343,23 +349,53 @@ int parse_hnew(const NewEnvelope &e, HnewCascade &out, std::string &err)
             }
             const int *r = hf.rect[k];
             // every corner the evaluator reads exists at every window position
-            if (r[0] < 0 || r[1] < 0 || r[2] <= 0 || r[3] <= 0 || r[0] + r[2] > e.ow || r[1] + r[3] > e.oh) { err = "rect outside the window"; return NVCA_ERR_PARSE; }
+            if (r[0] < 0 || r[1] < 0 || r[2] <= 0 || r[3] <= 0 || r[0] + r[2] > e.ow || (tl == 0 && r[1] + r[3] > e.oh)) { err = "rect outside the window"; return NVCA_ERR_PARSE; }
+            // tilted: the corners (x, y), (x - h, y + h), (x + w, y + w), (x + w - h, y + w + h) lie on the window's own lattice as well
+            if (tl != 0 && (r[0] - r[3] < 0 || r[1] + r[2] + r[3] > e.oh)) { err = "tilted rect outside the window"; return NVCA_ERR_PARSE; }
             if (!std::isfinite(dv[4])) { err = "rect weight is not a finite number"; return NVCA_ERR_PARSE; }
             hf.weight[k] = (float)dv[4];
         }
         out.features.push_back(hf);
+        if (general) { out.tilted.push_back(tl != 0 ? 1 : 0); if (tl != 0) out.has_tilted = true; }
     }
+    bool stumps = true;          // (general) every weak classifier read so far is the stump "0 -1"
     for (auto &st : e.stages->kids) {
         const XNode *sthr = st->child("stageThreshold"), *wk = st->child("weakClassifiers");
         int mwc = 0; double d;
         if (!sthr || !wk || !one_int(st->child("maxWeakCount"), mwc) || !to_double(sthr->text, d)) { err = "stage without maxWeakCount/stageThreshold/weakClassifiers"; return NVCA_ERR_PARSE; }
-        LbpStage ls; ls.first = (int)out.weak.size(); ls.count = (int)wk->kids.size();
+        LbpStage ls; ls.first = (int)(general ? out.trees.size() : out.weak.size()); ls.count = (int)wk->kids.size();
         ls.threshold = (float)d - 1e-5f;                  // THRESHOLD_EPS, subtracted in float
         if (ls.count <= 0) { err = "empty stage"; return NVCA_ERR_PARSE; }
         if (ls.count != mwc) { err = "stage's maxWeakCount disagrees with its weak classifiers"; return NVCA_ERR_PARSE; }
         for (auto &w : wk->kids) {
             const XNode *in = w->child("internalNodes"), *lf = w->child("leafValues");
             if (!in || !lf || !to_doubles(in->text, dv) || !to_doubles(lf->text, lv)) { err = "weak classifier without internalNodes/leafValues"; return NVCA_ERR_PARSE; }
+            if (general) {
+                if (dv.empty() || dv.size() % 4 != 0) { err = "internalNodes is not 'left right featureIdx threshold' per node"; return NVCA_ERR_PARSE; }
+                const size_t nn = dv.size() / 4;
+                if (nn > (size_t)kHgenMaxNodes) { err = "weak classifiers with more than 15 internal nodes are not supported"; return NVCA_ERR_UNSUPPORTED; }
+                if (lv.size() != nn + 1) { err = "leafValues does not hold one value more than internalNodes has nodes"; return NVCA_ERR_PARSE; }
+                HgenTree t; t.first_node = (int)out.nodes.size(); t.nnodes = (int)nn; t.first_leaf = (int)out.leaves.size();
+                for (size_t j = 0; j < nn; j++) {
+                    const double *q = &dv[4 * j];
+                    for (int side = 0; side < 2; side++) {
+                        const double c = q[side];
+                        if (!(c >= -(double)nn && c < (double)nn) || c != floor(c)) { err = c > 0. ? "child node index outside the tree" : "leaf index outside the leaf values"; return NVCA_ERR_PARSE; }
+                        // every walk from the root ends, on the device too: an index at or before the node itself would make the evaluator loop
+                        if (c > 0. && c <= (double)j) { err = "child node index does not lie behind its parent"; return NVCA_ERR_PARSE; }
+                    }
+                    if (!(q[2] >= 0. && q[2] < (double)out.features.size()) || q[2] != floor(q[2])) { err = "featureIdx outside the feature list"; return NVCA_ERR_PARSE; }
+                    if (!std::isfinite(q[3])) { err = "threshold or leaf value is not a finite number"; return NVCA_ERR_PARSE; }
+                    out.nodes.push_back(HgenNode{(int)q[0], (int)q[1], (int)q[2], (float)q[3]});
+                }
+                for (double v : lv) {
+                    if (!std::isfinite(v)) { err = "threshold or leaf value is not a finite number"; return NVCA_ERR_PARSE; }
+                    out.leaves.push_back((float)v);
+                }
+                if (nn != 1 || dv[0] != 0. || dv[1] != -1.) stumps = false;
+                out.trees.push_back(t);
+                continue;
+            }
             if (dv.size() > 4 && dv.size() % 4 == 0 && lv.size() == dv.size() / 4 + 1) { err = "weak classifiers with more than one internal node (trees) are not supported"; return NVCA_ERR_UNSUPPORTED; }
             if (dv.size() != 4 || dv[0] != 0. || dv[1] != -1. || lv.size() != 2) { err = "internalNodes is not '0 -1 featureIdx threshold' with two leaf values"; return NVCA_ERR_PARSE; }
             if (!(dv[2] >= 0. && dv[2] < (double)out.features.size()) || dv[2] != floor(dv[2])) { err = "featureIdx outside the feature list"; return NVCA_ERR_PARSE; }
@@ -371,6 +407,13 @@ int parse_hnew(const NewEnvelope &e, HnewCascade &out, std::string &err)
     }
     if (out.stages.empty()) { err = "cascade has no stages"; return NVCA_ERR_PARSE; }
     if ((int)out.stages.size() != e.nstages) { err = "stageNum disagrees with the stages"; return NVCA_ERR_PARSE; }
+    if (general && stumps && !out.has_tilted) {          // nothing the stump evaluator cannot take: the plain load's model
+        for (const HgenTree &t : out.trees) {
+            const HgenNode &n = out.nodes[(size_t)t.first_node];
+            out.weak.push_back(HnewWeak{n.feature, n.threshold, {out.leaves[(size_t)t.first_leaf], out.leaves[(size_t)t.first_leaf + 1]}});
+        }
+        out.trees.clear(); out.nodes.clear(); out.leaves.clear(); out.tilted.clear();
+    } else if (general) out.general = true;
     return NVCA_OK;
 }
 
@@ -385,16 +428,19 @@ int parse_cascade_xml(const char *text, size_t len, Cascade &out, std::string &e
 
 // cv::CascadeClassifier::load's dispatch (cascadedetect.cpp: Data::read, else the old-format cvLoad): the type_id of the first
 // child of <opencv_storage> decides the branch
-int parse_cascade_file(const char *text, size_t len, CascadeFile &out, std::string &err)
+int parse_cascade_file(const char *text, size_t len, CascadeFile &out, std::string &err) { return parse_cascade_file(text, len, 0u, out, err); }
+
+int parse_cascade_file(const char *text, size_t len, unsigned flags, CascadeFile &out, std::string &err)
 {
+    const bool general = (flags & NVCA_LOAD_HAAR_GENERAL) != 0;
     XNode root;
     if (int rc = parse_root(text, len, root, err)) return rc;
     if (!root.kids.empty() && root.kids[0]->type_id == "opencv-cascade-classifier") {
         NewEnvelope e;
         out.format = NVCA_CASCADE_LBP;
-        if (int rc = read_envelope(*root.kids[0], e, err)) return rc;
+        if (int rc = read_envelope(*root.kids[0], general, e, err)) return rc;
         out.format = e.haar ? NVCA_CASCADE_HAAR_NEW : NVCA_CASCADE_LBP;
-        const int rc = e.haar ? parse_hnew(e, out.hnew, err) : parse_lbp(e, out.lbp, err);
+        const int rc = e.haar ? parse_hnew(e, general, out.hnew, err) : parse_lbp(e, out.lbp, err);
         if (rc == NVCA_OK) { out.haar.ow = e.ow; out.haar.oh = e.oh; }
         return rc;
     }

@@ -284,6 +284,22 @@ struct HnewArgs {
     double area;                    // (ow - 2) * (oh - 2)
 };
 
+// ---- general new-format HAAR cascades (kernels_cascade_hgen.hip): the scan above with tree weak classifiers and
+// tilted features.  A node, wave-uniform (scalar loads, nine dwordx4): its feature's corners as HnewWeakDev has them, at BOTH pitches
+// (off: the planes' P, offt: the stage-0 tile's TP); a tilted feature's corners are (x, y), (x - h, y + h), (x + w, y + w),
+// (x + w - h, y + w + h) -- the same p0 - p1 - p2 + p3 on the level's tilted plane, which is read at pitch P always.  left / right: where
+// a window goes for value < thr / otherwise -- the child's index in the plan's node table (no tree base is added in the walk), or -1
+// for a leaf, whose value is lv[0] / lv[1] then: a leaf is held by the node that ends in it, so the walk needs no leaf table.
+struct alignas(16) HgenNodeDev { int off[12]; int offt[12]; float w[3]; float thr; int left, right, tilted, pad; float lv[2]; int pad2[2]; };
+static_assert(sizeof(HgenNodeDev) == 144, "HgenNodeDev is fetched with wide scalar loads");
+struct HgenWeakDev { int first, count; };          // a weak classifier's nodes in the node table: the root first, children behind parents
+struct HgenArgs {
+    HnewArgs h;                     // (h.gweak / h.tweak unused)
+    const HgenNodeDev *nodes;
+    const HgenWeakDev *weak;        // a stage's first / count index this table
+    const int *tilted;              // the levels' tilted planes, laid out as l.sum; null when no feature is tilted (none is read then)
+};
+
 // ---- detectMultiScale on a small image in one workgroup (kernels_roi.hip)
 struct RoiStep {                  // one ladder step (scale-cascade scan) or one pyramid level (CV_HAAR_SCALE_IMAGE) of a job
     const TStumpRec *trecs;       // the cascade's stumps at this step's factor (levels: factor 1)

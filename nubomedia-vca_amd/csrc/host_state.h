@@ -71,6 +71,8 @@ struct RowCopy {
 struct LbpPlan {
     DevBuf d_blob; LbpArgs args{};
     int format = NVCA_CASCADE_LBP; HnewArgs hnew{};
+    bool general = false, has_tilted = false;  // a general HAAR cascade: the hgen launches on these tables; the pyramid builds tilted planes
+    const HgenNodeDev *hg_nodes = nullptr; const HgenWeakDev *hg_weak = nullptr;      // (in d_blob)
     size_t bit_words = 0, positions = 0;      // stage-0 pass bits (u32 words) and grid positions of all levels
     int lds = 0;                              // bytes of the stage-0 tile (0: the window is too large, stage 0 gathers from the plane)
     const ScaleRec *gscales = nullptr; const int *gpos = nullptr;      // device grouping: a record per level, the levels' output coordinates (in d_blob)

@@ -127,6 +127,10 @@ void launch_hnew_rest(hipStream_t st, const HnewArgs &a, int s0, int s1, int in,
 // every one of them goes to the candidate list, its LevelRec to recs (a.hit_cap records) under the same index
 void launch_lbp_levels(hipStream_t st, const LbpArgs &a, LevelRec *recs, int in, int in_cnt, unsigned max_items);
 void launch_hnew_levels(hipStream_t st, const HnewArgs &a, LevelRec *recs, int in, int in_cnt, unsigned max_items);
+// ---- general new-format HAAR cascades (kernels_cascade_hgen.hip: trees, tilted features): the same three launches on HgenArgs
+void launch_hgen_stage0(hipStream_t st, const HgenArgs &g, int lds);
+void launch_hgen_rest(hipStream_t st, const HgenArgs &g, int s0, int s1, int in, int in_cnt, unsigned max_items);
+void launch_hgen_levels(hipStream_t st, const HgenArgs &g, LevelRec *recs, int in, int in_cnt, unsigned max_items);
 // ---- image-to-overlay and view-* outlines on a device frame (kernels_draw.hip)
 void launch_overlay(hipStream_t st, uint8_t *frame, int W, int H, int stride, const OverlayPlace &p, const OverlayImage &o);
 void launch_draw_shapes(hipStream_t st, uint8_t *data, int w, int h, int stride, int channels, const nvca_shape *d_shapes, int n,

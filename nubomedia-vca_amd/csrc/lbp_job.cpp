@@ -1,8 +1,8 @@
 // lbp_job.cpp -- the launch set of a detectMultiScale job on a new-format cascade: its cached plan (pyramid: pyramid.cpp; tables:
-// lbp_tables.cpp, hnew_tables.cpp) and the evaluator's launches (featureType LBP: kernels_cascade_lbp.hip; HAAR: kernels_cascade_hnew.hip
-// around the LBP file's walk kernel).
+// lbp_tables.cpp, hnew_tables.cpp, hgen_tables.cpp) and the evaluator's launches (featureType LBP: kernels_cascade_lbp.hip; HAAR:
+// kernels_cascade_hnew.hip, or kernels_cascade_hgen.hip for a general cascade, around the LBP file's walk kernel).
 #include "host_state.h"
-#include "hnew_tables.h"
+#include "hgen_tables.h"
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
@@ -31,13 +31,17 @@ int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double
         if (!np->lv.empty()) {
             // the scan grids: what hit_valid / hit_rect check and map a candidate key with
             for (const PyrLevel &L : np->lv) np->det.specs.push_back(level_spec(np->P, L, ow, oh, 1));
-            HnewTables ht; std::string err;
-            if ((rc = hnew ? build_hnew_tables(casc->hnew, np->lv, np->P, ht, err) : build_lbp_tables(casc->lbp, np->lv, np->P, ht.scan, err))) { ctx->set_error(err); return rc; }
+            const bool general = hnew && casc->hnew.general;
+            HgenTables gt; std::string err;
+            HnewTables &ht = gt.base;
+            if ((rc = general ? build_hgen_tables(casc->hnew, np->lv, np->P, gt, err) :
+                      hnew ? build_hnew_tables(casc->hnew, np->lv, np->P, ht, err) : build_lbp_tables(casc->lbp, np->lv, np->P, ht.scan, err))) { ctx->set_error(err); return rc; }
             const LbpTables &t = ht.scan;
             np->det.key_sy = t.key_sy; np->det.key_ss = t.key_ss;
             LbpPlan &lp = np->lbp;
             lp.format = casc->format;
             TableBlob blob;
+            const size_t o_gn = general ? blob.add(gt.nodes.data(), gt.nodes.size() * sizeof(HgenNodeDev)) : 0, o_gw = general ? blob.add(gt.weak.data(), gt.weak.size() * sizeof(HgenWeakDev)) : 0;
             const size_t o_hg = hnew ? blob.add(ht.gweak.data(), ht.gweak.size() * sizeof(HnewWeakDev)) : 0, o_ht = hnew ? blob.add(ht.tweak.data(), ht.tweak.size() * sizeof(HnewWeakDev)) : 0;
             const size_t o_levels = blob.add(t.levels.data(), t.levels.size() * sizeof(LbpLevelDev)), o_tiles = blob.add(t.tiles.data(), t.tiles.size() * sizeof(LbpTile)),
                          o_stages = blob.add(t.stages.data(), t.stages.size() * sizeof(LbpStageDev)), o_gweak = blob.add(t.gweak.data(), t.gweak.size() * sizeof(LbpWeakDev)),
@@ -59,6 +63,11 @@ int lbp_plan(nvca_ctx *ctx, const nvca_cascade *casc, int cols, int rows, double
                 a.gweak = a.tweak = nullptr;
                 h.gweak = (const HnewWeakDev *)(base + o_hg); h.tweak = (const HnewWeakDev *)(base + o_ht);
                 memcpy(h.nr, ht.nr, sizeof(h.nr)); memcpy(h.nrt, ht.nrt, sizeof(h.nrt)); h.area = ht.area;
+                if (general) {
+                    h.gweak = h.tweak = nullptr;
+                    lp.general = true; lp.has_tilted = casc->hnew.has_tilted;
+                    lp.hg_nodes = (const HgenNodeDev *)(base + o_gn); lp.hg_weak = (const HgenWeakDev *)(base + o_gw);
+                }
             }
         }
         pp = store_plan(ctx, key, std::move(np));
@@ -81,7 +90,8 @@ int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, 
     ResultBufs &rb = ws.res[ws.cur_res];
     int rc;
     // (the pyramid launchers write the squared integral with the sum: the HAAR evaluator reads it, the LBP one ignores it)
-    if ((rc = pyr_build(ctx, src, cols, rows, nimg, pp, false))) return rc;
+    // (... and the tilted integral where a general HAAR cascade holds a tilted feature)
+    if ((rc = pyr_build(ctx, src, cols, rows, nimg, pp, pp->lbp.has_tilted))) return rc;
     const LbpPlan &lp = pp->lbp;
     // The job's images share every launch.  Pass bits per image; the two survivor lists are the whole job's, and either holds every
     // grid position of every image: a list that could be too short would drop windows, so it is never sized by an estimate.
@@ -126,17 +136,20 @@ int lbp_launch_set(nvca_ctx *ctx, GeomPlan *pp, const PyrSource &src, int cols, 
         const bool hnew = lp.format == NVCA_CASCADE_HAAR_NEW;
         HnewArgs h = lp.hnew;
         h.l = a; h.sq = ws.ln().sqsum.as<unsigned>(); h.hi_mul = pp->pyr_ok ? 1 : 4;          // (where pyr_build left the levels' high-byte planes)
-        if (hnew) launch_hnew_stage0(ctx->cs(), h, lp.lds); else launch_lbp_stage0(ctx->cs(), a, lp.lds);
+        HgenArgs hg; hg.h = h; hg.nodes = lp.hg_nodes; hg.weak = lp.hg_weak; hg.tilted = lp.has_tilted ? ws.ln().tilted.as<int>() : nullptr;
+        const bool general = lp.general;
+        if (general) launch_hgen_stage0(ctx->cs(), hg, lp.lds); else if (hnew) launch_hnew_stage0(ctx->cs(), h, lp.lds); else launch_lbp_stage0(ctx->cs(), a, lp.lds);
         launch_lbp_walk(ctx->cs(), a);
         int g = 0;          // groups launched: the survivors in front of stage s_end lie in list g & 1, counted by cnt[g]
         for (int s0 = a.tile_stages, len = 2; s0 < s_end && g + 1 < (int)kCnt; s0 += len, len++) {
             // (the last group takes every stage that is left: the counters bound the number of groups)
             const int s1 = g + 2 == (int)kCnt ? s_end : std::min(s_end, s0 + len);
-            if (hnew) launch_hnew_rest(ctx->cs(), h, s0, s1, g & 1, g, (unsigned)entries); else launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)entries);
+            if (general) launch_hgen_rest(ctx->cs(), hg, s0, s1, g & 1, g, (unsigned)entries);
+            else if (hnew) launch_hnew_rest(ctx->cs(), h, s0, s1, g & 1, g, (unsigned)entries); else launch_lbp_rest(ctx->cs(), a, s0, s1, g & 1, g, (unsigned)entries);
             g++;
             if (s1 >= s_end) break;
         }
-        if (levels) { if (hnew) launch_hnew_levels(ctx->cs(), h, cj.d_recs, g & 1, g, (unsigned)entries); else launch_lbp_levels(ctx->cs(), a, cj.d_recs, g & 1, g, (unsigned)entries); }
+        if (levels) { if (general) launch_hgen_levels(ctx->cs(), hg, cj.d_recs, g & 1, g, (unsigned)entries); else if (hnew) launch_hnew_levels(ctx->cs(), h, cj.d_recs, g & 1, g, (unsigned)entries); else launch_lbp_levels(ctx->cs(), a, cj.d_recs, g & 1, g, (unsigned)entries); }
     }
     if (early_done) NVCA_HIP_CHECK(ctx, hipEventRecord(early_done, ctx->cs()));
     if (cj.dev_group) {

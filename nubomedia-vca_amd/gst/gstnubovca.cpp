@@ -157,7 +157,9 @@ static nvca_cascade *acquire_cascade(GpuSlot *g, const std::string &path)
     auto it = g->cascades.find(path);
     if (it != g->cascades.end()) { it->second.refs++; return it->second.h; }
     nvca_cascade *h = nullptr;
-    if (nvca_cascade_load_xml(g->ctx, path.c_str(), &h) != NVCA_OK) return nullptr;
+    // (general: an installed new-format file with tree weak classifiers or tilted features -- haarcascade_frontalface_alt2.xml, the
+    // *_2splits eye files -- loads as well; a file of stumps on upright features is the cascade the plain load makes)
+    if (nvca_cascade_load_xml_ex(g->ctx, path.c_str(), NVCA_LOAD_HAAR_GENERAL, &h) != NVCA_OK) return nullptr;
     // a new-format HAAR file (OpenCV 3 / 4's haarcascade_*.xml): the part elements' face-region searches share one small-image launch
     // a round instead of a launch set each (nothing changes for the other formats; results never depend on it)
     (void)nvca_cascade_set_small_route(h, 1);

@@ -103,7 +103,10 @@ SYMBOLS = [
     "nvca_part_stream_set_input", "nvca_tracker_set_input", "nvca_bgr_to_yuv420", "nvca_draw_shapes_yuv420",
     "nvca_overlay_blend_yuv420", "nvca_cascade_format", "nvca_cascade_dump_lbp", "nvca_cascade_dump_haar_new",
     "nvca_cascade_set_small_route", "nvca_cascade_get_small_route", "nvca_yuv422_to_bgr",
+    "nvca_cascade_load_xml_ex", "nvca_cascade_load_mem_ex", "nvca_cascade_validate_mem_ex", "nvca_cascade_tree_info",
+    "nvca_cascade_dump_haar_tree",
 ]
+LOAD_HAAR_GENERAL = 1
 
 _lib = None
 
@@ -177,6 +180,12 @@ def load():
     if hasattr(L, "nvca_cascade_set_small_route"):      # (NVCA_LIB may name an older library: A/B runs against a parent commit)
         L.nvca_cascade_set_small_route.argtypes = [vp, C.c_int]
         L.nvca_cascade_get_small_route.argtypes = [vp, ip]
+    if hasattr(L, "nvca_cascade_load_mem_ex"):          # (likewise)
+        L.nvca_cascade_load_xml_ex.argtypes = [vp, C.c_char_p, C.c_uint, C.POINTER(vp)]
+        L.nvca_cascade_load_mem_ex.argtypes = [vp, C.c_char_p, C.c_int64, C.c_uint, C.POINTER(vp)]
+        L.nvca_cascade_validate_mem_ex.argtypes = [C.c_char_p, C.c_int64, C.c_uint, ip, ip, ip, ip, C.c_char_p, C.c_int]
+        L.nvca_cascade_tree_info.argtypes = [vp, ip, ip, ip]
+        L.nvca_cascade_dump_haar_tree.argtypes = [vp, ip, C.POINTER(C.c_float), ip, ip, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
     L.nvca_cascade_dump_lbp.argtypes = [vp, ip, ip, C.POINTER(C.c_int32), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
     L.nvca_cascade_dump_haar_new.argtypes = [vp, ip, C.POINTER(C.c_float), ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), ip, C.POINTER(C.c_float)]
     L.nvca_detect_multiscale.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
@@ -324,16 +333,23 @@ class Context:
         return {self.L.nvca_kernel_name(k).decode(): (ms[k], n[k]) for k in range(K_COUNT) if n[k]}
 
     # ---- cascade
-    def load_cascade_xml(self, text):
+    def load_cascade_xml(self, text, general=False, flags=None):
+        """general=True: NVCA_LOAD_HAAR_GENERAL (trees and tilted features in a new-format HAAR file); flags: the raw flag word"""
         if isinstance(text, str):
             text = text.encode()
         h = C.c_void_p()
-        self.check(self.L.nvca_cascade_load_mem(self.h, text, len(text), C.byref(h)))
+        if not general and flags is None:
+            self.check(self.L.nvca_cascade_load_mem(self.h, text, len(text), C.byref(h)))
+        else:
+            self.check(self.L.nvca_cascade_load_mem_ex(self.h, text, len(text), LOAD_HAAR_GENERAL if flags is None else flags, C.byref(h)))
         return Cascade(self, h)
 
-    def load_cascade_file(self, path):
+    def load_cascade_file(self, path, general=False, flags=None):
         h = C.c_void_p()
-        self.check(self.L.nvca_cascade_load_xml(self.h, path.encode(), C.byref(h)))
+        if not general and flags is None:
+            self.check(self.L.nvca_cascade_load_xml(self.h, path.encode(), C.byref(h)))
+        else:
+            self.check(self.L.nvca_cascade_load_xml_ex(self.h, path.encode(), LOAD_HAAR_GENERAL if flags is None else flags, C.byref(h)))
         return Cascade(self, h)
 
     # ---- primitives on host numpy arrays
@@ -639,6 +655,27 @@ class Cascade:
                                                              fidx.ctypes.data_as(ip), thr.ctypes.data_as(fp), leaves.ctypes.data_as(fp),
                                                              ss.ctypes.data_as(ip), st.ctypes.data_as(fp)))
         return dict(size=(ow, oh), rects=rects, weights=wts, rect_counts=counts, feature_idx=fidx, thr=thr, leaves=leaves, stage_sizes=ss, stage_thr=st)
+
+    def tree_info(self):
+        """(nodes, leaves, general) of a new-format HAAR cascade"""
+        a, b, g = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.L.nvca_cascade_tree_info(self.h, C.byref(a), C.byref(b), C.byref(g)))
+        return a.value, b.value, bool(g.value)
+
+    def dump_haar_tree(self):
+        """a new-format HAAR cascade, general or not, in terms that express trees; ERR_ARG for any other cascade"""
+        ow, oh, ns, nw = self.info()
+        nf = self.format()[1]
+        nn, nl, _ = self.tree_info()
+        rects, wts, counts, tilted = np.zeros((nf, 3, 4), np.int32), np.zeros((nf, 3), np.float32), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
+        ncnt, nodes, nthr, leaves = np.zeros(nw, np.int32), np.zeros((nn, 3), np.int32), np.zeros(nn, np.float32), np.zeros(nl, np.float32)
+        ss, st = np.zeros(ns, np.int32), np.zeros(ns, np.float32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        self.ctx.check(self.ctx.L.nvca_cascade_dump_haar_tree(self.h, rects.ctypes.data_as(ip), wts.ctypes.data_as(fp), counts.ctypes.data_as(ip),
+                                                              tilted.ctypes.data_as(ip), ncnt.ctypes.data_as(ip), nodes.ctypes.data_as(ip),
+                                                              nthr.ctypes.data_as(fp), leaves.ctypes.data_as(fp), ss.ctypes.data_as(ip), st.ctypes.data_as(fp)))
+        return dict(size=(ow, oh), rects=rects, weights=wts, rect_counts=counts, tilted=tilted, node_counts=ncnt, nodes=nodes, node_thr=nthr,
+                    leaves=leaves, stage_sizes=ss, stage_thr=st)
 
     def free(self):
         if self.h:

@@ -863,3 +863,180 @@ def haar_old_xml_to_new_xml(xml, style="minimal"):
             thr.append(float(nd.findtext("threshold"))); lv.append(float(nd.findtext("left_val"))); rv.append(float(nd.findtext("right_val")))
         stages.append(dict(features=feats, thresholds=thr, left=lv, right=rv, stage_threshold=float(st.findtext("stage_threshold"))))
     return haar_new_cascade_to_xml(haar_old_to_new_dict(dict(name=c.tag, size=(ow, oh), stages=stages)), style)
+
+
+# ------------------------------------------------------------------ general new-format HAAR cascades: trees, tilted features
+def _tilted_integral_np(img):
+    """cv::integral's third plane, (h + 1) x (w + 1) int64, by its row recurrence T(X, Y) = T(X - 1, Y - 1) + T(X + 1, Y - 1) - T(X, Y - 2)
+    + p(X - 1, Y - 1) + p(X - 1, Y - 2) on an image padded with h + 1 zero columns either side (calibration only; the statement of the
+    definition is tests/haar_tree_reference.py's)"""
+    h, w = img.shape
+    pad = h + 1
+    p = np.zeros((h + 1, w + 2 * pad + 2), np.int64)          # p[y + 1, X]: pixel (X - 1 - pad, y); row 0: the row above the image
+    p[1:, pad + 1:pad + 1 + w] = img
+    T = np.zeros((h + 1, w + 2 * pad + 2), np.int64)
+    for Y in range(1, h + 1):
+        T[Y, 1:-1] = T[Y - 1, :-2] + T[Y - 1, 2:] + p[Y, 1:-1] + p[Y - 1, 1:-1]
+        if Y >= 2:
+            T[Y, 1:-1] -= T[Y - 2, 1:-1]
+    return T[:, pad:pad + w + 1].copy()
+
+
+def _haar_tree_values(S, Q, T, rects, tilted, ow, oh, xs, ys):
+    """_haar_new_values for a feature that may be tilted: its rects on T by CV_TILTED_PTRS, the file's weights as they stand"""
+    if not tilted:
+        return _haar_new_values(S, Q, rects, ow, oh, xs, ys)
+
+    def at(A, x, y):
+        return A[np.ix_(ys + y, xs + x)].astype(np.float64)
+
+    def norm(A):
+        return at(A, 1, 1) - at(A, ow - 1, 1) - at(A, 1, oh - 1) + at(A, ow - 1, oh - 1)
+    vs, vq = norm(S), norm(Q)
+    nf = (ow - 2) * (oh - 2) * vq - vs * vs
+    nf = np.where(nf > 0, np.sqrt(np.maximum(nf, 0)), 1.0)
+    v = sum(wt * (at(T, x, y) - at(T, x - h, y + h) - at(T, x + w, y + w) + at(T, x + w - h, y + w + h)) for (x, y, w, h, wt) in rects)
+    return v / nf
+
+
+def _rand_tree_shape(rng, nn):
+    """[(left, right)] of a binary tree of nn nodes: a child > 0 is a later node, <= 0 the leaf -child (nn + 1 leaves, numbered as they come)"""
+    next_free, next_leaf, out = 1, 0, []
+    for k in range(nn):
+        avail = nn - next_free
+        lo = 1 if (next_free == k + 1 and avail > 0) else 0          # the next node must hang somewhere before its turn comes
+        take = int(rng.randint(lo, min(2, avail) + 1)) if avail > 0 else 0
+        sides = [next_free + j for j in range(take)]
+        next_free += take
+        while len(sides) < 2:
+            sides.append(-next_leaf); next_leaf += 1
+        if rng.rand() < 0.5:
+            sides.reverse()
+        out.append((sides[0], sides[1]))
+    return out
+
+
+def make_haar_tree_cascade(ow=24, oh=24, seed=1, stage_sizes=(3, 4, 5, 6, 7, 8), pass_rate=0.5, tilt_frac=0.25, tree_frac=0.5, max_nodes=3,
+                           calibrate_on=None):
+    """A general new-format HAAR cascade as a dict: size, features=[[(x, y, w, h, weight)]], tilted=[0 | 1 per feature], stages=[dict(
+    threshold, weak=[dict(nodes=[(left, right, feature, threshold)], leaves=[nodes + 1 values])])].  Calibrated the way
+    make_haar_new_cascade is, on `calibrate_on` (default lbp_calibration_images()): a node's threshold is the median of its feature over the
+    sample windows that reach the node, so both of its children are taken; a stage passes about `pass_rate` of the windows that reach it.
+    A workload / parity generator, not a detector."""
+    rng = np.random.RandomState(seed)
+    imgs = lbp_calibration_images() if calibrate_on is None else list(calibrate_on)
+    sample = []
+    for im in imgs:
+        for lev in (im, im[::2, ::2]):
+            if lev.shape[0] > oh and lev.shape[1] > ow:
+                sample.append(_integral_pair_np(lev) + (_tilted_integral_np(lev), np.arange(0, lev.shape[1] - ow, 2), np.arange(0, lev.shape[0] - oh, 2)))
+    alive = [np.ones((len(ys), len(xs)), bool) for (_, _, _, xs, ys) in sample]
+    features, tilted, stages = [], [], []
+    for n in stage_sizes:
+        weak, sums = [], [np.zeros(a.shape, np.float64) for a in alive]
+        for _ in range(n):
+            nn = int(rng.randint(2, max_nodes + 1)) if rng.rand() < tree_frac else 1
+            shape = _rand_tree_shape(rng, nn)
+            leaves = [float(np.float32(rng.uniform(0.3, 1.0) * (1 if rng.rand() < 0.5 else -1))) for _ in range(nn + 1)]
+            at = [np.where(a, 0, -1) for a in alive]          # the node a sample window stands at (-1: not in this tree any more)
+            nodes = []
+            for k in range(nn):
+                tl = 1 if rng.rand() < tilt_frac else 0
+                rects = _rand_tilted_feature(rng, ow, oh) if tl else _rand_upright_feature(rng, ow, oh)
+                vals = [_haar_tree_values(S, Q, T, rects, tl, ow, oh, xs, ys) for (S, Q, T, xs, ys) in sample]
+                here = np.concatenate([v[a == k] for v, a in zip(vals, at)]) if sample else np.zeros(0)
+                allv = np.concatenate([v.ravel() for v in vals]) if sample else np.zeros(1)
+                thr = float(np.float32(np.median(here if len(here) >= 8 else allv)))
+                features.append(rects); tilted.append(tl)
+                nodes.append((shape[k][0], shape[k][1], len(features) - 1, thr))
+                for i, (v, a) in enumerate(zip(vals, at)):
+                    m = a == k
+                    child = np.where(v < thr, shape[k][0], shape[k][1])
+                    for c in set(shape[k]):
+                        if c <= 0:
+                            sums[i][m & (child == c)] += leaves[-c]
+                    a[m] = np.where(child[m] > 0, child[m], -1)
+            weak.append(dict(nodes=nodes, leaves=leaves))
+        reach = np.concatenate([s[a] for s, a in zip(sums, alive)]) if alive else np.zeros(0)
+        st_thr = float(np.float32(np.quantile(reach, 1.0 - pass_rate))) if len(reach) >= 16 else 0.0
+        alive = [a & (s >= st_thr) for s, a in zip(sums, alive)]
+        stages.append(dict(threshold=st_thr, weak=weak))
+    return dict(name="synthetic_haar_tree", size=(ow, oh), features=features, tilted=tilted, stages=stages)
+
+
+def haar_tree_cascade_to_xml(casc, style="traincascade"):
+    """haar_new_cascade_to_xml for a general cascade dict (a stump cascade's dict is taken as well: its weak classifiers are the trees
+    "0 -1"): internalNodes holds "left right featureIdx threshold" per node, leafValues one value more; <tilted> per feature; the
+    "traincascade" header names the depth of the deepest tree as maxDepth"""
+    assert style in ("traincascade", "minimal")
+    ow, oh = casc["size"]
+    tilted = casc.get("tilted", [0] * len(casc["features"]))
+
+    def tree(w):
+        return (w["nodes"], w["leaves"]) if "nodes" in w else ([(0, -1, w["feature"], w["threshold"])], list(w["leaves"]))
+
+    def depth(nodes, k=0):
+        return 1 + max([depth(nodes, c) for c in nodes[k][:2] if k < c < len(nodes)] or [0])          # (a damaged file's children are not followed)
+    mwc = max(len(s["weak"]) for s in casc["stages"])
+    md = max(depth(tree(w)[0]) for s in casc["stages"] for w in s["weak"])
+    o = ['<?xml version="1.0"?>', "<opencv_storage>", '<cascade type_id="opencv-cascade-classifier">', "  <stageType>BOOST</stageType>",
+         "  <featureType>HAAR</featureType>", "  <height>%d</height>" % oh, "  <width>%d</width>" % ow, "  <stageParams>"]
+    if style == "traincascade":
+        o += ["    <boostType>GAB</boostType>", "    <minHitRate>9.9500000476837158e-01</minHitRate>", "    <maxFalseAlarm>5.0000000000000000e-01</maxFalseAlarm>",
+              "    <weightTrimRate>9.4999999999999996e-01</weightTrimRate>", "    <maxDepth>%d</maxDepth>" % md]
+    o += ["    <maxWeakCount>%d</maxWeakCount></stageParams>" % mwc, "  <featureParams>", "    <maxCatCount>0</maxCatCount>"]
+    if style == "traincascade":
+        o += ["    <featSize>1</featSize>", "    <mode>ALL</mode>"]
+    o[-1] += "</featureParams>"
+    o += ["  <stageNum>%d</stageNum>" % len(casc["stages"]), "  <stages>"]
+    for si, st in enumerate(casc["stages"]):
+        if style == "traincascade":
+            o.append("    <!-- stage %d -->" % si)
+        o += ["    <_>", "      <maxWeakCount>%d</maxWeakCount>" % len(st["weak"]), "      <stageThreshold>%s</stageThreshold>" % _f(st["threshold"]), "      <weakClassifiers>"]
+        for w in st["weak"]:
+            nodes, leaves = tree(w)
+            o += ["        <_>", "          <internalNodes>", "            %s</internalNodes>" % " ".join("%d %d %d %s" % (l, r, f, _f(t)) for (l, r, f, t) in nodes),
+                  "          <leafValues>", "            %s</leafValues></_>" % " ".join(_f(v) for v in leaves)]
+        o += ["      </weakClassifiers></_>"]
+    o += ["  </stages>", "  <features>"]
+    for rects, tl in zip(casc["features"], tilted):
+        o += ["    <_>", "      <rects>"]
+        for (x, y, w, h, wt) in rects:
+            o += ["        <_>", "          %d %d %d %d %s</_>" % (x, y, w, h, _f(wt) + ("." if float(wt) == int(wt) and abs(float(wt)) < 1e6 else ""))]
+        o += ["      </rects>", "      <tilted>%d</tilted></_>" % int(tl)]
+    o += ["  </features></cascade>", "</opencv_storage>", ""]
+    return "\n".join(o)
+
+
+def haar_tree_cascade_xml(style="traincascade", **kw):
+    return haar_tree_cascade_to_xml(make_haar_tree_cascade(**kw), style)
+
+
+def haar_old_xml_to_tree_xml(xml, style="minimal"):
+    """An old-format XML text with tree weak classifiers and tilted features (generic_cascade_xml's) as a general new-format HAAR text:
+    one feature per node, in file order; a <left_val> / <right_val> becomes the next leaf of its tree, a <left_node> / <right_node> stays
+    the node index it is; rects, weights, thresholds and values as they stand.  The two formats are evaluated by different arithmetic
+    (no halved tilted weight, its own normaliser and scan), so this carries the workload's shape, not the answers."""
+    import xml.etree.ElementTree as ET
+    c = ET.fromstring(xml)[0]
+    assert c.get("type_id") == "opencv-haar-classifier"
+    ow, oh = (int(v) for v in c.findtext("size").split())
+    features, tilted, stages = [], [], []
+    for st in c.find("stages"):
+        weak = []
+        for tr in st.find("trees"):
+            nodes, leaves = [], []
+            for nd in tr:
+                f = nd.find("feature")
+                features.append([tuple([int(v) for v in r.text.split()[:4]] + [float(r.text.split()[4])]) for r in f.find("rects")])
+                tilted.append(int(f.findtext("tilted")))
+                sides = []
+                for side in ("left", "right"):
+                    if nd.find(side + "_node") is not None:
+                        sides.append(int(nd.findtext(side + "_node")))
+                    else:
+                        sides.append(-len(leaves)); leaves.append(float(nd.findtext(side + "_val")))
+                nodes.append((sides[0], sides[1], len(features) - 1, float(nd.findtext("threshold"))))
+            weak.append(dict(nodes=nodes, leaves=leaves))
+        stages.append(dict(threshold=float(st.findtext("stage_threshold")), weak=weak))
+    return haar_tree_cascade_to_xml(dict(name=c.tag + "_new", size=(ow, oh), features=features, tilted=tilted, stages=stages), style)
